@@ -1,7 +1,10 @@
 """bench.py -- scored triples/sec of the mkb training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+--steps K is the number of timed steps (split into back-to-back windows, see --windows); ms_per_step is the median window's
+time per step.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 
 Workload (BASELINE.json configs[2], the headline): FB15k-237 (14,541 entities, 237 relations, 272,115 training
 triples) + RotatE hidden_dim=1000 (entity rows 2000 fp32), K=256 negatives, batch 1024 rows PER GPU, Adversarial
@@ -115,7 +118,7 @@ def build(device, rank, world, seed=42, parallelism="table-rows", force=False):
     perm = torch.randperm(len(train_np), generator=g).to(device)
     train, weights = train[perm].contiguous(), weights[perm].contiguous()  # shuffled once (per epoch in a real loop):
     return dict(ride=os.environ.get("MKB_BENCH_NO_RIDE", "0") != "1", model=model, sampler=sampler, opt=opt, step=step, train=train, weights=weights, perm=perm, rank=rank,  # batches are views
-                world=world, n_train=len(train_np), exchange=None, dims=dims, trows=trows, table=table)
+                world=world, n_train=len(train_np), exchange=None, dims=dims, trows=trows, table=table, rel=rel_rep)
 
 
 def run_step(ctx, i):
@@ -415,9 +418,18 @@ def measure_traffic(prof_kind, config):
                    + "; ".join(notes)), (names[0].split("(")[0].replace("void ", "") if names else None), step_table
 
 
+def window_sizes(steps, windows):
+    """The `steps` timed steps split into back-to-back windows: `windows` of them (0: one per 20 steps, at most 15), never
+    more windows than steps; the first `steps % n` windows take one step more."""
+    n = windows if windows > 0 else min(15, steps // 20)
+    n = max(1, min(n, steps))
+    q, r = divmod(steps, n)
+    return [q + (j < r) for j in range(n)]
+
+
 def measure(args, device, rank, world, config, parallelism, steps, warmup, profile=True, force=False, windows=1):
-    """Build `config` under `parallelism`, warm up, time exactly `steps` steps between barriers (max over ranks).
-    -> dict with the context, the timing and the HIP-event timing of the dominant kernel class."""
+    """Build `config` under `parallelism`, warm up, time exactly `steps` steps in `window_sizes(steps, windows)` windows, each
+    between barriers (max over ranks).  -> dict with the context, the timing and the HIP-event timing of the dominant kernel class."""
     import torch.distributed as dist
     from mkb_amd import _hip
 
@@ -499,19 +511,23 @@ def measure(args, device, rank, world, config, parallelism, steps, warmup, profi
             gc_log.append({"generation": info["generation"], "ms": round((time.perf_counter() - gc_t[0]) * 1e3, 3), "at": time.perf_counter()})
 
     gc.callbacks.append(gc_cb)
-    # R windows of exactly `steps` steps each, every one between barriers; ms_per_step / value = the MEDIAN window, all of them
-    # are reported (windows_ms).  Per window: the host's enqueue time, the device's own time between two events on the step's
-    # stream, and the largest gap between two consecutive step submissions -- enough to tell a host stall from a device stall.
+    # The `steps` timed steps in R back-to-back windows, every one between barriers; ms_per_step / value = the MEDIAN window's
+    # time per step, all of them are reported (windows_ms).  Per window: the host's enqueue time, the device's own time between
+    # two events on the step's stream, and the largest gap between two consecutive step submissions -- enough to tell a host
+    # stall from a device stall.
+    sizes = window_sizes(steps, windows)
     wins = []
-    sclk = torch.zeros(windows, device=device) if os.environ.get("MKB_BENCH_SCLK") else None
+    sclk = torch.zeros(len(sizes), device=device) if os.environ.get("MKB_BENCH_SCLK") else None
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for w in range(windows):
+    nxt = first  # index of the next batch (consecutive across windows)
+    for w, n_w in enumerate(sizes):
         barrier()
         ev0.record()
         t0 = time.perf_counter()
         prev, gap, gap_at = t0, 0.0, -1
-        for i in range(steps):
-            loss = run_step(ctx, first + w * steps + i)
+        for i in range(n_w):
+            loss = run_step(ctx, nxt)
+            nxt += 1
             now = time.perf_counter()
             if now - prev > gap:
                 gap, gap_at = now - prev, i
@@ -528,17 +544,17 @@ def measure(args, device, rank, world, config, parallelism, steps, warmup, profi
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
-        wins.append({"ms": dt * 1e3, "host_enqueue_ms": t_host * 1e3, "device_ms": ev0.elapsed_time(ev1),
+        wins.append({"steps": n_w, "ms": dt * 1e3, "host_enqueue_ms": t_host * 1e3, "device_ms": ev0.elapsed_time(ev1),
                      "largest_submit_gap_ms": gap * 1e3, "largest_submit_gap_at_step": gap_at,
                      "gc_ms": sum(e["ms"] for e in gc_log if t0 <= e["at"] <= t1)})
         if sclk is not None:
             wins[-1]["sclk_mhz_after"] = float(sclk[w].item())
     gc.callbacks.remove(gc_cb)
-    order_ = sorted(range(windows), key=lambda j: wins[j]["ms"])
-    med = wins[order_[(windows - 1) // 2]]  # (lower median for an even count: an actual window, not a mean of two)
-    dt, t_host = med["ms"] / 1e3, med["host_enqueue_ms"] / 1e3
+    order_ = sorted(range(len(wins)), key=lambda j: wins[j]["ms"] / wins[j]["steps"])
+    med = wins[order_[(len(wins) - 1) // 2]]  # (lower median for an even count: an actual window, not a mean of two)
+    ms_per_step, t_host = med["ms"] / med["steps"], med["host_enqueue_ms"] / 1e3 / med["steps"]  # (t_host: seconds per step)
     if args.breakdown and rank == 0:
-        print(f"host enqueue {t_host / steps * 1e3:.4f} ms/step of {dt / steps * 1e3:.4f} ms/step", file=sys.stderr)
+        print(f"host enqueue {t_host * 1e3:.4f} ms/step of {ms_per_step:.4f} ms/step", file=sys.stderr)
     sampler_note = None
     try:
         ctx["sampler"].check()
@@ -560,10 +576,51 @@ def measure(args, device, rank, world, config, parallelism, steps, warmup, profi
     if prof_kind != "none":
         launches, kms = _hip.profile_read(prof_kind)
         _hip.profile_enable(prof_kind, False)
-    return dict(ctx=ctx, dt=dt, steps=steps, warmup=warmup, loss=float(loss.item()), launches=launches, kms=kms, prof_kind=prof_kind,
-                sampler_note=sampler_note, config=config, t_host=t_host, windows=wins,
+    return dict(ctx=ctx, steps=steps, warmup=warmup, loss=float(loss.item()), launches=launches, kms=kms, prof_kind=prof_kind,
+                sampler_note=sampler_note, config=config, t_host=t_host, windows=wins, next_step=nxt,
                 gc=[{k: e[k] for k in ("generation", "ms")} for e in gc_log],
-                value=world * ctx["rows_per_rank"] * (K + 1) * steps / dt, ms_per_step=dt / steps * 1e3)
+                value=world * ctx["rows_per_rank"] * (K + 1) / (ms_per_step / 1e3), ms_per_step=ms_per_step)
+
+
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: all arrays together
+DUMP_TABLE_BYTES = 32 << 20  # a table larger than this is dumped as a fixed, seeded sample of its rows
+
+
+def dump_outputs(res, path):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST timed step, as DIR/<name>.npy, so that two builds
+    run with the same arguments (hence the same inputs: seeded tables, batches and negatives) can be compared array by array.
+    loss (0-dim), positive_score [B, 1], negative_score [B, K], negative_sample [B, K] (entity ids as float64) and every table
+    after the step (each window ends with the optimizer's flush, so pending row steps are applied).  A table over 32 MB is a
+    seeded sample of its rows, whose ids are in <table>_rows.npy.  N > 1: what rank 0 holds (its shard of a sharded table)."""
+    ctx = res["ctx"]
+    step = ctx["step"]
+    arrays = {"loss": np.asarray(res["loss"], dtype=np.float32)}
+    for name in ("positive_score", "negative_score"):
+        v = getattr(step, name, None)
+        if v is not None:
+            arrays[name] = v.detach().float().cpu().numpy()
+    neg = getattr(step, "negative_sample", None)
+    if neg is not None:
+        arrays["negative_sample"] = neg.detach().cpu().numpy().astype(np.float64)
+    if ctx["trows"]:
+        tables = {"entity_embedding": ctx["table"].data, "relation_embedding": ctx["rel"]}
+    else:
+        tables = dict(ctx["model"].named_parameters())
+    for name, t in tables.items():
+        t = t.detach()
+        if t.numel() * t.element_size() > DUMP_TABLE_BYTES:
+            n = DUMP_TABLE_BYTES // (t[0].numel() * t.element_size())
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], n, replace=False))
+            arrays[f"{name}_rows"] = rows.astype(np.float64)
+            t = t[torch.as_tensor(rows, device=t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, over the {DUMP_MAX_BYTES} byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    return {"dir": path, "arrays": {n: list(a.shape) for n, a in arrays.items()}, "bytes": total}
 
 
 def parallelism_label(ctx, world):
@@ -719,9 +776,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=int(os.environ.get("MKB_BENCH_WINDOWS", "15")),
-                    help="timed windows of --steps steps each, back to back, every one between barriers; ms_per_step / value are "
-                         "the MEDIAN window and all of them are printed (windows_ms)")
+    ap.add_argument("--windows", type=int, default=int(os.environ.get("MKB_BENCH_WINDOWS", "0")),
+                    help="the --steps timed steps are split into this many back-to-back windows (0, the default: one per 20 steps, "
+                         "at most 15), every one between barriers; ms_per_step / value are the MEDIAN window's and all of them are "
+                         "printed (windows_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--preheat-ms", type=float, default=0.0,
                     help="diagnostic: keep the device busy with unrelated torch matmuls for that long right before the warm-up steps "
                          "(tells a clock / power ramp of the device from a warm-up effect of this code's own state)")
@@ -752,6 +812,8 @@ def main():
     ap.add_argument("--mrr-epochs", type=int, default=30,
                     help="after the timed region (N=1 only): train this many more epochs, then filtered MRR on the test set")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.windows < 0:
+        ap.error("--steps must be >= 1, --warmup and --windows >= 0")
     if args.config != "headline":
         args.mrr_epochs, args.no_cpu_baseline = 0, True
 
@@ -840,7 +902,7 @@ def main():
     for par in order:
         try:
             res = measure(args, device, rank, world, args.config, par, args.steps, args.warmup, force=args.force_parallelism,
-                          windows=max(1, args.windows))
+                          windows=args.windows)
             break
         except Exception as e:  # noqa: BLE001
             if world == 1:
@@ -853,6 +915,7 @@ def main():
     if res is None:
         raise SystemExit(f"every partitioning failed: {failures}")
     ctx = res["ctx"]
+    dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     out = None
     if rank == 0:
@@ -873,18 +936,22 @@ def main():
                        "global_batch": world * ctx["rows_per_rank"], "negatives": K,
                        "parallelism": parallelism_label(ctx, world)},
             "loss": res["loss"],
-            # the timed region: `windows` back-to-back windows of `steps` steps, each between barriers; ms_per_step and value
-            # are the MEDIAN window; nothing is dropped -- every window is listed
-            "windows": len(res["windows"]), "windows_ms": [round(w["ms"], 4) for w in res["windows"]],
-            "windows_ms_per_step": [round(w["ms"] / args.steps, 5) for w in res["windows"]],
-            "windows_spread": (max(w["ms"] for w in res["windows"]) - min(w["ms"] for w in res["windows"])) / res["dt"] / 1e3,
-            "t_host_ms_per_step": res["t_host"] / args.steps * 1e3,
+            # the timed region: the `steps` steps in back-to-back windows (windows_steps), each between barriers; ms_per_step and
+            # value are the MEDIAN window's; nothing is dropped -- every window is listed
+            "windows": len(res["windows"]), "windows_steps": [w["steps"] for w in res["windows"]],
+            "windows_ms": [round(w["ms"], 4) for w in res["windows"]],
+            "windows_ms_per_step": [round(w["ms"] / w["steps"], 5) for w in res["windows"]],
+            "windows_spread": (max(w["ms"] / w["steps"] for w in res["windows"])
+                               - min(w["ms"] / w["steps"] for w in res["windows"])) / res["ms_per_step"],
+            "t_host_ms_per_step": res["t_host"] * 1e3,
             "windows_detail": [{k: round(v, 4) if isinstance(v, float) else v for k, v in w.items()} for w in res["windows"]],
             "gc_collections_during_windows": res["gc"],
             "roofline": roofline_of(res, world, want_traffic=default_run and not args.no_traffic and res["prof_kind"] != "none"),
         }
         if out["roofline"] is not None:
             out["roofline"]["step"] = step_roofline(res, world)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if failures:
             out["partitioning_failures"] = failures
         if safety is not None:
@@ -895,7 +962,7 @@ def main():
             comm = getattr(ctx["step"], "_comm", None)
             out["table_rows"] = {"collectives_issued": bool(_collectives_run(world)), "backend": dist.get_backend() if dist is not None and dist.is_initialized() else None,
                                  "issued_by": "libmkb_hip.so (own RCCL communicators: mkb_rows_comm_*)" if comm else "torch.distributed",
-                                 "steps_counted": args.warmup + 8 + args.steps * len(res["windows"])}
+                                 "steps_counted": res["next_step"]}
             if comm:
                 st = comm.stats()
                 out["table_rows"].update(st, host_waits_that_blocked=st["waited_with_idle_stream"],
@@ -957,7 +1024,7 @@ def main():
         return
     ctx = res["ctx"]
     if world == 1 and args.mrr_epochs > 0 and not ctx["trows"]:
-        out["mrr"] = train_and_rank(ctx, args.mrr_epochs, args.warmup + 8 + args.steps * len(res["windows"]))
+        out["mrr"] = train_and_rank(ctx, args.mrr_epochs, res["next_step"])
     if world == 1 and args.config == "headline" and not args.no_variants and not ctx["trows"]:
         out["step_variants"] = step_variants(ctx)
     if not args.no_cpu_baseline and world == 1:

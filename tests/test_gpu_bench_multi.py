@@ -109,15 +109,16 @@ def test_bench_safety_line_of_the_row_sharded_step(timeout):
 
 
 def test_bench_line_reports_the_median_window_and_every_window():
-    """Round 6: the timed region is R back-to-back windows of --steps steps; ms_per_step / value are the MEDIAN window (an actual
-    window: the lower median for an even count) and nothing is dropped: every window is listed with its instruments."""
+    """The timed region is the --steps steps split into R back-to-back windows; ms_per_step / value are the MEDIAN window (an
+    actual window: the lower median for an even count) and nothing is dropped: every window is listed with its instruments."""
     from conftest import ROOT
 
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "6", "--warmup", "2", "--windows", "6", "--config", "wn18rr-rotate", "--no-traffic"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "36", "--warmup", "2", "--windows", "6", "--config", "wn18rr-rotate", "--no-traffic"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
-    assert d["steps"] == 6 and d["warmup"] == 2 and d["windows"] == 6 and len(d["windows_ms"]) == 6 == len(d["windows_detail"])
+    assert d["steps"] == 36 and d["warmup"] == 2 and d["windows"] == 6 and len(d["windows_ms"]) == 6 == len(d["windows_detail"])
+    assert d["windows_steps"] == [6] * 6 and all(w["steps"] == 6 for w in d["windows_detail"])  # the 36 timed steps, no more
     per_step = sorted(w / 6 for w in d["windows_ms"])
     assert abs(d["ms_per_step"] - per_step[2]) < 1e-6 * per_step[2] + 1e-5, (d["ms_per_step"], per_step)  # lower median of six
     assert abs(d["value"] - 1024 * 129 / (d["ms_per_step"] / 1e3)) < 1e-3 * d["value"]                   # B * (K + 1) per step
@@ -125,3 +126,34 @@ def test_bench_line_reports_the_median_window_and_every_window():
         assert {"ms", "host_enqueue_ms", "device_ms", "largest_submit_gap_ms", "largest_submit_gap_at_step", "gc_ms"} <= set(w)
         assert 0 < w["host_enqueue_ms"] <= w["ms"] + 1e-3 and 0 < w["device_ms"] <= w["ms"] + 0.5
     assert d["t_host_ms_per_step"] > 0 and isinstance(d["gc_collections_during_windows"], list)
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 / float64 .npy files, 64 MB at most, the same inputs on every
+    run with the same arguments -- two runs draw the same negatives and end on the same tables."""
+    import numpy as np
+
+    from conftest import ROOT
+
+    dumps = []
+    for run in ("a", "b"):
+        d_out = tmp_path / run
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "7", "--warmup", "2", "--config", "wn18rr-rotate", "--no-traffic",
+               "--dump-outputs", str(d_out)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 7 and sum(d["windows_steps"]) == 7 and d["dump_outputs"]["dir"] == str(d_out)
+        arrays = {p.stem: np.load(p) for p in d_out.glob("*.npy")}
+        assert set(arrays) == set(d["dump_outputs"]["arrays"]) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["loss"].item() == np.float32(d["loss"])
+        assert arrays["negative_score"].shape == (1024, 128) and arrays["negative_sample"].shape == (1024, 128)
+        assert arrays["entity_embedding"].shape == (len(arrays["entity_embedding_rows"]), 1000)  # a row sample of the 40,943 rows
+        dumps.append(arrays)
+    a, b = dumps
+    assert set(a) == set(b)
+    for name in ("negative_sample", "entity_embedding_rows"):
+        assert np.array_equal(a[name], b[name]), name
+    for name in set(a) - {"negative_sample", "entity_embedding_rows"}:
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-6, err_msg=name)

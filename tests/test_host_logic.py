@@ -75,19 +75,33 @@ def test_dataset_sizes_match_reference_doctests():
         assert (ds.n_entity, ds.n_relation, len(ds.train), len(ds.valid), len(ds.test)) == want
 
 
+def _reference_weights(captured):
+    """The reference's arithmetic, ``torch.sqrt(1 / torch.Tensor([count]))`` (datasets/base.py), evaluated on THIS machine on the
+    counts the golden pins.  fp32 ``torch.sqrt`` on the CPU rounds the last bit differently on different CPUs, so the captured
+    weights carry the last bits of the machine that captured them; the counts do not, and come back exactly (1 / w**2)."""
+    n = 1.0 / captured.astype(np.float64) ** 2
+    count = np.rint(n)
+    assert np.abs(n - count).max() < 1e-2
+    return torch.sqrt(1 / torch.from_numpy(count.astype(np.float32))).numpy()
+
+
 def test_train_batches_and_weights_match_reference(golden):
     from mkb_amd import datasets
 
     g = golden("weights.npz")
     for cls in ["Umls", "Fb15k237"]:
         ds = getattr(datasets, cls)(batch_size=256, shuffle=False, seed=42, num_workers=0)
-        np.testing.assert_array_equal(ds.dataset_head.dataset.weights.numpy(), g[f"{cls}/weights"])
+        w = ds.dataset_head.dataset.weights.numpy()
+        np.testing.assert_array_equal(w, _reference_weights(g[f"{cls}/weights"]))  # bit for bit, on any CPU
+        np.testing.assert_array_max_ulp(w, g[f"{cls}/weights"], maxulp=1)            # (0 ulp on the capturing machine)
     ds = datasets.Umls(batch_size=256, shuffle=False, seed=42, num_workers=0)
+    ref = dict(zip(map(tuple, ds.dataset_head.dataset.triples.tolist()), _reference_weights(g["Umls/weights"])))
     for i, data in enumerate(ds):
         if i == 4:
             break
         np.testing.assert_array_equal(data["sample"].numpy(), g[f"Umls/batch{i}/sample"])
-        np.testing.assert_array_equal(data["weight"].numpy(), g[f"Umls/batch{i}/weight"])
+        np.testing.assert_array_equal(data["weight"].numpy(), np.array([ref[tuple(s)] for s in data["sample"].tolist()]))
+        np.testing.assert_array_max_ulp(data["weight"].numpy(), g[f"Umls/batch{i}/weight"], maxulp=1)
         assert data["mode"] == bytes(g[f"Umls/batch{i}/mode"]).decode()
     ds = datasets.Umls(batch_size=256, shuffle=True, seed=42, num_workers=0)  # torch RandomSampler order
     for i, data in enumerate(ds):
@@ -220,3 +234,14 @@ def test_pipeline_host_stager_is_a_plain_copy_off_the_gpu():
     x, w = torch.arange(6).reshape(2, 3), torch.ones(2)
     y, v = s(x, w)
     assert torch.equal(x, y) and torch.equal(w, v) and y.device.type == "cpu"
+
+
+def test_bench_windows_cover_exactly_the_timed_steps():
+    """bench.py --steps K times K steps, no more: the windows split them (one per 20 steps by default, at most 15)."""
+    import bench
+
+    for steps in (1, 6, 19, 20, 36, 199, 300, 3001):
+        for windows in (0, 1, 6, 15, 50):
+            sizes = bench.window_sizes(steps, windows)
+            assert sum(sizes) == steps and min(sizes) >= 1 and max(sizes) - min(sizes) <= 1, (steps, windows, sizes)
+            assert len(sizes) == (min(windows, steps) if windows else max(1, min(15, steps // 20)))
