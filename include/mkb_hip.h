@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MKB_ABI_VERSION 6
+#define MKB_ABI_VERSION 7
 
 typedef enum {
     MKB_OK = 0,
@@ -382,6 +382,26 @@ int mkb_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode,
  * utils-style "score against all entities" callers get it without a [B, N, D] gather).  ABI 6. */
 int mkb_rank_scores(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys,
                     int64_t n_true, int64_t *rank, float *scores, void *ws, int64_t ws_bytes, void *stream);
+
+/* ---- filtered top-k entity prediction ------------------------------------------------------------------
+ * For each query of `sample` [B, 3] int64 (device) the k best candidate entities of the mode's side, on the same all-entity
+ * score block as mkb_rank_scores and the same candidate set as mkb_rank:
+ *   mode: MKB_MODE_HEAD (candidates replace h; the query is (?, r, t)) or MKB_MODE_TAIL (candidates replace t; (h, r, ?)).
+ *   true_keys: as for mkb_rank (ascending; tail-batch (h*n_relation + r)*n_entity + t, head-batch (t*n_relation + r)*n_entity + h);
+ *   every entity whose corrupted triple is a key is left out; n_true == 0 filters nothing.  flags: MKB_TOPK_KEEP_TARGET keeps the
+ *   query's own target (h for head-batch, t for tail-batch) in even when its triple is a key -- exactly the candidates the
+ *   filtered rank is counted on; without it the target column of `sample` is not read as an entity id.
+ *   ids [B, k] int64 / scores [B, k] fp32 out, best first in the order of the filtered rank: NaN first, then higher score, then
+ *   lower entity id among equal scores (a stable descending sort).  scores are bit-identical to mkb_rank_scores' entries.  When
+ *   fewer than k candidates are left, the trailing slots hold id -1 and score -inf.
+ *   1 <= k <= MKB_TOPK_MAX_K (k > n_entity is allowed: padded); B as for mkb_rank; flags other than MKB_TOPK_KEEP_TARGET,
+ *   a bad mode / k / B, null pointers or a short workspace -> MKB_ERR_INVALID before any launch.
+ *   ws: mkb_topk_workspace_bytes(tb, B, k) bytes, 256-byte aligned (0 for a bad k).  No [B, n_entity] output.  ABI 7. */
+#define MKB_TOPK_MAX_K 1024
+#define MKB_TOPK_KEEP_TARGET 1
+int64_t mkb_topk_workspace_bytes(const mkb_tables_t *tb, int64_t B, int k);
+int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true, int k,
+             int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream);
 
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream

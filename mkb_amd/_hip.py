@@ -14,11 +14,12 @@ import os
 
 # MKB_HIP_LIB selects an experimental build of the same ABI (tools/kbench.py); default = the in-tree product library
 _LIB_PATH = pathlib.Path(os.environ.get("MKB_HIP_LIB") or (pathlib.Path(__file__).resolve().parent / "libmkb_hip.so"))
-ABI_VERSION = 6  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a symbol or a signature changes)
+ABI_VERSION = 7  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a symbol or a signature changes)
 
 MODEL_IDS = {"TransE": 0, "RotatE": 1, "ComplEx": 2, "DistMult": 3, "pRotatE": 4}
 MODE_DEFAULT, MODE_HEAD, MODE_TAIL = 0, 1, 2
-ERR_KEY, ERR_EMPTY = -3, -4
+ERR_INVALID, ERR_KEY, ERR_EMPTY = -1, -3, -4
+TOPK_MAX_K, TOPK_KEEP_TARGET = 1024, 1  # MKB_TOPK_MAX_K, MKB_TOPK_KEEP_TARGET
 
 
 def mode_id(mode):
@@ -137,6 +138,9 @@ _SIGNATURES = {
                          c_void_p]),
     "mkb_rank_scores": (c_int, [POINTER(Tables), c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                 c_void_p]),
+    "mkb_topk_workspace_bytes": (c_int64, [POINTER(Tables), c_int64, c_int]),
+    "mkb_topk": (c_int, [POINTER(Tables), c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                         c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -237,17 +237,216 @@ __global__ __launch_bounds__(256) void iota_kernel(int64_t *ids, int64_t n, int6
     if (i < n) ids[i] = i < n_real ? i : n_real - 1;
 }
 
-template <int MODEL, bool HEAD>
-static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *keys, int64_t nk, int64_t *rank,
-                    float *Q, float *S, int64_t *ids, hipStream_t st, float *scores_out) {
-    // the last launch(es) of every route: count the filtered ranks on S (and hand the finished scores out when asked)
-    auto finish = [&](float f0, float f1, int64_t ld) {
-        hipLaunchKernelGGL(rank_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, S, sample, (int)B, tb->n_entity,
-                           tb->n_relation, HEAD ? 1 : 0, keys, nk, rank, f0, f1, ld);
-        if (scores_out)
-            hipLaunchKernelGGL(export_scores_kernel, dim3((unsigned)std::min<int64_t>((tb->n_entity + 255) / 256, 64), (unsigned)B), dim3(256), 0, st,
-                               S, scores_out, tb->n_entity, ld, f0, f1);
-    };
+// ---- filtered top k (mkb_topk) ----------------------------------------------------------------------------------------------------
+// One workgroup per query selects the k best entries of its row of S by the order of ranks_before (NaN first, then higher score,
+// then lower entity id), leaving out the query's true set (the contiguous range of the sorted key array rank_kernel walks; with
+// MKB_TOPK_KEEP_TARGET the target stays in).  The order is that of a composite 64-bit key: the order-preserving 32-bit image of the
+// finished score (NaN on top, -0 folded onto +0 so that the two tie as they compare) in the high word, ~id in the low word.
+//   1. radix select of the k-th largest 32-bit image, 11 + 11 + 10 bits: three passes over the row, each an LDS histogram of the
+//      entries that match the prefix found so far; the filtered entries are then walked (their key range) and taken back out of
+//      the counts, so the filtered set may be any size.  Ends with the threshold image T and `need`, the number of entries at T
+//      that belong to the top k (all of them when the row has fewer than k candidates left: T = 0, below every image).
+//   2. gather: one more pass appends every unfiltered entry above T and at T to an LDS buffer (a binary search of the key range
+//      per appended entry).  More than kTopkCap entries tie at T only for a collapsed row: those are then taken in id order, the
+//      first `need` of them.
+//   3. bitonic sort of the buffer (at most kTopkCap composite keys, descending) in LDS; the first k are written out with their
+//      scores re-read from S and finished as rank_kernel / export_scores_kernel finish them (bit-identical).  Slots past the
+//      candidates left: id -1, score -inf.
+constexpr int kTopkThreads = 256, kTopkCap = 2048;
+
+__device__ __forceinline__ uint32_t order_image(float f) {
+    if (f != f) return 0xFFFFFFFFu;
+    const uint32_t b = f == 0.f ? 0u : __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+struct TopkArgs {
+    const float *S;
+    const int64_t *sample, *keys;
+    int64_t *ids;
+    float *scores;
+    int64_t B, N, R, nk, ld;
+    int head_mode, k, keep_target;
+    float c0, c1;
+};
+
+__global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
+    __shared__ uint32_t s_hist[2048];
+    __shared__ uint32_t s_scan[kTopkThreads];
+    __shared__ uint64_t s_buf[kTopkCap];
+    __shared__ int64_t s_range[2];
+    __shared__ uint32_t s_sel[2], s_cnt;
+    constexpr int T = kTopkThreads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t N = A.N;
+    for (int64_t i = blockIdx.x; i < A.B; i += gridDim.x) {
+        const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
+        const int64_t keep = A.keep_target ? (A.head_mode ? h : t) : -1;
+        const int64_t base = ((A.head_mode ? t : h) * A.R + r) * N;  // as in rank_kernel
+        const float *row = A.S + i * A.ld;
+        if (tid < 2) {
+            const int64_t want = tid == 0 ? base : base + N;
+            int64_t lo = 0, hi = A.nk;
+            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (A.keys[mid] < want) lo = mid + 1; else hi = mid; }
+            s_range[tid] = lo;
+        }
+        __syncthreads();
+        const int64_t klo = s_range[0], khi = s_range[1];
+        auto image = [&](int64_t e) { return order_image(A.c0 + A.c1 * row[e]); };
+        auto filtered = [&](int64_t e) {
+            if (e == keep) return false;
+            int64_t lo = klo, hi = khi;
+            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (A.keys[mid] < base + e) lo = mid + 1; else hi = mid; }
+            return lo < khi && A.keys[lo] == base + e;
+        };
+
+        // 1. radix select
+        uint32_t prefix = 0, mask = 0, need = (uint32_t)A.k;
+        bool all = false;
+        for (int p = 0; p < 3; ++p) {
+            const int shift = p == 0 ? 21 : p == 1 ? 10 : 0;
+            const uint32_t bins = p == 2 ? 1024u : 2048u;
+            for (int b = tid; b < 2048; b += T) s_hist[b] = 0;
+            __syncthreads();
+            for (int64_t e0 = tid; e0 < N; e0 += T * 8) {  // eight strides' loads in flight (see rank_kernel)
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = row[min(e0 + T * j, N - 1)];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const uint32_t u = order_image(A.c0 + A.c1 * v[j]);
+                    if (e0 + T * j < N && (u & mask) == prefix) atomicAdd(&s_hist[(u >> shift) & (bins - 1)], 1u);
+                }
+            }
+            __syncthreads();  // (an entry counted above and taken back below may otherwise meet in the other order: unsigned wrap is harmless, but keep it plain)
+            for (int64_t q = klo + tid; q < khi; q += T) {
+                const int64_t e = A.keys[q] - base;
+                if (e == keep) continue;
+                const uint32_t u = image(e);
+                if ((u & mask) == prefix) atomicSub(&s_hist[(u >> shift) & (bins - 1)], 1u);
+            }
+            __syncthreads();
+            // thread tid owns bins [8 tid, 8 tid + 8): inclusive suffix sums over the threads
+            uint32_t own = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) own += s_hist[8 * tid + j];
+            s_scan[tid] = own;
+            __syncthreads();
+            for (int off = 1; off < T; off <<= 1) {
+                const uint32_t x = tid + off < T ? s_scan[tid + off] : 0u;
+                __syncthreads();
+                s_scan[tid] += x;
+                __syncthreads();
+            }
+            const uint32_t incl = s_scan[tid], total = s_scan[0];
+            if (total < need) {  // (pass 0 only) fewer than k candidates left: take them all
+                all = true;
+                break;
+            }
+            uint32_t above = incl - own;
+            if (above < need && need <= incl) {
+                for (int j = 7; j >= 0; --j) {
+                    const uint32_t c = s_hist[8 * tid + j];
+                    if (above + c >= need) { s_sel[0] = 8 * tid + j; s_sel[1] = need - above; break; }
+                    above += c;
+                }
+            }
+            __syncthreads();
+            prefix |= s_sel[0] << shift;
+            mask |= (bins - 1) << shift;
+            need = s_sel[1];
+            __syncthreads();
+        }
+        const uint32_t thr = all ? 0u : prefix;
+
+        // 2. gather
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        for (int64_t e0 = tid; e0 < N; e0 += T * 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = row[min(e0 + T * j, N - 1)];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int64_t e = e0 + T * j;
+                const uint32_t u = order_image(A.c0 + A.c1 * v[j]);
+                if (e < N && u >= thr && !filtered(e)) {
+                    const uint32_t slot = atomicAdd(&s_cnt, 1u);
+                    if (slot < (uint32_t)kTopkCap) s_buf[slot] = ((uint64_t)u << 32) | (uint32_t)~(uint32_t)e;
+                }
+            }
+        }
+        __syncthreads();
+        uint32_t n = s_cnt;
+        if (n > (uint32_t)kTopkCap) {  // uniform: more than kTopkCap - (k - need) entries tie at T (a collapsed row)
+            __syncthreads();
+            if (tid == 0) s_cnt = 0;
+            __syncthreads();
+            for (int64_t e = tid; e < N; e += T) {  // the k - need < k entries above T
+                const uint32_t u = image(e);
+                if (u > thr && !filtered(e)) {
+                    const uint32_t slot = atomicAdd(&s_cnt, 1u);
+                    if (slot < (uint32_t)A.k) s_buf[slot] = ((uint64_t)u << 32) | (uint32_t)~(uint32_t)e;  // (< k by the select)
+                }
+            }
+            __syncthreads();
+            const uint32_t at = min(s_cnt, (uint32_t)A.k);
+            uint32_t taken = 0;
+            for (int64_t e0 = 0; e0 < N && taken < need; e0 += T) {  // ... and the first `need` ties in id order
+                const int64_t e = e0 + tid;
+                const bool tie = e < N && image(e) == thr && !filtered(e);
+                const uint64_t m = __ballot(tie);
+                __syncthreads();
+                if (lane == 0) s_scan[wave] = (uint32_t)__popcll(m);
+                __syncthreads();
+                uint32_t before = 0, here = 0;
+                for (int w = 0; w < T / 64; ++w) {
+                    before += w < wave ? s_scan[w] : 0u;
+                    here += s_scan[w];
+                }
+                const uint32_t pos = taken + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                if (tie && pos < need && at + pos < (uint32_t)kTopkCap) s_buf[at + pos] = ((uint64_t)thr << 32) | (uint32_t)~(uint32_t)e;
+                taken += here;
+            }
+            n = min(at + min(need, taken), (uint32_t)kTopkCap);
+            __syncthreads();
+        }
+
+        // 3. bitonic sort, descending, of the n <= kTopkCap keys (padded with 0, below every key)
+        uint32_t P = 2;
+        while (P < n) P <<= 1;
+        for (uint32_t j = n + tid; j < P; j += T) s_buf[j] = 0;
+        __syncthreads();
+        for (uint32_t size = 2; size <= P; size <<= 1)
+            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+                for (uint32_t q = tid; q < P / 2; q += T) {
+                    const uint32_t a = 2 * q - (q & (stride - 1)), b = a + stride;
+                    const uint64_t x = s_buf[a], y = s_buf[b];
+                    if ((x < y) == ((a & size) == 0)) { s_buf[a] = y; s_buf[b] = x; }
+                }
+                __syncthreads();
+            }
+        for (int j = tid; j < A.k; j += T) {
+            const int64_t o = i * A.k + j;
+            if ((uint32_t)j < n) {
+                const int64_t e = (int64_t)(uint32_t)~(uint32_t)s_buf[j];
+                A.ids[o] = e;
+                A.scores[o] = A.c0 + A.c1 * row[e];
+            } else {
+                A.ids[o] = -1;
+                A.scores[o] = -INFINITY;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The all-entity score block of B queries into S on one of three routes, then `finish(c0, c1, ld)`: the launch(es) that read S (the
+// filtered ranks of mkb_rank / mkb_rank_scores, the filtered top k of mkb_topk).  S holds raw pair sums (tile route) or finished
+// scores, ld floats apart; the finisher applies c0 + c1 * S[e].
+template <int MODEL, bool HEAD, class Finish>
+static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, float *Q, float *S, int64_t *ids, hipStream_t st,
+                    const Finish &finish) {
     RowArgsR ra{tb->ent, tb->rel, sample, Q, tb->entity_dim, tb->relation_dim, tb->hidden_dim, tb->phase_div};
     hipLaunchKernelGGL((query_build_kernel_r<MODEL, HEAD>), dim3((unsigned)B), dim3(256), 0, st, ra);
     const float c0 = ModelTraits<MODEL>::uses_gamma ? tb->gamma : 0.f, c1 = ModelTraits<MODEL>::uses_gamma ? -1.f : 1.f;
@@ -322,6 +521,33 @@ extern "C" int64_t mkb_rank_workspace_bytes(const mkb_tables_t *tb, int64_t B) {
            (int64_t)(tb->n_entity + 3) * 8;
 }
 
+// run_rank<MODEL, HEAD> for the tables' model and the mode's side
+template <class Finish>
+static int run_all(const mkb_tables_t *tb, const int64_t *sample, int64_t B, bool head, float *Q, float *S, int64_t *ids, hipStream_t st,
+                   const Finish &fin) {
+    switch (tb->model) {
+        case MKB_TRANSE: return head ? run_rank<MKB_TRANSE, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_TRANSE, false>(tb, sample, B, Q, S, ids, st, fin);
+        case MKB_ROTATE: return head ? run_rank<MKB_ROTATE, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_ROTATE, false>(tb, sample, B, Q, S, ids, st, fin);
+        case MKB_COMPLEX: return head ? run_rank<MKB_COMPLEX, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_COMPLEX, false>(tb, sample, B, Q, S, ids, st, fin);
+        case MKB_DISTMULT: return head ? run_rank<MKB_DISTMULT, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_DISTMULT, false>(tb, sample, B, Q, S, ids, st, fin);
+        case MKB_PROTATE: return head ? run_rank<MKB_PROTATE, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_PROTATE, false>(tb, sample, B, Q, S, ids, st, fin);
+    }
+    return set_error(MKB_ERR_INVALID, "unknown model");
+}
+
+// workspace carve-up shared by mkb_rank and mkb_topk: Q [B, De], S [B, N (+3)], the id list [N + 3]
+struct RankWs {
+    float *Q, *S;
+    int64_t *ids;
+};
+static RankWs carve_ws(const mkb_tables_t *tb, int64_t B, void *ws) {
+    RankWs w;
+    w.Q = (float *)ws;
+    w.S = (float *)((unsigned char *)ws + (((size_t)B * tb->entity_dim * 4 + 255) & ~(size_t)255));
+    w.ids = (int64_t *)((unsigned char *)w.S + (((size_t)B * (tb->n_entity + 3) * 4 + 255) & ~(size_t)255));  // [N + 3] 0, 1, ... (tile / GEMM routes)
+    return w;
+}
+
 static int rank_impl(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys,
                      int64_t n_true, int64_t *rank, float *scores, void *ws, int64_t ws_bytes, void *stream) {
     if (int rc = validate_tables(tb)) return rc;
@@ -331,19 +557,19 @@ static int rank_impl(const mkb_tables_t *tb, const int64_t *sample, int64_t B, i
     MKB_REQUIRE(ws_bytes >= mkb_rank_workspace_bytes(tb, B) && (((uintptr_t)ws) & 255) == 0, "workspace too small / unaligned");
     const int NU = tb->model == MKB_ROTATE ? tb->hidden_dim : (int)tb->entity_dim;
     MKB_REQUIRE(NU <= 4 * kWGr, "rows of more than 4096 units are not supported");
-    float *Q = (float *)ws;
-    float *S = (float *)((unsigned char *)ws + (((size_t)B * tb->entity_dim * 4 + 255) & ~(size_t)255));
-    int64_t *ids = (int64_t *)((unsigned char *)S + (((size_t)B * (tb->n_entity + 3) * 4 + 255) & ~(size_t)255));  // [N + 3] 0, 1, ... (tile / GEMM routes)
+    const RankWs w = carve_ws(tb, B, ws);
+    float *S = w.S;
     hipStream_t st = (hipStream_t)stream;
     const bool head = mode == MKB_MODE_HEAD;
-    switch (tb->model) {
-        case MKB_TRANSE: return head ? run_rank<MKB_TRANSE, true>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores) : run_rank<MKB_TRANSE, false>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores);
-        case MKB_ROTATE: return head ? run_rank<MKB_ROTATE, true>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores) : run_rank<MKB_ROTATE, false>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores);
-        case MKB_COMPLEX: return head ? run_rank<MKB_COMPLEX, true>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores) : run_rank<MKB_COMPLEX, false>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores);
-        case MKB_DISTMULT: return head ? run_rank<MKB_DISTMULT, true>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores) : run_rank<MKB_DISTMULT, false>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores);
-        case MKB_PROTATE: return head ? run_rank<MKB_PROTATE, true>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores) : run_rank<MKB_PROTATE, false>(tb, sample, B, true_keys, n_true, rank, Q, S, ids, st, scores);
-    }
-    return set_error(MKB_ERR_INVALID, "unknown model");
+    // count the filtered ranks on S (and hand the finished scores out when asked)
+    auto finish = [&](float f0, float f1, int64_t ld) {
+        hipLaunchKernelGGL(rank_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, S, sample, (int)B, tb->n_entity,
+                           tb->n_relation, head ? 1 : 0, true_keys, n_true, rank, f0, f1, ld);
+        if (scores)
+            hipLaunchKernelGGL(export_scores_kernel, dim3((unsigned)std::min<int64_t>((tb->n_entity + 255) / 256, 64), (unsigned)B), dim3(256), 0, st,
+                               S, scores, tb->n_entity, ld, f0, f1);
+    };
+    return run_all(tb, sample, B, head, w.Q, S, w.ids, st, finish);
 }
 
 extern "C" int mkb_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys,
@@ -355,4 +581,32 @@ extern "C" int mkb_rank_scores(const mkb_tables_t *tb, const int64_t *sample, in
                                int64_t n_true, int64_t *rank, float *scores, void *ws, int64_t ws_bytes, void *stream) {
     MKB_REQUIRE(scores, "null pointer");
     return rank_impl(tb, sample, B, mode, true_keys, n_true, rank, scores, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t mkb_topk_workspace_bytes(const mkb_tables_t *tb, int64_t B, int k) {
+    if (k < 1 || k > MKB_TOPK_MAX_K) return 0;
+    return mkb_rank_workspace_bytes(tb, B);
+}
+
+extern "C" int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true,
+                        int k, int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream) {
+    if (int rc = validate_tables(tb)) return rc;
+    MKB_REQUIRE(sample && ids && scores && ws && (true_keys || n_true == 0) && n_true >= 0, "null pointer");
+    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "mkb_topk needs head-batch or tail-batch");
+    MKB_REQUIRE(k >= 1 && k <= MKB_TOPK_MAX_K, "k must lie in [1, %d]", MKB_TOPK_MAX_K);
+    MKB_REQUIRE((flags & ~MKB_TOPK_KEEP_TARGET) == 0, "unknown flags");
+    MKB_REQUIRE(B > 0 && B <= INT32_MAX, "bad B");
+    MKB_REQUIRE(tb->n_entity <= INT32_MAX, "more than 2^31 - 1 entities");
+    MKB_REQUIRE(ws_bytes >= mkb_topk_workspace_bytes(tb, B, k) && (((uintptr_t)ws) & 255) == 0, "workspace too small / unaligned");
+    const int NU = tb->model == MKB_ROTATE ? tb->hidden_dim : (int)tb->entity_dim;
+    MKB_REQUIRE(NU <= 4 * kWGr, "rows of more than 4096 units are not supported");
+    const RankWs w = carve_ws(tb, B, ws);
+    hipStream_t st = (hipStream_t)stream;
+    const bool head = mode == MKB_MODE_HEAD;
+    auto finish = [&](float f0, float f1, int64_t ld) {
+        TopkArgs A{w.S, sample, true_keys, ids, scores, B, tb->n_entity, tb->n_relation, n_true, ld, head ? 1 : 0, k,
+                   (flags & MKB_TOPK_KEEP_TARGET) ? 1 : 0, f0, f1};
+        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)std::min<int64_t>(B, 1 << 20)), dim3(kTopkThreads), 0, st, A);  // (queries loop past the grid)
+    };
+    return run_all(tb, sample, B, head, w.Q, w.S, w.ids, st, finish);
 }

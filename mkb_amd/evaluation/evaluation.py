@@ -18,7 +18,7 @@ from torch.utils import data
 from .. import _hip
 from ..datasets import base
 from ..models.base import BaseModel
-from ..utils import Bar, Mean
+from ..utils import Bar, Mean, predict_top_k, true_keys
 
 __all__ = ["Evaluation"]
 
@@ -49,17 +49,8 @@ class Evaluation:
 
     # ------------------------------------------------------------------ device ranking (mkb_rank)
     def _true_keys(self, device, n_entity, n_relation):
-        """Sorted keys of all true triples, one ordering per mode (cached on the device)."""
-        cache = getattr(self, "_keys_cache", None)
-        if cache is None or cache[0] != (device, len(self.true_triples)):
-            a = np.asarray(self.true_triples, dtype=np.int64).reshape(-1, 3)
-            h, r, t = a[:, 0], a[:, 1], a[:, 2]
-            tail = np.unique((h * n_relation + r) * n_entity + t)
-            head = np.unique((t * n_relation + r) * n_entity + h)
-            cache = ((device, len(self.true_triples)),
-                     {"head-batch": torch.as_tensor(head, device=device), "tail-batch": torch.as_tensor(tail, device=device)})
-            self._keys_cache = cache
-        return cache[1]
+        """Sorted keys of all true triples, one ordering per mode (cached on the device: utils.true_keys)."""
+        return true_keys(self.true_triples, device, n_entity, n_relation)
 
     def ranks(self, model, dataset, mode, chunk=1024, with_scores=False):
         """Filtered rank (1-based) of every triple of ``dataset`` in ``mode``, computed on the device: int64 tensor.
@@ -93,6 +84,12 @@ class Evaluation:
                                         _hip.stream_ptr()),
                            "mkb_rank")
         return (out, scores) if with_scores else out
+
+    def top_k(self, model, dataset, mode, k, keep_target=True, chunk=1024):
+        """The k best candidates of every triple of ``dataset`` in ``mode`` on the device, filtered by ``true_triples`` (with
+        ``keep_target=True`` the candidate set ``ranks`` counts on: wherever the target's rank is at most k, it sits at that
+        position) -> ``(ids [n, k], scores [n, k])``; see ``utils.predict_top_k``."""
+        return predict_top_k(model, dataset, mode, k, true_triples=self.true_triples, keep_target=keep_target, chunk=chunk)
 
     def _device_ok(self, model):
         units = model.hidden_dim if model.name == "RotatE" else model.entity_dim
