@@ -410,7 +410,7 @@ int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode,
  * their summed duration in milliseconds, and resets the counters.  kernel: 0 = pooled backward (the dq and dx passes
  * in one launch; for ComplEx / DistMult the dQ GEMM),
  * 1 = pooled forward, 2 = Adam, 3 = sampler (draw + filter), 4 = adversarial loss, 5 = general forward,
- * 6 = general backward, 7 = pooled backward dx pass when it is launched alone (the GEMM route, MKB_POOL_SPLIT_BWD).  At most 8192 launches are kept between reads.
+ * 6 = general backward, 7 = pooled backward dx pass when it is launched alone (the GEMM route).  At most 8192 launches are kept between reads.
  */
 #define MKB_PROF_POOL_BWD_Q 0
 #define MKB_PROF_POOL_FWD 1

@@ -403,8 +403,7 @@ __device__ __forceinline__ void replay_finish(const AdamRowArgs &A, int64_t row,
 // one row: LANES lanes x EPL elements per pass.  The first chunk is requested BEFORE the ownership exchange returns (a
 // global atomic round trip ahead of the row's HBM latency otherwise); lanes that turn out to have nothing to do drop it.
 template <int EPL, int UNROLL>
-__device__ __forceinline__ void replay_row_block(const AdamRowArgs &A, int64_t row, bool valid, int lane, int lanes, int *s_old,
-                                                 bool ahead) {
+__device__ __forceinline__ void replay_row_block(const AdamRowArgs &A, int64_t row, bool valid, int lane, int lanes, int *s_old) {
     // whole waves per row: the row index is wave-uniform -- say so, and the four row addresses become one scalar base each plus a
     // 32-bit lane offset instead of four 64-bit vector addresses (registers: the point is a fourth workgroup per CU)
     row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)row);
@@ -416,13 +415,13 @@ __device__ __forceinline__ void replay_row_block(const AdamRowArgs &A, int64_t r
 #endif
     const int k0 = lane * EPL, D = (int)A.D;  // (row lengths fit 31 bits: fill_args)
     RowChunk<EPL> c;
-    if (valid && ahead && k0 < D) replay_load<EPL>(A, row, k0, c);
+    if (valid && k0 < D) replay_load<EPL>(A, row, k0, c);
     __syncthreads();
     if (!valid) return;
     const int old = __builtin_amdgcn_readfirstlane(*s_old);  // (whole waves per row: uniform)
     if (old <= 0 || old >= A.step) return;  // never touched (m = v = 0: identity) or already current
     for (int k = k0; k < D; k += EPL * lanes) {
-        if (!ahead || k != k0) replay_load<EPL>(A, row, k, c);
+        if (k != k0) replay_load<EPL>(A, row, k, c);
         replay_finish<EPL, UNROLL>(A, row, k, old, A.step, c);
     }
 }
@@ -452,7 +451,6 @@ __global__ __launch_bounds__(kCatchThreads) void adam_rows_catchup_kernel(AdamRo
         return;
     }
     __shared__ int s_old2[16];
-    const bool ahead = A.ids || A.seg_pool || A.own_ids;  // (a flush walks every row, most of them with nothing pending: no guessing there)
     const int rpb = A.rows_per_block, lanes = kCatchThreads / rpb;
     const int sub = (int)threadIdx.x / lanes, lane = (int)threadIdx.x - sub * lanes;
     const int64_t r = bid * rpb + sub;
@@ -467,17 +465,16 @@ __global__ __launch_bounds__(kCatchThreads) void adam_rows_catchup_kernel(AdamRo
             row = (int)(e % A.own_world) == A.own_rank ? e / A.own_world : -1;
         } else if (A.own_ids) row = A.ids[r - A.own_n];
         else if (A.ids) row = A.ids[r];
-        else if (A.seg_pool) row = r < A.seg_P ? A.seg_pool[r]
-                                 : (r < A.seg_P + A.seg_B ? A.seg_sample[3 * (r - A.seg_P)]
-                                                          : A.seg_sample[3 * (r - A.seg_P - A.seg_B) + 2]);
-        else row = r;
+        else row = r < A.seg_P ? A.seg_pool[r]  // (a whole-table flush is adam_rows_flush_kernel's)
+                               : (r < A.seg_P + A.seg_B ? A.seg_sample[3 * (r - A.seg_P)]
+                                                        : A.seg_sample[3 * (r - A.seg_P - A.seg_B) + 2]);
     }
     // a negative id = "not a row of this table" (an entry another rank owns): skipped.  So is an id past the table (n_table is set
     // whenever the rows come from an id list): the caller's id check raises the reference's IndexError for it afterwards
     // (mkb_check_ids sets its flag asynchronously) -- the replay must not have written p / m / v / last out of bounds by then
     if (row < 0 || (A.n_table > 0 && row >= A.n_table)) { valid = false; row = 0; }
-    if (A.vec4) replay_row_block<4, UNROLL>(A, row, valid, lane, lanes, &s_old2[sub], ahead);
-    else replay_row_block<2, UNROLL>(A, row, valid, lane, lanes, &s_old2[sub], ahead);
+    if (A.vec4) replay_row_block<4, UNROLL>(A, row, valid, lane, lanes, &s_old2[sub]);
+    else replay_row_block<2, UNROLL>(A, row, valid, lane, lanes, &s_old2[sub]);
 }
 
 // A flush (every row of the table, no id list, no riders) is a stream over the whole table: p, m, v of every row with pending
@@ -638,7 +635,6 @@ static int attach_rider(AdamRowArgs &A, const mkb_adam_dense_t *rider, float lr,
 
 // mean gap between two visits of a row = table rows / rows a launch lists: short gaps take the lean replay (see the kernel)
 static bool short_gaps(const AdamRowArgs &A) {
-    if (const char *e = getenv("MKB_ADAM_UNROLL")) return atoi(e) == 1;  // A/B switch (read per call)
     return A.n_table > 0 && A.n_batch_rows > 0 && (int64_t)A.n_table < (int64_t)12 * A.n_batch_rows;
 }
 
@@ -660,8 +656,7 @@ static int rows_advance(float *param, float *grad, float *exp_avg, float *exp_av
     set_row_blocks(A, n, (ids || own_ids) ? n_rows : 0);  // (a flush walks the whole table anyway)
     n = A.n_ids;
     int64_t extra = 0;
-    static const bool no_flush_kernel = getenv("MKB_ADAM_NO_FLUSH_KERNEL") != nullptr;  // A/B switch
-    if (!ids && !own_ids && A.n_rows_listed > 0 && A.n_rows_listed == A.n_batch_rows && !no_flush_kernel) {  // the whole table
+    if (!ids && !own_ids && A.n_rows_listed > 0) {  // the whole table
         if (int rc = attach_rider(A, rider, lr, beta1, beta2, 256, &extra)) return rc;
         ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
         hipLaunchKernelGGL(adam_rows_flush_kernel, dim3((unsigned)(A.n_rows_listed + extra)), dim3(256), 0, (hipStream_t)stream, A);

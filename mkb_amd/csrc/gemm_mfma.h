@@ -664,7 +664,7 @@ static int launch_gemm(GemmArgs G, hipStream_t st, float *partials = nullptr, Ge
     const bool to_slices = slices_cap > 0 && EPI == GEMM_STORE && slices_used;
     if (slices_used) *slices_used = 1;
     {   // 128 x 128 / 128 x 64 tiles (4 / 2 accumulators per wave) when the operands allow 16-byte loads
-        static const bool off = getenv("MKB_GEMM_NO128") != nullptr;  // A/B switch
+        const bool off = getenv("MKB_GEMM_NO128") != nullptr;  // read per call, as in launch_gemm_bwd_pair
         const bool al = (((uintptr_t)G.A | (uintptr_t)G.B) & 15) == 0 && G.lda % 4 == 0 && G.ldb % 4 == 0 && G.M % 4 == 0 &&
                         G.N % 4 == 0 && G.K % 4 == 0;
         const int tiles128 = ((G.M + 127) / 128) * ((G.N + 127) / 128);
@@ -675,8 +675,7 @@ static int launch_gemm(GemmArgs G, hipStream_t st, float *partials = nullptr, Ge
             int ks = 1;
             // workgroups wanted: ~1 per CU by default; the score product asks for 2 (want_wg = 500: a lone 4-wave workgroup leaves
             // each SIMD's matrix pipe idle during its staging; measured 37 -> 29 us, the split-K sum rides the loss rows anyway)
-            static const int env_wg = getenv("MKB_GEMM_MIN_WG") ? atoi(getenv("MKB_GEMM_MIN_WG")) : 0;  // experiment knob
-            const int min_wg = env_wg ? env_wg : (want_wg ? want_wg : 200);
+            const int min_wg = want_wg ? want_wg : 200;
             while (tiles * ks < min_wg && ks < max_ks && G.K / (ks * 2) >= 96 && (!to_slices || ks * 2 <= slices_cap)) ks *= 2;
             G.ksplit = ks;
             if (to_slices) *slices_used = ks;
@@ -768,7 +767,7 @@ static int launch_gemm(GemmArgs G, hipStream_t st, float *partials = nullptr, Ge
 static int launch_gemm_bwd_pair(GemmArgs GQ, int slices_cap, int *slices_used, GemmArgs GX, float *partials, GemmTail *x_tail,
                                 hipStream_t st, bool *done) {
     *done = false;
-    const bool off = getenv("MKB_GEMM_NO128") != nullptr || getenv("MKB_GEMM_NO_PAIR") != nullptr;  // A/B switches (read per call: the tests flip them within one process)
+    const bool off = getenv("MKB_GEMM_NO128") != nullptr || getenv("MKB_GEMM_NO_PAIR") != nullptr;  // (read per call: the tests flip them within one process)
     const char *bx = getenv("MKB_GEMM_BF16X3");
     if (off || !(bx ? bx[0] == '1' : kGemmBf16x3Default) || !partials || !slices_used || slices_cap < 1) return MKB_OK;
     struct Plan { bool ok, narrow; int ks, tn, mx, ny; size_t lds; };
@@ -784,10 +783,9 @@ static int launch_gemm_bwd_pair(GemmArgs GQ, int slices_cap, int *slices_used, G
         P.narrow = tiles128 < 200;
         P.tn = P.narrow ? 64 : 128;
         const int tiles = P.narrow ? ((G.M + 127) / 128) * ((G.N + 63) / 64) : tiles128;
-        static const int env_wg = getenv("MKB_GEMM_MIN_WG") ? atoi(getenv("MKB_GEMM_MIN_WG")) : 0;
         // (short rows -- DistMult's 1000 floats -- leave few tiles: split K further there: 26.5 -> 23.4 us for its pair; the
         // 2000-float rows of ComplEx lose with more splits, 42 -> 49 us: their partials are what the extra workgroups move)
-        const int min_wg = env_wg ? env_wg : (G.N <= 1024 ? 400 : 200);
+        const int min_wg = G.N <= 1024 ? 400 : 200;
         while (tiles * P.ks < min_wg && P.ks < 8 && G.K / (P.ks * 2) >= 96 && (cap <= 0 || P.ks * 2 <= cap)) P.ks *= 2;
         P.mx = (G.M + 127) / 128; P.ny = (G.N + P.tn - 1) / P.tn;
         P.lds = (size_t)3 * (128 + P.tn) * kBfPitch + (size_t)(((G.K + P.ks - 1) / P.ks + 31) / 32 * 32) * 4;

@@ -18,7 +18,6 @@
 #include "score_pool_tile.h"  // the pooled forward's outer-product register tile, for the all-entity block of RotatE / TransE
 #include "gemm_mfma.h"        // ... and the matrix-core product for ComplEx / DistMult, whose score is a dot product
 
-#include <stdlib.h>
 #include <algorithm>
 
 namespace mkb {
@@ -452,12 +451,11 @@ static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, fl
     const float c0 = ModelTraits<MODEL>::uses_gamma ? tb->gamma : 0.f, c1 = ModelTraits<MODEL>::uses_gamma ? -1.f : 1.f;
     // RotatE / TransE: the all-entity block on the pooled forward's register tile (score_pool_tile.h: 64 queries x 64 entities per
     // workgroup, 4 x 4 pairs per lane, operands staged through LDS -- no per-candidate wave reduction at all), the "pool" being
-    // every entity in order and nothing masked; S then holds raw pair sums, finished by the rank kernel.  MKB_RANK_TILE=0: A/B.
+    // every entity in order and nothing masked; S then holds raw pair sums, finished by the rank kernel.
     if constexpr (ModelTraits<MODEL>::cplx_pair || MODEL == MKB_TRANSE) {
-        static const bool tile_off = getenv("MKB_RANK_TILE") && getenv("MKB_RANK_TILE")[0] == '0';
         const bool shape_ok = ModelTraits<MODEL>::cplx_pair ? (tb->hidden_dim % 4 == 0 && tb->hidden_dim >= 32)
                                                             : (tb->entity_dim % 4 == 0 && tb->entity_dim >= 64);
-        if (!tile_off && shape_ok && (((uintptr_t)tb->ent | (uintptr_t)Q | (uintptr_t)S) & 15) == 0 && ids && tb->n_entity < (1 << 30)) {
+        if (shape_ok && (((uintptr_t)tb->ent | (uintptr_t)Q | (uintptr_t)S) & 15) == 0 && ids && tb->n_entity < (1 << 30)) {
             hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((tb->n_entity + 255) / 256)), dim3(256), 0, st, ids, tb->n_entity, tb->n_entity);
             PoolArgs P{};
             P.ent = tb->ent; P.Q = Q; P.pool = ids; P.B = (int)B; P.P = (int)tb->n_entity; P.d = tb->hidden_dim; P.De = tb->entity_dim;
@@ -474,11 +472,10 @@ static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, fl
     // ComplEx / DistMult: score = <q, x> over the entity row, so the all-entity block is ONE product Q [B, De] . E^T [De, N] on the
     // matrix cores (gemm_mfma.h: 128-row tiles, fp32 operands split three ways on the bf16 pipe as in the pooled forward of these
     // models).  N is padded to a multiple of 4 through the id list (the tail repeats the last row; the rank kernel never reads it),
-    // S rows are Npad floats apart.  Ragged last batches (B % 4 != 0) keep the lane-owns-dims kernel.  MKB_RANK_GEMM=0: A/B.
+    // S rows are Npad floats apart.  Ragged last batches (B % 4 != 0) keep the lane-owns-dims kernel.
     if constexpr (MODEL == MKB_COMPLEX || MODEL == MKB_DISTMULT) {
-        static const bool gemm_off = getenv("MKB_RANK_GEMM") && getenv("MKB_RANK_GEMM")[0] == '0';
         const int64_t Npad = (tb->n_entity + 3) & ~(int64_t)3;
-        if (!gemm_off && ids && B % 4 == 0 && tb->entity_dim % 4 == 0 && tb->entity_dim >= 16 && B >= 32 &&
+        if (ids && B % 4 == 0 && tb->entity_dim % 4 == 0 && tb->entity_dim >= 16 && B >= 32 &&
             (((uintptr_t)tb->ent | (uintptr_t)Q | (uintptr_t)S) & 15) == 0 && Npad < (1 << 30)) {
             hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, st, ids, Npad, tb->n_entity);
             GemmArgs G{};
@@ -500,10 +497,8 @@ static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, fl
     if ((int64_t)slices > tb->n_entity) slices = (int)tb->n_entity;
     dim3 grid((unsigned)tiles, (unsigned)slices);
     const int NU = tb->model == MKB_ROTATE ? tb->hidden_dim : (int)tb->entity_dim;
-    static const bool narrow_off = getenv("MKB_RANK_WIDE") != nullptr;  // A/B switch: 16 waves x 1 unit per lane as before
     if (NU <= kWGr / 2) hipLaunchKernelGGL((all_fwd_kernel<MODEL, HEAD, 1>), grid, dim3(kWGr), 0, st, A);
-    else if (NU <= kWGr && !narrow_off) hipLaunchKernelGGL((all_fwd_kernel<MODEL, HEAD, 2, 8>), grid, dim3(512), 0, st, A);
-    else if (NU <= kWGr) hipLaunchKernelGGL((all_fwd_kernel<MODEL, HEAD, 1>), grid, dim3(kWGr), 0, st, A);
+    else if (NU <= kWGr) hipLaunchKernelGGL((all_fwd_kernel<MODEL, HEAD, 2, 8>), grid, dim3(512), 0, st, A);
     else if (NU <= 2 * kWGr) hipLaunchKernelGGL((all_fwd_kernel<MODEL, HEAD, 2>), grid, dim3(kWGr), 0, st, A);
     else hipLaunchKernelGGL((all_fwd_kernel<MODEL, HEAD, 4>), grid, dim3(kWGr), 0, st, A);
     finish(0.f, 1.f, tb->n_entity);

@@ -298,9 +298,8 @@ extern "C" int mkb_rows_route(const int64_t *ids, int64_t n, int sample_layout, 
     const int64_t reqs = sample_layout ? 2 * n : n;
     int cap = 2;
     while (cap < 2 * reqs && cap <= 8192) cap <<= 1;
-    static const bool no_merge = getenv("MKB_ROWS_NO_MERGE") != nullptr;  // A/B switch
     size_t lds = 0;
-    if (cap <= 8192 && !no_merge) {  // 12 bytes per slot: 96 KB at the limit (4096 requests = 2048 triples per rank and step)
+    if (cap <= 8192) {  // 12 bytes per slot: 96 KB at the limit (4096 requests = 2048 triples per rank and step)
         A.merge_cap = cap;
         lds = (size_t)cap * 12;
         static LdsOptIn grant;

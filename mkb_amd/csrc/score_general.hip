@@ -348,8 +348,7 @@ static int bwd2_scratch(const mkb_tables_t *tb, int64_t B, int64_t K, Bwd2Scratc
     return MKB_OK;
 }
 static bool bwd2_applies(const mkb_tables_t *tb, const int64_t *cand, int64_t B, int64_t K) {
-    static const bool one_pass = getenv("MKB_GENERAL_ONE_PASS") != nullptr;  // A/B: per-pair atomics
-    return cand && K > 1 && B * K <= INT32_MAX && tb->n_entity <= INT32_MAX && !one_pass;
+    return cand && K > 1 && B * K <= INT32_MAX && tb->n_entity <= INT32_MAX;
 }
 
 template <int MODEL>

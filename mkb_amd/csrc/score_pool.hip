@@ -341,7 +341,8 @@ static int units_of(const mkb_tables_t *tb) { return tb->model == MKB_ROTATE ? t
 // Kernel configuration for a table shape: units per lane (vector width of the loads), waves per workgroup, and how
 // many workgroups share a row tile / position tile so that the grid fills 256 CUs with 16-32 waves each.
 // ComplEx / DistMult: the pair function is a dot product, so the pooled block is three dense fp32 GEMMs on the matrix
-// cores (gemm_mfma.h) instead of the lane-owns-dims VALU kernels.  MKB_POOL_NO_MFMA=1 keeps the VALU kernels (A/B).
+// cores (gemm_mfma.h) instead of the lane-owns-dims VALU kernels.  MKB_POOL_NO_MFMA=1 keeps the VALU kernels (the tests'
+// independent route).
 // (The two per-call switches -- MKB_POOL_NO_MFMA, MKB_POOL_DENSE -- change the workspace layout.  Callers cache a workspace
 // per table shape, so mkb_pool_step_workspace_bytes reports the LARGEST layout over the switches' settings: g_force_* let it
 // ask pick_config for each.  Found in round 4 by filling freed device memory with NaN between calls: a workspace sized for the
@@ -361,9 +362,8 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
     L.rel_copies = 1;
     L.n_entity = tb->n_entity;
     {
-        static const bool off = getenv("MKB_POOL_NO_REL_COPIES") != nullptr;  // A/B switch
         const int64_t per_rel = tb->n_relation > 0 ? B / tb->n_relation : 0;
-        if (!off && per_rel >= 16 && L.rel_elems > 0) {
+        if (per_rel >= 16 && L.rel_elems > 0) {
             int64_t c = per_rel / 4;
             const int64_t cap = (1 << 18) / L.rel_elems;  // 1 MB of floats
             if (c > cap) c = cap;
@@ -387,12 +387,6 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
     if (L.kpt == 1) L.nw = lanes <= 64 ? 1 : (lanes <= 128 ? 2 : (lanes <= 256 ? 4 : 16));
     else if (L.kpt == 2) L.nw = lanes <= 64 ? 1 : (lanes <= 128 ? 2 : (lanes <= 256 ? 4 : (lanes <= 512 ? 8 : 16)));
     else L.nw = 16;
-    if (const char *e = getenv("MKB_POOL_CFG")) {  // experiment knob: "kpt,nw"
-        int k = 0, n = 0;
-        if (sscanf(e, "%d,%d", &k, &n) == 2 && (k == 1 || (k == 2 && even2) || (k == 4 && even4)) && (int64_t)k * n * 64 >= NU) {
-            L.kpt = k; L.nw = n;
-        }
-    }
     // forward: 4 units per lane when the row allows it (measured 91 -> 77 us at the headline shape: the per-position
     // wave reduction is amortised over twice the pair evaluations); the backward kernels gain nothing from it
     L.fkpt = L.kpt; L.fnw = L.nw;
@@ -402,21 +396,18 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
     // 257 .. 1024 complex dims), whole 64-position tiles in the prefix (K = P / 2 >= 64) and 16-byte rows.
     L.tile = 0; L.tile_kd = 0; L.tile_ks = 1; L.tile_fringe_slices = 1;
     {
-        static const bool off = getenv("MKB_POOL_TILE") && getenv("MKB_POOL_TILE")[0] == '0';  // A/B switch
         const int64_t Kd = (P / 2) / 64 * 64;
         // (round 5: TransE's |q - x| on the same tile -- its "dims" are pairs of floats, so that a chunk is 32 floats either way)
         const bool te = tb->model == MKB_TRANSE && De % 4 == 0;
         const int64_t dt = cp ? d : De / 2;
-        if (!off && (te || (cp && d % 4 == 0)) && !use_mfma(tb) && al16 && L.fnw == 4 && (L.fkpt == 4 || L.fkpt == 2) && Kd >= 64 && B >= 64) {
+        if ((te || (cp && d % 4 == 0)) && !use_mfma(tb) && al16 && L.fnw == 4 && (L.fkpt == 4 || L.fkpt == 2) && Kd >= 64 && B >= 64) {
             L.tile = 1;
             L.tile_kd = (int)Kd;
             const int tiles = (int)((B + 63) / 64) * (int)(Kd / 64);
             int ks = 1;
             while (tiles * ks < 512 && ks < 16 && dt / (ks * 2) >= 32) ks *= 2;  // fill the chip; >= 2 chunks of 16 dims per split
-            if (const char *e = getenv("MKB_POOL_TILE_KS")) { const int v = atoi(e); if (v >= 1 && v <= 16) ks = v; }
             L.tile_ks = ks;
             L.tile_fringe_slices = 2;
-            if (const char *e = getenv("MKB_POOL_TILE_FSL")) { const int v = atoi(e); if (v >= 1 && v <= 16) L.tile_fringe_slices = v; }
         }
     }
     const int target = 256 * 16 / L.nw;  // workgroups for ~16 waves per CU
@@ -441,13 +432,11 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
     // blocks of <= 64 * halves (LDS accumulator <= 128 KB), row tiles into groups of 16 waves.  Position blocks are doubled
     // until the grid holds ~4096 waves (16 per CU); each block costs one dQ partial buffer.
     {
-        const char *e = getenv("MKB_POOL_BWD1");  // A/B switch: 0 = the two-pass merged kernel
-        L.bwd1 = (!L.mfma && !(e && e[0] == '0')) ? 1 : 0;
+        L.bwd1 = L.mfma ? 0 : 1;
         L.row_groups = 0; L.cplx = cp ? 1 : 0; L.pb_halves = 0; L.tiles_per_wave = 1;
         // units per lane of the single-pass backward: 2 (1 for odd rows); real-valued models with long rows take 4 -- the
         // same 4 floats per lane and position as RotatE's two complex dims, half the per-position bookkeeping of 2
-        static const bool no_k4 = getenv("MKB_POOL_BWD1_NO_K4") != nullptr;  // A/B switch
-        const int k1 = (!cp && k4 && NU >= 512 && !no_k4) ? 4 : (L.kpt >= 2 ? 2 : 1), nc = k1 * (cp ? 2 : 1);
+        const int k1 = (!cp && k4 && NU >= 512) ? 4 : (L.kpt >= 2 ? 2 : 1), nc = k1 * (cp ? 2 : 1);
         L.bkpt = k1;
         const int lanes1 = (NU + k1 - 1) / k1;
         L.dim_slices = (lanes1 + 63) / 64;
@@ -455,8 +444,11 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
         int npb = 1;
         while (((P + npb - 1) / npb + 63) / 64 > max_halves) npb *= 2;
         while (npb < kMaxSlices && (int64_t)row_tiles * L.dim_slices * npb < 4096 && (P + npb - 1) / npb > 32) npb *= 2;
-        if (const char *q = getenv("MKB_POOL_PBLOCKS")) { const int v = atoi(q); if (v >= npb && v <= kMaxSlices && (v & (v - 1)) == 0) npb = v; }
-        if (npb > kMaxSlices) L.bwd1 = 0;
+        if (npb > kMaxSlices) {  // too many positions for the single-pass kernel: the two-pass one (pool_bwd_kernel)
+            L.bwd1 = 0;
+            // (compiled only where a shape can reach it; the check keeps a route with no kernel from being picked)
+            if (!L.mfma && !pool_two_pass_compiled(tb->model, L.kpt)) return false;
+        }
         if (L.bwd1) {
             L.q_slices = npb;
             // halves: ROUNDED UP to a power of two.  The kernel cuts its 16 chunks into 16 / halves lanes per half, the seed
@@ -489,17 +481,15 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
         }
         // Small problems: when the single-pass grid would be a handful of 16-wave workgroups, its ring and its prologue ARE the
         // launch (Umls TransE-64, K 16, B 256: two workgroups, 43 us for 0.5 MFLOP).  One wave per (row tile, <= 64 positions,
-        // 64 * kpt units) instead: pool_bwd_wave_kernel; position slices until ~1024 waves are in flight.  MKB_POOL_SMALL=0: A/B.
+        // 64 * kpt units) instead: pool_bwd_wave_kernel; position slices until ~1024 waves are in flight.
         L.small = 0; L.skpt = 1; L.schunks = 1;
         if (L.bwd1) {
-            const char *e = getenv("MKB_POOL_SMALL");
             const int groups1 = (row_tiles + 15) / 16;
             const int skpt = L.kpt >= 2 ? 2 : 1;
             const int chunks = (NU + 64 * skpt - 1) / (64 * skpt);
             int nsl = (int)((P + 63) / 64);
             while (nsl < kMaxSlices && (int64_t)row_tiles * chunks * nsl < 1024 && P / nsl > 2) ++nsl;
-            const int limit = e && atoi(e) > 1 ? atoi(e) : 32;  // (MKB_POOL_SMALL=<n>: the workgroup count below which it applies)
-            if (!(e && e[0] == '0') && (int64_t)groups1 * npb * L.dim_slices <= limit && nsl <= kMaxSlices) {
+            if ((int64_t)groups1 * npb * L.dim_slices <= 32 && nsl <= kMaxSlices) {
                 L.small = 1; L.bwd1 = 0; L.skpt = skpt; L.schunks = chunks; L.q_slices = nsl;
                 L.dense_lanes = 0; L.pb_halves = 0;
             }
@@ -507,14 +497,10 @@ static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch
         if (L.bwd1) {
             const int64_t waves = (int64_t)row_tiles * L.dim_slices * npb;
             L.tiles_per_wave = (int)(waves >= 3 * 4096 ? waves / (2 * 4096) : 1);
-            if (const char *q = getenv("MKB_POOL_TPW")) { const int v = atoi(q); if (v >= 1 && v <= 64) L.tiles_per_wave = v; }
             L.row_groups = (row_tiles + 16 * L.tiles_per_wave - 1) / (16 * L.tiles_per_wave);
             L.cplx = cp ? 1 : 0;
         }
     }
-    if (const char *e = getenv("MKB_POOL_FSLICES")) { const int v = atoi(e); if (v >= 1 && v <= 64) L.fwd_slices = v; }
-    if (const char *e = getenv("MKB_POOL_QSLICES")) { const int v = atoi(e); if (v >= 1 && v <= kMaxSlices && !L.mfma && !L.bwd1 && !L.small) L.q_slices = v; }
-    if (const char *e = getenv("MKB_POOL_XSLICES")) { const int v = atoi(e); if (v >= min_x && v >= 1) L.x_slices = v; }
     return true;
 }
 
@@ -642,19 +628,18 @@ static int pooled_fwd(const mkb_tables_t *tb, bool head, const int64_t *sample, 
                       bool build_queries = true, GemmTail *s_tail = nullptr, int *occ = nullptr, bool *occ_counted = nullptr) {
     if (s_tail) s_tail->kind = 0;
     if (occ_counted) *occ_counted = false;
-    static const bool no_cut = getenv("MKB_GEMM_NO_DEPTH") != nullptr;  // A/B: multiply all P pool positions
-    const bool cut = use_mfma(tb) && !no_cut;
+    const bool mfma = use_mfma(tb);  // (the GEMMs multiply only the pool positions each row uses: depth cuts)
     if (build_queries) {
         RowArgs ra{tb->ent, tb->rel, sample, w.Q, nullptr, nullptr, tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B,
                    1, tb->phase_div};
-        if (cut) { ra.cnt = cnt; ra.depth = w.depth; ra.P = (int)P; }
+        if (mfma) { ra.cnt = cnt; ra.depth = w.depth; ra.P = (int)P; }
         if (int rc = dispatch_query_build(tb, head, ra, B, st)) return rc;
     }
-    if (use_mfma(tb)) {  // S = Q . ent[pool]^T on the matrix cores, over the pool positions the row tile uses (cnt masks later)
+    if (mfma) {  // S = Q . ent[pool]^T on the matrix cores, over the pool positions the row tile uses (cnt masks later)
         GemmArgs g{};
         g.A = w.Q; g.lda = tb->entity_dim; g.B = tb->ent; g.ldb = tb->entity_dim; g.b_idx = pool; g.b_rows = tb->n_entity;
         g.C = S; g.ldc = P; g.M = (int)B; g.N = (int)P; g.K = (int)tb->entity_dim; g.c0 = 0.f; g.c1 = 1.f;
-        if (cut) { g.depth = w.depth; g.depth_mode = 1; g.n_depth = (int)B; }
+        g.depth = w.depth; g.depth_mode = 1; g.n_depth = (int)B;
         ProfScope ps(MKB_PROF_POOL_FWD, st);
         return launch_gemm<true, true, GEMM_STORE_AFFINE>(g, st, w.gemm_part, s_tail, s_tail ? 500 : 0);
     }
@@ -665,9 +650,9 @@ static int pooled_fwd(const mkb_tables_t *tb, bool head, const int64_t *sample, 
     if (L.tile) {  // (s_tail: the loss rows of mkb_pool_step add the prefix's partial sums up; otherwise S is finished here)
         A.tile_part = w.tile_part;
         A.tile_tail = s_tail;
-        return launcher_of(tb->model)(5, head, L, A, st);
+        return launcher_of(tb->model)(kPoolFwdTile, head, L, A, st);
     }
-    return launcher_of(tb->model)(0, head, L, A, st);
+    return launcher_of(tb->model)(kPoolFwd, head, L, A, st);
 }
 
 // dq_slices (out): how many [B, De] partial products the dQ buffer holds (the consumer -- row / query backward -- adds them up)
@@ -676,19 +661,17 @@ static int pooled_bwd(const mkb_tables_t *tb, bool head, const mkb_grads_t *gr, 
                       bool chain_queries = true, DxReduce *dx_out = nullptr, GemmTail *x_tail = nullptr, int *dq_slices = nullptr) {
     int dq_used = L.q_slices;
     if (x_tail) x_tail->kind = 0;
-    static const bool no_cut = getenv("MKB_GEMM_NO_DEPTH") != nullptr;
-    const bool cut = use_mfma(tb) && !no_cut;  // w.depth was written by this call's row_fwd / query_build
-    if (use_mfma(tb)) {
+    if (use_mfma(tb)) {  // (w.depth was written by this call's row_fwd / query_build)
         // dQ [B, De] = G [B, P] . ent[pool]
         GemmArgs gq{};
         gq.A = w.G; gq.lda = P; gq.B = tb->ent; gq.ldb = tb->entity_dim; gq.b_idx = pool; gq.b_rows = tb->n_entity;
         gq.C = w.dQ; gq.ldc = tb->entity_dim; gq.M = (int)B; gq.N = (int)tb->entity_dim; gq.K = (int)P;
-        if (cut) { gq.depth = w.depth; gq.depth_mode = 2; gq.n_depth = (int)B; }  // (G is exactly 0 beyond a row's depth)
+        gq.depth = w.depth; gq.depth_mode = 2; gq.n_depth = (int)B;  // (G is exactly 0 beyond a row's depth)
         // g_ent[pool[p]] += (G^T [P, B] . Q [B, De])[p]
         GemmArgs gx{};
         gx.A = w.G; gx.lda = P; gx.B = w.Q; gx.ldb = tb->entity_dim; gx.b_idx = nullptr;
         gx.C = gr->g_ent; gx.ldc = tb->entity_dim; gx.c_idx = pool; gx.M = (int)P; gx.N = (int)tb->entity_dim; gx.K = (int)B;
-        if (cut) { gx.depth = w.depth; gx.depth_mode = 3; gx.n_depth = (int)B; }
+        gx.depth = w.depth; gx.depth_mode = 3; gx.n_depth = (int)B;
         bool paired = false;
         {   // round 5: both products in ONE launch where they qualify (profiled as the POOL_BWD_Q class)
             ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
@@ -709,23 +692,15 @@ static int pooled_bwd(const mkb_tables_t *tb, bool head, const mkb_grads_t *gr, 
         A.g_modulus = gr->g_modulus;
         A.g_ent = gr->g_ent;
         A.dx_reduce_out = dx_out;
-        static const bool split = getenv("MKB_POOL_SPLIT_BWD") != nullptr;  // A/B: the two passes as two launches
         if (L.bwd1) {  // every pair term evaluated once (pool_bwd1_kernel); profiled as the POOL_BWD_Q class
             ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launcher_of(tb->model)(4, head, L, A, st)) return rc;
+            if (int rc = launcher_of(tb->model)(kPoolBwd1, head, L, A, st)) return rc;
         } else if (L.small) {  // a small problem: one wave per piece, every pair evaluated once (pool_bwd_wave_kernel)
             ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launcher_of(tb->model)(6, head, L, A, st)) return rc;
-        } else if (!split) {  // dq and dx passes in one grid (pool_bwd_kernel); profiled as the POOL_BWD_Q class
+            if (int rc = launcher_of(tb->model)(kPoolBwdSmall, head, L, A, st)) return rc;
+        } else {  // dq and dx passes in one grid (pool_bwd_kernel); profiled as the POOL_BWD_Q class
             ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launcher_of(tb->model)(1, head, L, A, st)) return rc;
-        } else {
-            {
-                ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-                if (int rc = launcher_of(tb->model)(3, head, L, A, st)) return rc;
-            }
-            ProfScope ps(MKB_PROF_POOL_BWD_X, st);
-            if (int rc = launcher_of(tb->model)(2, head, L, A, st)) return rc;
+            if (int rc = launcher_of(tb->model)(kPoolBwd, head, L, A, st)) return rc;
         }
     }
     if (dq_slices) *dq_slices = dq_used;
@@ -826,11 +801,9 @@ static int pool_step_fwd(const mkb_tables_t *tb, const int64_t *sample, const in
     const bool head = mode_is_head(mode);
     RowStepArgs ra{tb->ent, tb->rel, tb->modulus, sample, w.Q, w.dQ, pos_score, w.dpos, nullptr, nullptr, nullptr,
                    tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, L.q_slices, tb->phase_div, tb->gamma};
-    static const bool no_own = getenv("MKB_POOL_NO_OWN") != nullptr;  // A/B: every gradient row through atomics
-    if (!no_own) { ra.occ = w.occ; ra.pool = pool; ra.P = (int)P; }
+    ra.occ = w.occ; ra.pool = pool; ra.P = (int)P;
     if (L.rel_copies > 1) { ra.rel_rep = w.rel_rep; ra.rel_copies = L.rel_copies; ra.n_rel = (int)tb->n_relation; }
-    static const bool no_cut = getenv("MKB_GEMM_NO_DEPTH") != nullptr;
-    if (use_mfma(tb) && !no_cut) { ra.cnt = cnt; ra.depth = w.depth; ra.depth_P = (int)P; }  // used pool depth per row (GEMM cuts)
+    if (use_mfma(tb)) { ra.cnt = cnt; ra.depth = w.depth; ra.depth_P = (int)P; }  // used pool depth per row (GEMM cuts)
     // positive pass (mode None: tail-style formula against the true tail, pipeline.py:211) + negative-path queries
     {
         ProfScope ps(MKB_PROF_GENERAL_FWD, st);
@@ -857,8 +830,7 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
     RowStepArgs ra{tb->ent, tb->rel, tb->modulus, sample, w.Q, w.dQ, nullptr, w.dpos, gr->g_ent, gr->g_rel, gr->g_modulus,
                    tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, L.q_slices, tb->phase_div, tb->gamma};
     // Adversarial forward + gradient seeds (pipeline.py:234 and the head of :236)
-    static const bool no_own = getenv("MKB_POOL_NO_OWN") != nullptr;
-    if (!no_own) { ra.occ = w.occ; ra.pool = pool; ra.P = (int)P; }
+    ra.occ = w.occ; ra.pool = pool; ra.P = (int)P;
     if (L.rel_copies > 1) {  // (zeroed by the row forward kernel of this step)
         ra.rel_rep = w.rel_rep; ra.rel_copies = L.rel_copies; ra.n_rel = (int)tb->n_relation;
     }
@@ -870,9 +842,8 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
     ra.loss_scal = weight_sum ? weight_sum : w.scratch;
     ra.loss_out = loss;
     // backward (pipeline.py:236): pooled negatives, then the positive pair and both query chains in one row kernel
-    static const bool no_fold = getenv("MKB_GEMM_NO_FOLD") != nullptr;
     if (int rc = pooled_bwd(tb, head, gr, sample, pool, cnt, B, P, w, L, st, /*chain_queries=*/false, L.bwd1 ? &ra.dx : nullptr,
-                            no_fold ? nullptr : &ra.sc, &ra.nslices)) return rc;
+                            &ra.sc, &ra.nslices)) return rc;
     ra.dx.occ = ra.occ;  // (the dx reduction riding this launch writes pool rows: exclusive ones without atomics)
     ra.grads_clear = gr->rows_clear ? 1 : 0;
     ra.dx.clear = ra.grads_clear;
@@ -904,10 +875,9 @@ extern "C" int mkb_pool_step(const mkb_tables_t *tb, const mkb_grads_t *gr, cons
                              const int64_t *pool, const uint16_t *cnt, int64_t B, int64_t K, int mode, float alpha,
                              const float *weight_sum, float *pos_score, float *pool_score, float *loss, void *ws,
                              void *stream) {
-    // one call: the split-K tails of the MFMA products fold into the launches that follow them (MKB_GEMM_NO_FOLD=1: A/B)
-    static const bool no_fold = getenv("MKB_GEMM_NO_FOLD") != nullptr;
+    // one call: the split-K tails of the MFMA products fold into the launches that follow them
     GemmTail s_tail{};
-    if (int rc = pool_step_fwd(tb, sample, pool, cnt, B, K, mode, pos_score, pool_score, ws, stream, no_fold ? nullptr : &s_tail))
+    if (int rc = pool_step_fwd(tb, sample, pool, cnt, B, K, mode, pos_score, pool_score, ws, stream, &s_tail))
         return rc;
     return pool_step_bwd(tb, gr, sample, weight, pool, cnt, B, K, mode, alpha, weight_sum, pos_score, pool_score, loss, ws,
                          stream, (s_tail.kind == 1 || s_tail.kind == 3) ? &s_tail : nullptr);

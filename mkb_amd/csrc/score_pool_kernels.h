@@ -688,8 +688,7 @@ __device__ __forceinline__ void pool_bwd_x_body(const PoolArgs &A, const int blo
 // of two saves a kernel boundary (~15 us between two large kernels on this part) and keeps two workgroups resident on
 // every CU for the whole launch.  Dispatch order (a CU issues oldest-first, so the order is the schedule): the first
 // q_first dq workgroups (on most CUs), then the dx pass (fringe, heavy, light tiles: the heavy ones take the CUs' second
-// slots), then the remaining dq workgroups, which replace the first ones as they retire.  x_blocks == 0 or no dq blocks
-// runs one pass alone (A/B measurements).
+// slots), then the remaining dq workgroups, which replace the first ones as they retire.
 template <int MODEL, bool HEAD, int KPT, int NW>
 __global__ __launch_bounds__(NW * 64) void pool_bwd_kernel(PoolArgs A) {
     extern __shared__ __attribute__((aligned(16))) int lds_bwd[];
@@ -1827,9 +1826,20 @@ struct PoolLaunch {
     int64_t n_entity;
 };
 
-// Per-model entry points (defined in score_pool_<model>.hip): launch one of the three kernels for (head, config).
-typedef int (*pool_launch_fn)(int which /*0 fwd, 1 bwd (dq + dx in one grid), 2 dx pass alone, 3 dq pass alone, 4 single-pass bwd, 5 fwd: tile + fringe, 6 bwd of a small problem (one wave per piece)*/, bool head, const PoolLaunch &L, const PoolArgs &A,
-                              hipStream_t st);
+// The kernels a pool_launch_fn launches (its `which` argument)
+constexpr int kPoolFwd = 0;       // forward (pool_fwd_kernel)
+constexpr int kPoolBwd = 1;       // two-pass backward: dq and dx passes in one grid (pool_bwd_kernel)
+constexpr int kPoolBwd1 = 2;      // single-pass backward (pool_bwd1_kernel)
+constexpr int kPoolFwdTile = 3;   // forward: dense prefix on the register tile + sparse fringe (pool_fwd_tile_kernel)
+constexpr int kPoolBwdSmall = 4;  // backward of a small problem, one wave per piece (pool_bwd_wave_kernel)
+
+// The two-pass backward runs only when a pool needs more position blocks than the single-pass kernel has (pick_config),
+// which takes 4 floats per lane and position: RotatE at >= 2 units per lane, or a real-valued model at 4 (pRotatE has no
+// 4-unit form).  It is compiled for these (model, units per lane) pairs alone.
+constexpr bool pool_two_pass_compiled(int model, int kpt) { return model != MKB_PROTATE && kpt >= 2; }
+
+// Per-model entry points (defined in score_pool_<model>.hip): launch one of the kernels above for (head, config).
+typedef int (*pool_launch_fn)(int which, bool head, const PoolLaunch &L, const PoolArgs &A, hipStream_t st);
 int pool_launch_transe(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
 int pool_launch_rotate(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
 int pool_launch_complex(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
@@ -1839,23 +1849,23 @@ int pool_launch_protate(int, bool, const PoolLaunch &, const PoolArgs &, hipStre
 template <int MODEL, bool HEAD, int KPT, int NW>
 static int launch_cfg(int which, const PoolLaunch &L, const PoolArgs &A, hipStream_t st) {
     const dim3 block(NW * 64);
-    if (which == 0) {
+    if (which == kPoolFwd) {
         dim3 grid((unsigned)((A.B + TI - 1) / TI), (unsigned)L.fwd_slices);
         hipLaunchKernelGGL((pool_fwd_kernel<MODEL, HEAD, KPT, NW>), grid, block, (size_t)3 * ((A.P + L.fwd_slices - 1) / L.fwd_slices) * 4, st, A);
-    } else {
-        // which: 1 = both passes in one grid, 2 = dx pass only, 3 = dq pass only
+    } else if constexpr (pool_two_pass_compiled(MODEL, KPT)) {
         const size_t rows_per = (size_t)((A.B + L.x_slices - 1) / L.x_slices);
         const size_t lds_x = ((TI + 2) * rows_per + 16) * 4;
         const size_t lds_q = ((size_t)(TI + 2) * ((A.P + L.q_slices - 1) / L.q_slices) + 32) * 4;
-        const unsigned xb = which == 3 ? 0u : (unsigned)(((A.P + TI - 1) / TI) * L.x_slices);
-        const unsigned qb = which == 2 ? 0u : (unsigned)(((A.B + TI - 1) / TI) * L.q_slices);
+        const unsigned xb = (unsigned)(((A.P + TI - 1) / TI) * L.x_slices);
+        const unsigned qb = (unsigned)(((A.B + TI - 1) / TI) * L.q_slices);
         PoolArgs A2 = A;
         A2.x_blocks = (int)xb;
         // dq workgroups ahead of the dx pass: a little under one per CU measured best (headline: 0 -> 169 us, 96..224 ->
         // 160-165 us, 256 -> 170 us; the other shapes are flat within 2 %)
-        A2.q_first = xb ? (int)(qb < 160u ? qb : 160u) : 0;
-        if (const char *e = getenv("MKB_POOL_QFIRST")) A2.q_first = xb ? (atoi(e) < (int)qb ? atoi(e) : (int)qb) : 0;
+        A2.q_first = (int)(qb < 160u ? qb : 160u);
         hipLaunchKernelGGL((pool_bwd_kernel<MODEL, HEAD, KPT, NW>), dim3(xb + qb), block, lds_x > lds_q ? lds_x : lds_q, st, A2);
+    } else {
+        return set_error(MKB_ERR_UNSUPPORTED, "two-pass pooled backward not compiled for this model at %d units per lane", KPT);
     }
     MKB_LAUNCH_CHECK();
     return MKB_OK;
@@ -1920,15 +1930,16 @@ static int launch_wave(const PoolLaunch &L, const PoolArgs &A, hipStream_t st) {
 
 template <int MODEL, bool HEAD>
 static int launch_head(int which, const PoolLaunch &L0, const PoolArgs &A, hipStream_t st) {
-    if (which == 5) return launch_fwd_tile<MODEL, HEAD>(L0, A, st, A.tile_part, A.tile_tail);
-    if (which == 6) return L0.skpt == 2 ? launch_wave<MODEL, HEAD, 2>(L0, A, st) : launch_wave<MODEL, HEAD, 1>(L0, A, st);
-    if (which == 4) {
+    if (which == kPoolFwdTile) return launch_fwd_tile<MODEL, HEAD>(L0, A, st, A.tile_part, A.tile_tail);
+    if (which == kPoolBwdSmall) return L0.skpt == 2 ? launch_wave<MODEL, HEAD, 2>(L0, A, st) : launch_wave<MODEL, HEAD, 1>(L0, A, st);
+    if (which == kPoolBwd1) {
         if constexpr (!ModelTraits<MODEL>::cplx_pair && MODEL != MKB_PROTATE)
             if (L0.bkpt == 4) return launch_bwd1<MODEL, HEAD, 4>(L0, A, st);
         return L0.bkpt >= 2 ? launch_bwd1<MODEL, HEAD, 2>(L0, A, st) : launch_bwd1<MODEL, HEAD, 1>(L0, A, st);
     }
+    if (which != kPoolFwd && which != kPoolBwd) return set_error(MKB_ERR_INVALID, "unknown pooled kernel %d", which);
     PoolLaunch L = L0;
-    if (which == 0) { L.kpt = L0.fkpt; L.nw = L0.fnw; }
+    if (which == kPoolFwd) { L.kpt = L0.fkpt; L.nw = L0.fnw; }
     if (L.kpt == 1 && L.nw == 1) return launch_cfg<MODEL, HEAD, 1, 1>(which, L, A, st);
     if (L.kpt == 2 && L.nw == 1) return launch_cfg<MODEL, HEAD, 2, 1>(which, L, A, st);
     if (L.kpt == 1 && L.nw == 2) return launch_cfg<MODEL, HEAD, 1, 2>(which, L, A, st);

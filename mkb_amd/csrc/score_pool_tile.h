@@ -238,12 +238,6 @@ static int launch_fwd_tile(const PoolLaunch &L, const PoolArgs &A0, hipStream_t 
         const bool fringe = A.P > T.Kd;
         T.fringe_tiles = fringe ? (A.B + TI - 1) / TI : 0;
         T.fringe_slices = fringe ? L.tile_fringe_slices : 0;
-        // measurement only, WRONG scores ('d' = the dense tiles alone, 'f' = the fringe alone): honoured only together with
-        // MKB_MEASURE_WRONG_RESULTS=1, so that a stray variable cannot silently break a run
-        if (const char *e = getenv("MKB_MEASURE_WRONG_RESULTS") ? getenv("MKB_POOL_TILE_ONLY") : nullptr) {
-            if (e[0] == 'd') { T.fringe_tiles = 0; T.fringe_slices = 0; }
-            if (e[0] == 'f') T.pos_tiles = 0;
-        }
         const size_t lds = (T.fringe_tiles > 0) ? (size_t)3 * ((A.P - T.Kd + T.fringe_slices - 1) / T.fringe_slices) * 4 : 0;
         const unsigned blocks = (unsigned)(T.fringe_tiles * T.fringe_slices + T.row_tiles * T.pos_tiles * T.ks);
         if (L.fkpt == 4) hipLaunchKernelGGL((pool_fwd_tile_kernel<MODEL, HEAD, 4>), dim3(blocks), dim3(256), lds, st, A, T);

@@ -245,3 +245,19 @@ def test_bench_windows_cover_exactly_the_timed_steps():
             sizes = bench.window_sizes(steps, windows)
             assert sum(sizes) == steps and min(sizes) >= 1 and max(sizes) - min(sizes) <= 1, (steps, windows, sizes)
             assert len(sizes) == (min(windows, steps) if windows else max(1, min(15, steps // 20)))
+
+
+def test_library_reads_only_the_listed_environment_switches():
+    """The HIP library's run-time switches are the ones DESIGN.md section 5 lists, each used by a test or a tool.  A switch that
+    only selects a measurement variant makes the product depend on more than its arguments (and the workspace layouts that
+    mkb_pool_step_workspace_bytes sizes over do not cover it): measure with a compile-time variant instead."""
+    from conftest import ROOT
+
+    csrc = ROOT / "mkb_amd" / "csrc"
+    names = set()
+    for src in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h")):
+        names |= set(re.findall(r'getenv\(\s*"([A-Za-z0-9_]+)"', src.read_text()))
+    assert names == {
+        "MKB_POOL_NO_MFMA", "MKB_POOL_DENSE", "MKB_GEMM_BF16X3", "MKB_GEMM_NO_PAIR", "MKB_GEMM_NO128", "MKB_ADAM_SWEEP",
+        "MKB_ROWS_LOOP_TIMEOUT_S", "MKB_ROWS_TAKE_TIMEOUT_S", "MKB_ROWS_ONE_GROUP",
+    }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/ab_env.sh <config> <kernel class> "<ENV=.. ENV=..>" ["<ENV=..>" ...]: A/B of environment switches through bench.py on the GPU
 # box, one line per setting: ms per step, the class's kernel, its mean duration under the bench's HIP events, frac, loss.
-# (round 5's measurements: MKB_POOL_SMALL, MKB_POOL_TILE_ONLY, MKB_POOL_TILE_KS / _FSL, MKB_POOL_DENSE, MKB_POOL_BWD1 ...)
+# (the switches the library reads are listed in DESIGN.md section 5, e.g. MKB_POOL_DENSE, MKB_GEMM_NO128)
 cfg=$1; cls=$2; shift 2
 for v in "X=1" "$@"; do
   echo -n "$cfg [$v]: "

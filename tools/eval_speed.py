@@ -1,7 +1,5 @@
 """python tools/eval_speed.py [Model ...]: seconds of one filtered evaluation (evaluation.Evaluation.eval, both corruption sides) of
-FB15k-237's test split -- 40,932 queries x 14,541 entities, hidden 1000, random tables -- per model.  A/B switches of mkb_rank:
-MKB_RANK_TILE=0 (RotatE / TransE without the register tile), MKB_RANK_GEMM=0 (ComplEx / DistMult without the matrix cores),
-MKB_RANK_WIDE=1 (16 waves x 1 unit per lane)."""
+FB15k-237's test split -- 40,932 queries x 14,541 entities, hidden 1000, random tables -- per model."""
 import sys, time, torch
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from mkb_amd import datasets, evaluation, models
