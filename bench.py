@@ -1,10 +1,15 @@
 """bench.py -- scored triples/sec of the mkb training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 --steps K is the number of timed steps (split into back-to-back windows, see --windows); ms_per_step is the median window's
 time per step.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
+
+A plain run sets up, warms up, times the K steps, writes its outputs if asked and prints the line.  --full adds what the line's
+value does not need: the HBM traffic of the profiled kernel class and of the step (two rocprofv3 runs of their own), MRR after
+more training, the step without optimizer / sampler, the CPU baseline, and at N > 1 the other partitionings and BASELINE
+configs[4]; --no-traffic, --mrr-epochs 0, --no-variants, --no-cpu-baseline and --no-extras leave one of them out.
 
 Workload (BASELINE.json configs[2], the headline): FB15k-237 (14,541 entities, 237 relations, 272,115 training
 triples) + RotatE hidden_dim=1000 (entity rows 2000 fp32), K=256 negatives, batch 1024 rows PER GPU, Adversarial
@@ -17,7 +22,7 @@ state) are resident in HBM before the timed region; batches are index-selected o
 Multi-GPU (N > 1), weak scaling with a global batch of N*1024 rows scored against ONE candidate pool (replicated
 MT19937 state).  Default --parallelism table-rows, the partitioning BASELINE.json's north_star names: the entity table, its
 gradient and its Adam state are sharded by ROW (owner = id % N, mkb_amd/table_rows.py); pool rows by one all-reduce,
-positive rows by all-to-all, gradients back the same way, row-lazy Adam per shard.  The same run then measures the two
+positive rows by all-to-all, gradients back the same way, row-lazy Adam per shard.  With --full the same run then measures the two
 alternatives (fewer steps) and BASELINE configs[4] (YAGO3-10 RotatE-500, the config north_star shards) and reports them
 under "other_partitionings" / "config5" of the same JSON line:
 --parallelism dims: the embedding DIMENSION is sharded (rank g holds 1/N of every table column-wise, 1/N of the optimizer
@@ -27,7 +32,8 @@ then loss / backward / Adam are local -- no gradient exchange.
 rows (mkb_amd.parallel.SparseGradExchange).
 
 Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant kernel (HIP-event timed inside the
-timed region) and "cpu_baseline" (the oracle restatement of the reference's PyTorch-CPU path on a bounded sample).
+timed region; its measured traffic with --full) and, with --full, "cpu_baseline" (the oracle restatement of the reference's
+PyTorch-CPU path on a bounded sample).
 """
 import argparse
 import gc
@@ -358,13 +364,12 @@ def measure_traffic(prof_kind, config):
         return None, f"no kernel name known for class {prof_kind}", None, None
     out, notes, names, tables = {}, [], [], {}
     tmp = tempfile.mkdtemp(prefix="mkb_traffic_", dir="/tmp")
-    env = dict(os.environ, TMPDIR="/tmp", MKB_BENCH_INNER="1")
+    env = dict(os.environ, TMPDIR="/tmp")
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "run", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "12", "--warmup", "4", "--config", config, "--no-cpu-baseline", "--mrr-epochs", "0", "--no-variants",
-                   "--profile-kernel", "none", "--no-traffic"]
+                   "--steps", "12", "--warmup", "4", "--config", config, "--profile-kernel", "none"]  # a plain run: no --full
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=240)
             dbs = glob.glob(os.path.join(d, "**", "*.db"), recursive=True)
             if r.returncode != 0 or not dbs:
@@ -643,7 +648,7 @@ def roofline_of(res, world, want_traffic):
     De, Dr, N, R = m_.entity_dim, m_.relation_dim, m_.n_entity, m_.n_relation  # per rank (dims: 1/world of the row)
     Bk = world * ctx["rows_per_rank"] if ctx["dims"] else ctx["rows_per_rank"]  # rows each rank's kernels see
     avg_s = res["kms"] / launches / 1e3
-    traffic, traffic_note, kname, step_table = (None, "not measured (--no-traffic, N > 1, or a non-default run)", None, None)
+    traffic, traffic_note, kname, step_table = (None, "not measured (a run without --full, --no-traffic, or N > 1)", None, None)
     if want_traffic:
         traffic, traffic_note, kname, step_table = measure_traffic(prof_kind, res["config"])
     res["step_traffic"] = step_table
@@ -785,11 +790,14 @@ def main():
     ap.add_argument("--preheat-ms", type=float, default=0.0,
                     help="diagnostic: keep the device busy with unrelated torch matmuls for that long right before the warm-up steps "
                          "(tells a clock / power ramp of the device from a warm-up effect of this code's own state)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own measurement, also measure what its value does not need: HBM traffic (rocprofv3), "
+                         "MRR, step variants, the CPU baseline; N>1: the other partitionings and config 5 (see the --no-* switches)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-rows", type=int, default=64, help="rows of the cpu_baseline sample (reference-faithful form)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the with/without optimizer & sampler step variants")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 PMC passes behind roofline.traffic")
-    ap.add_argument("--no-extras", action="store_true", help="N>1: skip the other partitionings and config 5")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the with/without optimizer & sampler step variants")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the rocprofv3 PMC passes behind roofline.traffic")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N>1: skip the other partitionings and config 5")
     ap.add_argument("--profile-kernel", default="auto", help="kernel class bracketed with HIP events (or 'none')")
     ap.add_argument("--breakdown", action="store_true", help="also print per-phase timings (stderr)")
     ap.add_argument("--scaling", default=os.environ.get("MKB_BENCH_SCALING", "weak"), choices=["weak", "strong"],
@@ -810,7 +818,7 @@ def main():
     ap.add_argument("--config", default="headline", choices=sorted(CONFIGS),
                     help="BASELINE.json configuration (default: the headline; the others are for profiles/)")
     ap.add_argument("--mrr-epochs", type=int, default=30,
-                    help="after the timed region (N=1 only): train this many more epochs, then filtered MRR on the test set")
+                    help="--full, after the timed region (N=1 only): train this many more epochs, then filtered MRR on the test set")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.windows < 0:
         ap.error("--steps must be >= 1, --warmup and --windows >= 0")
@@ -921,7 +929,6 @@ def main():
     if rank == 0:
         if res["sampler_note"]:
             print(res["sampler_note"], file=sys.stderr)
-        default_run = world == 1 and not os.environ.get("MKB_BENCH_INNER")
         out = {
             "metric": "scored triples/sec (pos+K neg), FB15k-237 RotatE d=1000" if args.config == "headline"
             else f"scored triples/sec (pos+K neg), {args.config}", "value": res["value"], "unit": "triples/s",
@@ -946,7 +953,7 @@ def main():
             "t_host_ms_per_step": res["t_host"] * 1e3,
             "windows_detail": [{k: round(v, 4) if isinstance(v, float) else v for k, v in w.items()} for w in res["windows"]],
             "gc_collections_during_windows": res["gc"],
-            "roofline": roofline_of(res, world, want_traffic=default_run and not args.no_traffic and res["prof_kind"] != "none"),
+            "roofline": roofline_of(res, world, want_traffic=args.full and world == 1 and not args.no_traffic and res["prof_kind"] != "none"),
         }
         if out["roofline"] is not None:
             out["roofline"]["step"] = step_roofline(res, world)
@@ -975,9 +982,9 @@ def main():
                                          note="host_waits_that_blocked = steps whose split sizes (read back one batch ahead on a side "
                                               "stream) were not there yet when the step needed them")
 
-    # ---- N > 1: the other partitionings and BASELINE configs[4] in the same run (fewer steps; same barrier + max-over-ranks
+    # ---- --full, N > 1: the other partitionings and BASELINE configs[4] in the same run (fewer steps; same barrier + max-over-ranks
     # timing).  A watchdog prints the line without them if they hang: the headline number must not be lost to an extra.
-    if world > 1 and not args.no_extras and not failures:
+    if world > 1 and args.full and not args.no_extras and not failures:
         import threading
 
         def bail():
@@ -1023,11 +1030,11 @@ def main():
             dist.destroy_process_group()
         return
     ctx = res["ctx"]
-    if world == 1 and args.mrr_epochs > 0 and not ctx["trows"]:
+    if args.full and world == 1 and args.mrr_epochs > 0 and not ctx["trows"]:
         out["mrr"] = train_and_rank(ctx, args.mrr_epochs, res["next_step"])
-    if world == 1 and args.config == "headline" and not args.no_variants and not ctx["trows"]:
+    if args.full and world == 1 and args.config == "headline" and not args.no_variants and not ctx["trows"]:
         out["step_variants"] = step_variants(ctx)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(rows=args.cpu_rows)
     print(json.dumps(out))
     if dist is not None and dist.is_initialized():

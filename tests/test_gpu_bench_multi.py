@@ -35,8 +35,8 @@ def test_bench_two_ranks_on_one_device(parallelism, scaling):
 
 
 def test_bench_default_partitioning_is_table_rows_and_reports_the_others():
-    """What the driver launches (no --parallelism): the north_star partitioning is the line's value; dims and rows ride in
-    the same line under other_partitionings."""
+    """No --parallelism: the north_star partitioning is the line's value; with --full, dims and rows ride in the same line
+    under other_partitionings."""
     from conftest import ROOT
 
     with socket.socket() as s:
@@ -46,7 +46,7 @@ def test_bench_default_partitioning_is_table_rows_and_reports_the_others():
     env.pop("MKB_BENCH_PARALLELISM", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--config", "wn18rr-rotate"]
+           "--config", "wn18rr-rotate", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -61,7 +61,7 @@ def test_bench_default_partitioning_is_table_rows_and_reports_the_others():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--config", "wn18rr-rotate", "--parallelism", "dims"]
+           "--config", "wn18rr-rotate", "--parallelism", "dims", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -126,6 +126,24 @@ def test_bench_line_reports_the_median_window_and_every_window():
         assert {"ms", "host_enqueue_ms", "device_ms", "largest_submit_gap_ms", "largest_submit_gap_at_step", "gc_ms"} <= set(w)
         assert 0 < w["host_enqueue_ms"] <= w["ms"] + 1e-3 and 0 < w["device_ms"] <= w["ms"] + 0.5
     assert d["t_host_ms_per_step"] > 0 and isinstance(d["gc_collections_during_windows"], list)
+
+
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """A plain headline run prints the line and its in-region roofline only; --full adds the measurements the value does not
+    need (here the step variants: the others have their own --no-* switches, and take a rocprofv3 pass, training or the CPU)."""
+    from conftest import ROOT
+
+    extras = {"mrr", "step_variants", "cpu_baseline"}
+    lines = {}
+    for name, flags in (("plain", []), ("full", ["--full", "--no-traffic", "--mrr-epochs", "0", "--no-cpu-baseline"])):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", *flags]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+        lines[name] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 4 and plain["value"] > 0 and not extras & set(plain)
+    assert plain["roofline"]["launches"] > 0 and plain["roofline"]["traffic"] is None
+    assert set(full) & extras == {"step_variants"} and all(v["value"] > 0 for v in full["step_variants"].values())
 
 
 def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):

@@ -21,7 +21,7 @@ python tools/prof_summary.py $(find $O/ktrace -name "*.db" | head -1) timeline >
 cp $(ls $O/ktrace/*kernel_stats.csv 2>/dev/null | head -1) $O/rocprofv3_kernel_stats.csv 2>/dev/null
 python tools/pmc_summary.py $(find $O/pmc_FETCH_SIZE -name "*.db" | head -1) $(find $O/pmc_WRITE_SIZE -name "*.db" | head -1) > $O/pmc_hbm_traffic.txt
 python tools/pmc_summary.py $(find $O/pmc_sq -name "*.db" | head -1) $(find $O/pmc_clk -name "*.db" | head -1) > $O/pmc_sq.txt 2>&1
-timeout 900 python bench.py --breakdown > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full --breakdown > $O/bench_default.json 2> $O/bench_default.err
 # the driver's protocol, three fresh processes
 for i in 1 2 3; do timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O/bench_driver_protocol.jsonl; done
 # which launch of the step gets faster over the first ~150 steps of a process (the trend inside windows_ms)
@@ -38,7 +38,7 @@ done
 # N > 1 entry path on ONE device (gloo through the host: a functional check, not a scaling number): what the driver launches
 # (default partitioning table-rows, the others + config 5 in the same line), and config 5 on its own
 echo "== python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 (MKB_BENCH_ONE_DEVICE=1, gloo)" >> $O/one_device_world2.txt
-MKB_BENCH_ONE_DEVICE=1 MKB_BENCH_EXTRAS_TIMEOUT=600 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O/one_device_world2.txt
+MKB_BENCH_ONE_DEVICE=1 MKB_BENCH_EXTRAS_TIMEOUT=600 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $O/one_device_world2.txt
 echo "== ... --config yago310-rotate --no-extras" >> $O/one_device_world2.txt
 MKB_BENCH_ONE_DEVICE=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 2 --steps 20 --warmup 5 --config yago310-rotate --no-extras 2>/dev/null | tail -1 >> $O/one_device_world2.txt
 # what ONE rank of the row-sharded step computes (world 1: every collective degenerates to a copy), next to the plain
