@@ -402,6 +402,18 @@ int mkb_rank_scores(const mkb_tables_t *tb, const int64_t *sample, int64_t B, in
 int64_t mkb_topk_workspace_bytes(const mkb_tables_t *tb, int64_t B, int k);
 int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true, int k,
              int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream);
+/* mkb_topk over a subset of the entities: entity e is a candidate when bit e % 32 of word e / 32 of cand_bits
+ * [ceil(n_entity / 32)] uint32 (device) is set.  An entity outside the mask is never returned: not with MKB_TOPK_KEEP_TARGET
+ * either; it combines with the true_keys filter.  cand_bits == null: exactly mkb_topk, bit for bit.  Arguments, workspace
+ * (mkb_topk_workspace_bytes(tb, B, k)), order and padding as for mkb_topk. */
+int mkb_topk_masked(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys,
+                    int64_t n_true, const uint32_t *cand_bits, int k, int flags, int64_t *ids, float *scores,
+                    void *ws, int64_t ws_bytes, void *stream);
+/* The same selection on a caller's fp32 block S [B, N] (device), rows ld >= N floats apart: for each row the k best columns,
+ * NaN first, then higher value, then lower column; ids [B, k] int64 / scores [B, k] fp32 out (the block's own values, bit for
+ * bit; -1 / -inf past the N columns).  No keys, no finisher, no workspace.  1 <= k <= MKB_TOPK_MAX_K, 0 <= B <= 2^31 - 1 (B = 0:
+ * nothing), 1 <= N <= 2^31 - 1, ld >= N, non-null pointers; otherwise MKB_ERR_INVALID before any launch. */
+int mkb_topk_block(const float *S, int64_t B, int64_t N, int64_t ld, int k, int64_t *ids, float *scores, void *stream);
 
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream

@@ -141,6 +141,9 @@ _SIGNATURES = {
     "mkb_topk_workspace_bytes": (c_int64, [POINTER(Tables), c_int64, c_int]),
     "mkb_topk": (c_int, [POINTER(Tables), c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                          c_int64, c_void_p]),
+    "mkb_topk_masked": (c_int, [POINTER(Tables), c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p,
+                                c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_topk_block": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -251,7 +251,19 @@ __global__ __launch_bounds__(256) void iota_kernel(int64_t *ids, int64_t n, int6
 //   3. bitonic sort of the buffer (at most kTopkCap composite keys, descending) in LDS; the first k are written out with their
 //      scores re-read from S and finished as rank_kernel / export_scores_kernel finish them (bit-identical).  Slots past the
 //      candidates left: id -1, score -inf.
+// Three instantiations of the one kernel:
+//   kTopkPlain  -- mkb_topk;
+//   kTopkMasked -- mkb_topk_masked: only the entities whose bit is set in cand_bits [ceil(N / 32)] are candidates.  An entity outside
+//                  the mask is treated as a filtered one at every step (not counted in the histograms, not taken back out of them,
+//                  not gathered, not taken by the collapsed-row fallback), MKB_TOPK_KEEP_TARGET included.  The mask is read from
+//                  global memory, not staged in LDS: it is 1/32 of the bytes of the score row it sits next to, every workgroup reads
+//                  the same words (they stay in L2 after the first few rows), and the eight mask loads of a strided step are issued
+//                  with the eight score loads; staging it would need an LDS block sized by N (15 KB at YAGO3-10's 123 k entities,
+//                  on top of the kernel's 25 KB) and cost occupancy on every shape;
+//   kTopkBlock  -- mkb_topk_block: a caller's fp32 block [B, N] with row stride ld: no sample, no true keys, no finisher (the
+//                  scores handed out are the block's own values, bit for bit).
 constexpr int kTopkThreads = 256, kTopkCap = 2048;
+constexpr int kTopkPlain = 0, kTopkMasked = 1, kTopkBlock = 2;
 
 __device__ __forceinline__ uint32_t order_image(float f) {
     if (f != f) return 0xFFFFFFFFu;
@@ -268,8 +280,17 @@ struct TopkArgs {
     int head_mode, k, keep_target;
     float c0, c1;
 };
+// kTopkMasked's arguments: the candidate bitmask, bit e % 32 of word e / 32 (a struct of its own, so that kTopkPlain's kernel
+// arguments keep their layout)
+struct TopkMaskedArgs : TopkArgs {
+    const uint32_t *cand;
+};
 
-__global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
+// (static: with internal linkage the kTopkPlain instantiation compiles to the very code and LDS layout of the non-template kernel
+// mkb_topk launched before the two other instantiations were added)
+template <int VAR, class Args = TopkArgs>
+static __global__ __launch_bounds__(kTopkThreads) void topk_kernel(Args A) {
+    constexpr bool MASKED = VAR == kTopkMasked, BLOCK = VAR == kTopkBlock;
     __shared__ uint32_t s_hist[2048];
     __shared__ uint32_t s_scan[kTopkThreads];
     __shared__ uint64_t s_buf[kTopkCap];
@@ -279,7 +300,8 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t N = A.N;
     for (int64_t i = blockIdx.x; i < A.B; i += gridDim.x) {
-        const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
+        // (kTopkBlock: no sample, no keys -- keep = -1, base = 0 and an empty key range, so nothing is filtered)
+        const int64_t h = BLOCK ? 0 : A.sample[3 * i], r = BLOCK ? 0 : A.sample[3 * i + 1], t = BLOCK ? 0 : A.sample[3 * i + 2];
         const int64_t keep = A.keep_target ? (A.head_mode ? h : t) : -1;
         const int64_t base = ((A.head_mode ? t : h) * A.R + r) * N;  // as in rank_kernel
         const float *row = A.S + i * A.ld;
@@ -291,7 +313,20 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
         }
         __syncthreads();
         const int64_t klo = s_range[0], khi = s_range[1];
-        auto image = [&](int64_t e) { return order_image(A.c0 + A.c1 * row[e]); };
+        auto fin = [&](float x) {
+            if constexpr (BLOCK) return x;
+            else return A.c0 + A.c1 * x;
+        };
+        auto image = [&](int64_t e) { return order_image(fin(row[e])); };
+        auto cand_word = [&](int64_t e) -> uint32_t {
+            if constexpr (MASKED) return A.cand[e >> 5];
+            else return 1u;
+        };
+        auto in_word = [&](uint32_t w, int64_t e) {
+            if constexpr (MASKED) return ((w >> (e & 31)) & 1u) != 0u;
+            else return true;
+        };
+        auto is_cand = [&](int64_t e) { return in_word(cand_word(e), e); };
         auto filtered = [&](int64_t e) {
             if (e == keep) return false;
             int64_t lo = klo, hi = khi;
@@ -309,12 +344,15 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
             __syncthreads();
             for (int64_t e0 = tid; e0 < N; e0 += T * 8) {  // eight strides' loads in flight (see rank_kernel)
                 float v[8];
+                uint32_t w[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = row[min(e0 + T * j, N - 1)];
 #pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = cand_word(min(e0 + T * j, N - 1));
+#pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const uint32_t u = order_image(A.c0 + A.c1 * v[j]);
-                    if (e0 + T * j < N && (u & mask) == prefix) atomicAdd(&s_hist[(u >> shift) & (bins - 1)], 1u);
+                    const uint32_t u = order_image(fin(v[j]));
+                    if (e0 + T * j < N && (u & mask) == prefix && in_word(w[j], e0 + T * j)) atomicAdd(&s_hist[(u >> shift) & (bins - 1)], 1u);
                 }
             }
             __syncthreads();  // (an entry counted above and taken back below may otherwise meet in the other order: unsigned wrap is harmless, but keep it plain)
@@ -322,7 +360,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
                 const int64_t e = A.keys[q] - base;
                 if (e == keep) continue;
                 const uint32_t u = image(e);
-                if ((u & mask) == prefix) atomicSub(&s_hist[(u >> shift) & (bins - 1)], 1u);
+                if ((u & mask) == prefix && is_cand(e)) atomicSub(&s_hist[(u >> shift) & (bins - 1)], 1u);
             }
             __syncthreads();
             // thread tid owns bins [8 tid, 8 tid + 8): inclusive suffix sums over the threads
@@ -363,13 +401,16 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
         __syncthreads();
         for (int64_t e0 = tid; e0 < N; e0 += T * 8) {
             float v[8];
+            uint32_t w[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = row[min(e0 + T * j, N - 1)];
 #pragma unroll
+            for (int j = 0; j < 8; ++j) w[j] = cand_word(min(e0 + T * j, N - 1));
+#pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int64_t e = e0 + T * j;
-                const uint32_t u = order_image(A.c0 + A.c1 * v[j]);
-                if (e < N && u >= thr && !filtered(e)) {
+                const uint32_t u = order_image(fin(v[j]));
+                if (e < N && u >= thr && in_word(w[j], e) && !filtered(e)) {
                     const uint32_t slot = atomicAdd(&s_cnt, 1u);
                     if (slot < (uint32_t)kTopkCap) s_buf[slot] = ((uint64_t)u << 32) | (uint32_t)~(uint32_t)e;
                 }
@@ -383,7 +424,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
             __syncthreads();
             for (int64_t e = tid; e < N; e += T) {  // the k - need < k entries above T
                 const uint32_t u = image(e);
-                if (u > thr && !filtered(e)) {
+                if (u > thr && is_cand(e) && !filtered(e)) {
                     const uint32_t slot = atomicAdd(&s_cnt, 1u);
                     if (slot < (uint32_t)A.k) s_buf[slot] = ((uint64_t)u << 32) | (uint32_t)~(uint32_t)e;  // (< k by the select)
                 }
@@ -393,7 +434,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
             uint32_t taken = 0;
             for (int64_t e0 = 0; e0 < N && taken < need; e0 += T) {  // ... and the first `need` ties in id order
                 const int64_t e = e0 + tid;
-                const bool tie = e < N && image(e) == thr && !filtered(e);
+                const bool tie = e < N && image(e) == thr && is_cand(e) && !filtered(e);
                 const uint64_t m = __ballot(tie);
                 __syncthreads();
                 if (lane == 0) s_scan[wave] = (uint32_t)__popcll(m);
@@ -430,7 +471,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(TopkArgs A) {
             if ((uint32_t)j < n) {
                 const int64_t e = (int64_t)(uint32_t)~(uint32_t)s_buf[j];
                 A.ids[o] = e;
-                A.scores[o] = A.c0 + A.c1 * row[e];
+                A.scores[o] = fin(row[e]);
             } else {
                 A.ids[o] = -1;
                 A.scores[o] = -INFINITY;
@@ -583,8 +624,9 @@ extern "C" int64_t mkb_topk_workspace_bytes(const mkb_tables_t *tb, int64_t B, i
     return mkb_rank_workspace_bytes(tb, B);
 }
 
-extern "C" int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true,
-                        int k, int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream) {
+// mkb_topk and mkb_topk_masked (cand_bits == null: the kTopkPlain launch of mkb_topk itself)
+static int topk_impl(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true,
+                     const uint32_t *cand_bits, int k, int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream) {
     if (int rc = validate_tables(tb)) return rc;
     MKB_REQUIRE(sample && ids && scores && ws && (true_keys || n_true == 0) && n_true >= 0, "null pointer");
     MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "mkb_topk needs head-batch or tail-batch");
@@ -599,9 +641,41 @@ extern "C" int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B
     hipStream_t st = (hipStream_t)stream;
     const bool head = mode == MKB_MODE_HEAD;
     auto finish = [&](float f0, float f1, int64_t ld) {
-        TopkArgs A{w.S, sample, true_keys, ids, scores, B, tb->n_entity, tb->n_relation, n_true, ld, head ? 1 : 0, k,
-                   (flags & MKB_TOPK_KEEP_TARGET) ? 1 : 0, f0, f1};
-        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)std::min<int64_t>(B, 1 << 20)), dim3(kTopkThreads), 0, st, A);  // (queries loop past the grid)
+        const TopkArgs A{w.S, sample, true_keys, ids, scores, B, tb->n_entity, tb->n_relation, n_true, ld, head ? 1 : 0, k,
+                         (flags & MKB_TOPK_KEEP_TARGET) ? 1 : 0, f0, f1};
+        const dim3 grid((unsigned)std::min<int64_t>(B, 1 << 20));  // (queries loop past the grid)
+        if (cand_bits) {
+            TopkMaskedArgs M;
+            static_cast<TopkArgs &>(M) = A;
+            M.cand = cand_bits;
+            hipLaunchKernelGGL((topk_kernel<kTopkMasked, TopkMaskedArgs>), grid, dim3(kTopkThreads), 0, st, M);
+        } else {
+            hipLaunchKernelGGL(topk_kernel<kTopkPlain>, grid, dim3(kTopkThreads), 0, st, A);
+        }
     };
     return run_all(tb, sample, B, head, w.Q, w.S, w.ids, st, finish);
+}
+
+extern "C" int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true,
+                        int k, int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream) {
+    return topk_impl(tb, sample, B, mode, true_keys, n_true, nullptr, k, flags, ids, scores, ws, ws_bytes, stream);
+}
+
+extern "C" int mkb_topk_masked(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys,
+                               int64_t n_true, const uint32_t *cand_bits, int k, int flags, int64_t *ids, float *scores, void *ws,
+                               int64_t ws_bytes, void *stream) {
+    return topk_impl(tb, sample, B, mode, true_keys, n_true, cand_bits, k, flags, ids, scores, ws, ws_bytes, stream);
+}
+
+extern "C" int mkb_topk_block(const float *S, int64_t B, int64_t N, int64_t ld, int k, int64_t *ids, float *scores, void *stream) {
+    MKB_REQUIRE(S && ids && scores, "null pointer");
+    MKB_REQUIRE(k >= 1 && k <= MKB_TOPK_MAX_K, "k must lie in [1, %d]", MKB_TOPK_MAX_K);
+    MKB_REQUIRE(B >= 0 && B <= INT32_MAX, "bad B");
+    MKB_REQUIRE(N >= 1 && N <= INT32_MAX, "N must lie in [1, 2^31 - 1]");
+    MKB_REQUIRE(ld >= N, "ld must be >= N");
+    if (B == 0) return MKB_OK;
+    TopkArgs A{S, nullptr, nullptr, ids, scores, B, N, 0, 0, ld, 0, k, 0, 0.f, 1.f};
+    hipLaunchKernelGGL(topk_kernel<kTopkBlock>, dim3((unsigned)std::min<int64_t>(B, 1 << 20)), dim3(kTopkThreads), 0, (hipStream_t)stream, A);
+    MKB_LAUNCH_CHECK();
+    return MKB_OK;
 }

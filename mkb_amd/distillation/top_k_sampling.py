@@ -1,0 +1,259 @@
+"""Teacher top-k candidate samplers for distillation (reference mkb/distillation/top_k_sampling.py:9-662): ``TopKSampling`` picks,
+for every positive triple, the k entities / relations the teacher scores highest among those both graphs share;
+``FastTopKSampling`` precomputes those lists over the teacher's training triples once and looks them up.  Unsupervised: the
+ground truth is not put into the lists, so ``Distillation`` distils each part of a triple whose other two parts are shared.
+
+The reference loops over the triples on the host with three ``argsort``s per triple.  Here the entity sides are one
+``mkb_topk_masked`` launch per side and batch (the all-entity score block, restricted to the shared entities by a bitmask), the
+relation side one general forward of the ``[b, shared relations, 3]`` block (as ``Evaluation.relation_ranks`` scores it) and one
+``mkb_topk_block``; the ids are mapped with device tables.  The TransE teacher of ``FastTopKSampling`` takes the reference's faiss
+L2 index (``TopKSamplingTransE``), which is not part of mkb_amd."""
+import collections
+
+import numpy as np
+import torch
+
+from .. import _hip
+from ..utils.predict_top_k import _launch, candidate_bits, topk_block
+
+__all__ = ["FastTopKSampling", "TopKSampling"]
+
+
+def _shared(teacher, student):
+    """teacher id -> student id of the labels both know, in the teacher dict's order (the reference's mapping)."""
+    return collections.OrderedDict((i, student[label]) for label, i in teacher.items() if label in student)
+
+
+def _check_k(k, n_shared, what):
+    if not 1 <= k <= _hip.TOPK_MAX_K:
+        raise ValueError(f"batch_size_{what} must lie in [1, {_hip.TOPK_MAX_K}], got {k}")
+    if k > n_shared:
+        raise ValueError(f"batch_size_{what} = {k} is larger than the {n_shared} {what} teacher and student share")
+
+
+class _Random:
+    """The random columns of the reference's ``_randomize_distribution`` (top_k_sampling.py:877-960): one draw of entities, then
+    one of relations, per call, from the sampler's ``RandomState``; the same draw goes to every row."""
+
+    def _random_columns(self, b, dev, outs):
+        head_t, rel_t, tail_t, head_s, rel_s, tail_s = outs
+        if self.n_random_entities > 0:
+            t = self._rng.choice(list(self.mapping_entities.keys()), size=self.n_random_entities, replace=False)
+            s = [self.mapping_entities[i] for i in t]
+            t, s = (torch.as_tensor(np.asarray(x, dtype=np.int64)).to(dev).view(1, -1).expand(b, -1) for x in (t, s))
+            head_t, tail_t = torch.cat([head_t, t], dim=1), torch.cat([tail_t, t], dim=1)
+            head_s, tail_s = torch.cat([head_s, s], dim=1), torch.cat([tail_s, s], dim=1)
+        if self.n_random_relations > 0:
+            t = self._rng.choice(list(self.mapping_relations.keys()), size=self.n_random_relations, replace=False)
+            s = [self.mapping_relations[i] for i in t]
+            t, s = (torch.as_tensor(np.asarray(x, dtype=np.int64)).to(dev).view(1, -1).expand(b, -1) for x in (t, s))
+            rel_t, rel_s = torch.cat([rel_t, t], dim=1), torch.cat([rel_s, s], dim=1)
+        return head_t, rel_t, tail_t, head_s, rel_s, tail_s
+
+    @property
+    def batch_size_entity(self):
+        return self.batch_size_entity_top_k + self.n_random_entities
+
+    @property
+    def batch_size_relation(self):
+        return self.batch_size_relation_top_k + self.n_random_relations
+
+
+class TopKSampling(_Random):
+    """The teacher's top ``batch_size_entity`` heads and tails and top ``batch_size_relation`` relations of every triple of
+    ``sample``, among the entities / relations teacher and student share, followed by ``n_random_entities`` /
+    ``n_random_relations`` random shared ones (reference top_k_sampling.py:267-662).
+
+    ``get(sample, teacher)`` -> six int64 tensors on ``sample``'s device: head, relation and tail candidates in teacher ids,
+    then the same in student ids, ``[b, batch_size_entity]`` / ``[b, batch_size_relation]``.
+
+    Two differences from the reference, both where it is ill-defined:
+      - equal teacher scores are ordered by lower teacher id (the reference's ``argsort`` leaves their order unspecified);
+      - the teacher relation list holds teacher relation ids.  The reference returns student ids there
+        (``relations_student[rank_relations]``): the same list whenever both graphs number their shared relations alike;
+        where they do not, it scores the teacher on the wrong relations or indexes out of its table.
+    A top k larger than the number of shared entities / relations raises ``ValueError`` (the reference would return fewer
+    columns and fail later)."""
+
+    supervised = False  # the ground truth is not part of the distributions
+    depends_on_teacher = True  # KdmkbModel.learn rebuilds it as the teacher trains
+
+    def __init__(self, teacher_entities, teacher_relations, student_entities, student_relations, batch_size_entity,
+                 batch_size_relation, n_random_entities, n_random_relations, device="cpu", seed=None, **kwargs):
+        self.batch_size_entity_top_k, self.batch_size_relation_top_k = batch_size_entity, batch_size_relation
+        self.n_random_entities, self.n_random_relations = n_random_entities, n_random_relations
+        self.device = device
+        self._rng = np.random.RandomState(seed)
+        self.mapping_entities = _shared(teacher_entities, student_entities)
+        self.mapping_relations = _shared(teacher_relations, student_relations)
+        self.n_teacher_entities, self.n_teacher_relations = len(teacher_entities), len(teacher_relations)
+        _check_k(batch_size_entity, len(self.mapping_entities), "entity")
+        _check_k(batch_size_relation, len(self.mapping_relations), "relation")
+        for what, n, shared in (("entity", n_random_entities, self.mapping_entities),
+                                ("relation", n_random_relations, self.mapping_relations)):
+            if n < 0 or n > len(shared):
+                raise ValueError(f"n_random_{what} = {n} must lie in [0, {len(shared)}]")
+        self._tables = {}
+
+    def tables(self, device):
+        """-> dict of device tables: ``ent_bits`` (the shared teacher entities as an mkb_topk_masked bitmask), ``ent_map`` /
+        ``rel_map`` (teacher id -> student id, -1 = not shared), ``rel_t`` / ``rel_s`` (the shared relations, ascending teacher
+        id, and their student ids)."""
+        device = torch.device(device)
+        tb = self._tables.get(device)
+        if tb is None:
+            def lookup(mapping, n):
+                out = torch.full((n,), -1, dtype=torch.int64)
+                out[torch.tensor(list(mapping.keys()), dtype=torch.int64)] = torch.tensor(list(mapping.values()), dtype=torch.int64)
+                return out.to(device)
+            rel_t = torch.tensor(sorted(self.mapping_relations), dtype=torch.int64)
+            tb = self._tables[device] = {
+                "ent_bits": candidate_bits(torch.tensor(list(self.mapping_entities), dtype=torch.int64), self.n_teacher_entities, device),
+                "ent_map": lookup(self.mapping_entities, self.n_teacher_entities),
+                "rel_map": lookup(self.mapping_relations, self.n_teacher_relations),
+                "rel_t": rel_t.to(device),
+                "rel_s": torch.tensor([self.mapping_relations[int(r)] for r in rel_t], dtype=torch.int64).to(device),
+            }
+        return tb
+
+    def _check_teacher(self, teacher):
+        if teacher.n_entity != self.n_teacher_entities or teacher.n_relation != self.n_teacher_relations:
+            raise ValueError(f"the teacher's tables ({teacher.n_entity} entities, {teacher.n_relation} relations) do not match "
+                             f"teacher_entities / teacher_relations ({self.n_teacher_entities}, {self.n_teacher_relations})")
+
+    def top_k(self, sample, teacher, chunk=1024):
+        """-> (heads, relations, tails) in teacher ids, then the same in student ids: the top-k columns only, on the teacher's
+        device, for ``sample`` [b, 3] int64 on that device.  No random columns, no synchronisation."""
+        dev = teacher.entity_embedding.device
+        tb = self.tables(dev)
+        b = sample.shape[0]
+        ke, kr = self.batch_size_entity_top_k, self.batch_size_relation_top_k
+        none = torch.empty(0, dtype=torch.int64, device=dev)
+        out = []
+        for mode in ("head-batch", "tail-batch"):  # the shared entities only, nothing filtered
+            ids = torch.empty((b, ke), dtype=torch.int64, device=dev)
+            _launch(teacher, sample, mode, ke, none, 0, tb["ent_bits"], chunk, ids, torch.empty((b, ke), dtype=torch.float32, device=dev))
+            out.append(ids)
+        heads_t, tails_t = out
+        rel_pos = torch.empty((b, kr), dtype=torch.int64, device=dev)
+        rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
+        for lo in range(0, b, chunk):  # the relation side: the general forward of [b, R_shared, 3], then the block selection
+            s = sample[lo: lo + chunk]
+            block = torch.stack([s[:, 0:1].expand(-1, n_rel), rel_t.view(1, -1).expand(s.shape[0], -1),
+                                 s[:, 2:3].expand(-1, n_rel)], dim=-1)
+            score = teacher(block.contiguous()).reshape(s.shape[0], n_rel).float().contiguous()
+            topk_block(score, kr, ids=rel_pos[lo: lo + chunk])
+        rels_t = rel_t[rel_pos]
+        return heads_t, rels_t, tails_t, tb["ent_map"][heads_t], tb["rel_s"][rel_pos], tb["ent_map"][tails_t]
+
+    def get(self, sample, teacher, **kwargs):
+        """-> (head, relation, tail distributions of the teacher, then of the student): int64 on ``sample``'s device."""
+        _hip.require_device(teacher.entity_embedding)
+        self._check_teacher(teacher)
+        out_dev = sample.device
+        dev = teacher.entity_embedding.device
+        teacher.sync_parameters()  # (rows a row-lazy Adam has not brought current yet)
+        with torch.no_grad():
+            s = sample.to(device=dev, dtype=torch.int64).reshape(-1, 3).contiguous()
+            b = s.shape[0]
+            if b:
+                outs = self.top_k(s, teacher)
+            else:
+                ke, kr = self.batch_size_entity_top_k, self.batch_size_relation_top_k
+                outs = tuple(torch.empty((0, k), dtype=torch.int64, device=dev) for k in (ke, kr, ke, ke, kr, ke))
+            outs = self._random_columns(b, dev, outs)
+        return tuple(x.contiguous().to(out_dev) for x in outs)
+
+
+class FastTopKSampling(_Random):
+    """``TopKSampling`` precomputed over the teacher's training triples when it is built (reference top_k_sampling.py:9-264):
+    for every distinct (r, t) of ``dataset_teacher``'s triples the teacher's top heads, for every distinct (h, t) its top
+    relations, for every distinct (h, r) its top tails -- on the device, ``chunk`` queries at a time.  ``get`` looks the rows of
+    a sample up (``KeyError`` for a key that was not precomputed, like the reference's dicts) and appends the random columns.
+
+    Building it walks ``dataset_teacher`` once as the reference does (its loaders draw their seeds from torch's global generator
+    when their iterators are created), so a seeded run keeps the reference's batch order.  A TransE teacher raises
+    ``ImportError``: the reference hands it to a faiss L2 index, which mkb_amd does not provide."""
+
+    supervised = False
+    depends_on_teacher = True
+
+    def __init__(self, teacher_entities, teacher_relations, student_entities, student_relations, batch_size_entity,
+                 batch_size_relation, n_random_entities, n_random_relations, dataset_teacher, teacher, device="cpu", seed=None,
+                 chunk=1024, **kwargs):
+        if teacher.name == "TransE":
+            raise ImportError("FastTopKSampling with a TransE teacher needs the faiss L2 index of the reference's "
+                              "TopKSamplingTransE (No module named 'faiss'); use another teacher or TopKSampling")
+        base = TopKSampling(teacher_entities=teacher_entities, teacher_relations=teacher_relations,
+                            student_entities=student_entities, student_relations=student_relations,
+                            batch_size_entity=batch_size_entity, batch_size_relation=batch_size_relation, n_random_entities=0,
+                            n_random_relations=0, device=device, seed=seed)
+        self.mapping_entities, self.mapping_relations = base.mapping_entities, base.mapping_relations
+        self.batch_size_entity_top_k, self.batch_size_relation_top_k = batch_size_entity, batch_size_relation
+        self.n_random_entities, self.n_random_relations = n_random_entities, n_random_relations
+        if n_random_entities > len(self.mapping_entities) or n_random_relations > len(self.mapping_relations) \
+                or min(n_random_entities, n_random_relations) < 0:
+            raise ValueError("n_random_entities / n_random_relations must lie in [0, the number of shared entities / relations]")
+        self._rng = np.random.RandomState(seed)
+        self.device = device
+        _hip.require_device(teacher.entity_embedding)
+        base._check_teacher(teacher)
+        # the reference's pass over the teacher's training batches (its dicts are filled from the head-batch ones)
+        batches = [data["sample"] for data in dataset_teacher if data["mode"] == "head-batch"]
+        dev = teacher.entity_embedding.device
+        N, R = teacher.n_entity, teacher.n_relation
+        tri = torch.cat(batches).to(device=dev, dtype=torch.int64) if batches else torch.empty((0, 3), dtype=torch.int64, device=dev)
+        h, r, t = tri[:, 0], tri[:, 1], tri[:, 2]
+        teacher.sync_parameters()
+        self._keys = {}
+        with torch.no_grad():
+            tb = base.tables(dev)
+            ke, kr = batch_size_entity, batch_size_relation
+            none = torch.empty(0, dtype=torch.int64, device=dev)
+            # heads of (?, r, t) and tails of (h, r, ?): one masked top k per distinct key
+            for part, key, mode, cols in (("head", r * N + t, "head-batch", lambda u: (u // N, u % N)),
+                                          ("tail", h * R + r, "tail-batch", lambda u: (u // R, u % R))):
+                u = torch.unique(key)
+                a, c = cols(u)
+                q = torch.stack([torch.zeros_like(a), a, c], 1) if part == "head" else torch.stack([a, c, torch.zeros_like(a)], 1)
+                ids = torch.empty((u.numel(), ke), dtype=torch.int64, device=dev)
+                if u.numel():
+                    _launch(teacher, q.contiguous(), mode, ke, none, 0, tb["ent_bits"], chunk, ids,
+                            torch.empty((u.numel(), ke), dtype=torch.float32, device=dev))
+                self._keys[part] = (u, ids, tb["ent_map"][ids])
+            # relations of (h, ?, t)
+            u = torch.unique(h * N + t)
+            q = torch.stack([u // N, torch.zeros_like(u), u % N], 1).contiguous()
+            pos = torch.empty((u.numel(), kr), dtype=torch.int64, device=dev)
+            rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
+            for lo in range(0, u.numel(), chunk):
+                s = q[lo: lo + chunk]
+                block = torch.stack([s[:, 0:1].expand(-1, n_rel), rel_t.view(1, -1).expand(s.shape[0], -1),
+                                     s[:, 2:3].expand(-1, n_rel)], dim=-1)
+                score = teacher(block.contiguous()).reshape(s.shape[0], n_rel).float().contiguous()
+                topk_block(score, kr, ids=pos[lo: lo + chunk])
+            self._keys["relation"] = (u, rel_t[pos], tb["rel_s"][pos])
+        self._N, self._R = N, R
+
+    def _rows(self, part, key):
+        keys, t, s = self._keys[part]
+        if keys.numel() == 0:
+            raise KeyError(f"no {part} distribution was precomputed")
+        key = key.to(keys.device)
+        pos = torch.searchsorted(keys, key).clamp_(max=keys.numel() - 1)
+        missing = keys[pos] != key
+        if bool(missing.any()):
+            raise KeyError(f"{part} distribution of a triple whose key was not among the teacher's training triples")
+        return t[pos], s[pos]
+
+    def get(self, sample, **kwargs):
+        """-> (head, relation, tail distributions of the teacher, then of the student): int64 on ``sample``'s device."""
+        out_dev = sample.device
+        dev = self._keys["head"][0].device
+        s = sample.to(device=dev, dtype=torch.int64).reshape(-1, 3)
+        h, r, t = s[:, 0], s[:, 1], s[:, 2]
+        head_t, head_s = self._rows("head", r * self._N + t)
+        rel_t, rel_s = self._rows("relation", h * self._N + t)
+        tail_t, tail_s = self._rows("tail", h * self._R + r)
+        outs = self._random_columns(s.shape[0], dev, (head_t, rel_t, tail_t, head_s, rel_s, tail_s))
+        return tuple(x.contiguous().to(out_dev) for x in outs)

@@ -474,6 +474,100 @@ def gen_distill():
     (OUT / "distill.json").write_text(json.dumps(js, indent=1))
 
 
+def _topk_gaps(teacher, sample, ents, rels, k_e, k_r):
+    """Smallest gap between the k-th and (k+1)-th teacher score over the rows of `sample` (heads, relations, tails), on the
+    shared entities `ents` / relations `rels`: above 1e-4, an fp32 near-tie cannot reorder the device's selection."""
+    gaps = []
+    with torch.no_grad():
+        e = torch.tensor([ents])
+        for mode in ("head-batch", "tail-batch"):
+            sc = teacher(sample, e.expand(sample.shape[0], -1).contiguous(), mode).sort(dim=1, descending=True).values
+            if sc.shape[1] > k_e:
+                gaps.append((sc[:, k_e - 1] - sc[:, k_e]).min().item())
+        if len(rels) > k_r:
+            blk = torch.stack([sample[:, 0:1].expand(-1, len(rels)), torch.tensor([rels]).expand(sample.shape[0], -1),
+                               sample[:, 2:3].expand(-1, len(rels))], dim=-1)
+            sc = teacher(blk).sort(dim=1, descending=True).values
+            gaps.append((sc[:, k_r - 1] - sc[:, k_r]).min().item())
+    return min(gaps)
+
+
+def gen_topk_sampling():
+    """Teacher top-k samplers (distillation/top_k_sampling.py) captured from the live reference: (a) TopKSampling.get on
+    CountriesS1 (teacher and student the same graph) for RotatE / ComplEx / DistMult teachers, several batches, random columns
+    on; (b) Distillation.distill with TopKSampling (the unsupervised branch): loss and student gradients; (c) KdmkbModel.forward,
+    3 steps on two CountriesS1 copies with the reference's real default sampler (FastTopKSampling): per-step losses and final
+    tables.  Each case records the smallest gap between the k-th and (k+1)-th teacher score of the rows it selects."""
+    from mkb import distillation
+    out, js = {}, {"gaps": {}}
+    ds = datasets.CountriesS1(batch_size=6, seed=42, shuffle=False)
+    ents = sorted(ds.entities.values())
+    rels = sorted(ds.relations.values())
+    it = iter(ds)
+    batches = [next(it)["sample"] for _ in range(4)]
+    out["get/samples"] = np.stack([npy(b) for b in batches])
+    for cls, seed, hid in (("RotatE", 11, 6), ("ComplEx", 15, 6), ("DistMult", 13, 8)):
+        torch.manual_seed(seed)
+        teacher = getattr(models, cls)(hidden_dim=hid, entities=ds.entities, relations=ds.relations, gamma=4)
+        out[f"get/{cls}/ent"], out[f"get/{cls}/rel"] = npy(teacher.entity_embedding), npy(teacher.relation_embedding)
+        sampler = distillation.TopKSampling(teacher_entities=ds.entities, teacher_relations=ds.relations, student_entities=ds.entities,
+                                            student_relations=ds.relations, batch_size_entity=5, batch_size_relation=1,
+                                            n_random_entities=3, n_random_relations=1, seed=7)
+        gaps = []
+        for j, b in enumerate(batches):
+            got = sampler.get(sample=b, teacher=teacher)
+            for name, x in zip(("head_t", "rel_t", "tail_t", "head_s", "rel_s", "tail_s"), got):
+                out[f"get/{cls}/{j}/{name}"] = npy(x)
+            gaps.append(_topk_gaps(teacher, b, ents, rels, 5, 1))
+        js["gaps"][f"get/{cls}"] = min(gaps)
+
+    # (b) Distillation.distill with TopKSampling on Umls (RotatE teaches DistMult)
+    du = datasets.Umls(batch_size=5, shuffle=False, seed=42)
+    torch.manual_seed(3)
+    teacher = models.RotatE(hidden_dim=6, entities=du.entities, relations=du.relations, gamma=6)
+    student = models.DistMult(hidden_dim=8, entities=du.entities, relations=du.relations, gamma=6)
+    sampler = distillation.TopKSampling(teacher_entities=du.entities, teacher_relations=du.relations, student_entities=du.entities,
+                                        student_relations=du.relations, batch_size_entity=4, batch_size_relation=3,
+                                        n_random_entities=2, n_random_relations=2, seed=9)
+    proc = distillation.Distillation(teacher_entities=du.entities, student_entities=du.entities, teacher_relations=du.relations,
+                                     student_relations=du.relations, sampling=sampler)
+    sample = next(iter(du))["sample"]
+    js["gaps"]["distill"] = _topk_gaps(teacher, sample, sorted(du.entities.values()), sorted(du.relations.values()), 4, 3)
+    loss = proc.distill(teacher=teacher, student=student, sample=sample)
+    loss.backward()
+    out["distill/teacher_ent"], out["distill/teacher_rel"] = npy(teacher.entity_embedding), npy(teacher.relation_embedding)
+    out["distill/student_ent"], out["distill/student_rel"] = npy(student.entity_embedding), npy(student.relation_embedding)
+    out["distill/sample"], out["distill/loss"] = npy(sample), npy(loss)
+    out["distill/g_ent"], out["distill/g_rel"] = npy(student.entity_embedding.grad), npy(student.relation_embedding.grad)
+
+    # (c) KdmkbModel with its real default sampler (FastTopKSampling): two RotatE models of different sizes teaching each other
+    # (ComplEx / DistMult at this size leave top-k gaps below 1e-4 somewhere in the training split)
+    from mkb.distillation import kdmkb_model as km
+    torch.manual_seed(42)
+    d1 = datasets.CountriesS1(batch_size=8, seed=42)
+    d2 = datasets.CountriesS1(batch_size=8, seed=42)
+    m1 = models.RotatE(hidden_dim=6, entities=d1.entities, relations=d1.relations, gamma=3)
+    m2 = models.RotatE(hidden_dim=4, entities=d2.entities, relations=d2.relations, gamma=3)
+    out["kd/m1_ent"], out["kd/m1_rel"], out["kd/m2_ent"], out["kd/m2_rel"] = (npy(m1.entity_embedding), npy(m1.relation_embedding),
+                                                                              npy(m2.entity_embedding), npy(m2.relation_embedding))
+    train = torch.tensor(d1.train)
+    js["gaps"]["kd"] = min(_topk_gaps(m, train, sorted(d1.entities.values()), sorted(d1.relations.values()), 4, 1) for m in (m1, m2))
+    mods, dsets = collections.OrderedDict(a=m1, b=m2), collections.OrderedDict(a=d1, b=d2)
+    kd = km.KdmkbModel(models=mods, datasets=dsets, lr={"a": 1e-2, "b": 1e-2}, alpha_kl={"a": 0.3, "b": 0.6},
+                       alpha_adv={"a": 0.5, "b": 0.5}, negative_sampling_size={"a": 4, "b": 4}, batch_size_entity={"a": 4, "b": 4},
+                       batch_size_relation={"a": 1, "b": 1}, n_random_entities={"a": 3, "b": 2}, n_random_relations={"a": 1, "b": 1},
+                       device="cpu", seed=42)
+    steps = []
+    for step in range(3):
+        kd.forward(dsets, mods, {"a": 0.3, "b": 0.6})
+        steps.append({k: kd.metrics[k].w[-1] for k in mods})
+    js["kd_step_losses"] = steps
+    out["kd/m1_ent_after"], out["kd/m2_ent_after"] = npy(m1.entity_embedding), npy(m2.entity_embedding)
+    out["kd/m1_rel_after"], out["kd/m2_rel_after"] = npy(m1.relation_embedding), npy(m2.relation_embedding)
+    np.savez_compressed(OUT / "topk_sampling.npz", **out)
+    (OUT / "topk_sampling.json").write_text(json.dumps(js, indent=1))
+
+
 if __name__ == "__main__":
     OUT.mkdir(parents=True, exist_ok=True)
     which = sys.argv[1:] or ["models", "init", "sampler", "weights", "pipeline", "eval", "headline_slice", "distill", "eval_headline"]
