@@ -414,6 +414,23 @@ int mkb_topk_masked(const mkb_tables_t *tb, const int64_t *sample, int64_t B, in
  * bit; -1 / -inf past the N columns).  No keys, no finisher, no workspace.  1 <= k <= MKB_TOPK_MAX_K, 0 <= B <= 2^31 - 1 (B = 0:
  * nothing), 1 <= N <= 2^31 - 1, ld >= N, non-null pointers; otherwise MKB_ERR_INVALID before any launch. */
 int mkb_topk_block(const float *S, int64_t B, int64_t N, int64_t ld, int k, int64_t *ids, float *scores, void *stream);
+/* Exact squared-L2 k nearest rows (a flat L2 index; the distillation sampler of TransE teachers): for each query row i of Q [B, D]
+ * fp32 (device, rows ldq >= D floats apart) the k candidates c of cand [n_cand] int64 (device; row ids of X, rows ldx >= D floats
+ * apart, duplicates allowed) with the smallest d(i, c) = sum_j (Q[i, j] - X[cand[c], j])^2, computed in this difference form (not
+ * |q|^2 + |x|^2 - 2 q.x, which loses the distance under a large common offset).
+ *   ids [B, k] int64: the cand VALUES, nearest first; dists [B, k] fp32: their distances.  Equal distances go to the lower position
+ *   in cand; a NaN distance comes before every number (NaN rows first, lower position first among them).  When k > n_cand the
+ *   trailing slots hold id -1 and distance +inf.  The distances are bit-identical on every shape and route.
+ *   1 <= k <= MKB_TOPK_MAX_K, 0 <= B <= 2^31 - 1 (B = 0: nothing), 1 <= n_cand <= 2^31 - 1, D >= 1, ldq >= D, ldx >= D, non-null
+ *   pointers, ws of mkb_topk_nearest_workspace_bytes(B, n_cand, k) bytes, 256-byte aligned (0 bytes for B = 0 or a bad argument);
+ *   otherwise MKB_ERR_INVALID before any launch.  Every cand value must be a row of X (not checked: device memory).  ABI 7. */
+int64_t mkb_topk_nearest_workspace_bytes(int64_t B, int64_t n_cand, int k);
+int mkb_topk_nearest(const float *Q, int64_t ldq, const float *X, int64_t ldx, const int64_t *cand, int64_t n_cand, int64_t B,
+                     int64_t D, int k, int64_t *ids, float *dists, void *ws, int64_t ws_bytes, void *stream);
+/* The same, and the whole distance block the selection ran on handed out as well: block [B, n_cand] fp32 (device, rows n_cand
+ * apart; the tests' reference).  Arguments and workspace as above; a null block -> MKB_ERR_INVALID. */
+int mkb_topk_nearest_dists(const float *Q, int64_t ldq, const float *X, int64_t ldx, const int64_t *cand, int64_t n_cand, int64_t B,
+                           int64_t D, int k, int64_t *ids, float *dists, float *block, void *ws, int64_t ws_bytes, void *stream);
 
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream

@@ -144,6 +144,11 @@ _SIGNATURES = {
     "mkb_topk_masked": (c_int, [POINTER(Tables), c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p,
                                 c_void_p, c_void_p, c_int64, c_void_p]),
     "mkb_topk_block": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "mkb_topk_nearest_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
+    "mkb_topk_nearest": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_int64, c_void_p]),
+    "mkb_topk_nearest_dists": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -262,8 +262,11 @@ __global__ __launch_bounds__(256) void iota_kernel(int64_t *ids, int64_t n, int6
 //                  on top of the kernel's 25 KB) and cost occupancy on every shape;
 //   kTopkBlock  -- mkb_topk_block: a caller's fp32 block [B, N] with row stride ld: no sample, no true keys, no finisher (the
 //                  scores handed out are the block's own values, bit for bit).
+// and a fourth, kTopkNearest (mkb_topk_nearest): kTopkBlock on a block of squared L2 distances, selected on -d (the k SMALLEST
+// distances; NaN first, ties to the lower column as before); out go the candidate ids cand[column] and the distances themselves,
+// padded with -1 / +inf.
 constexpr int kTopkThreads = 256, kTopkCap = 2048;
-constexpr int kTopkPlain = 0, kTopkMasked = 1, kTopkBlock = 2;
+constexpr int kTopkPlain = 0, kTopkMasked = 1, kTopkBlock = 2, kTopkNearest = 3;
 
 __device__ __forceinline__ uint32_t order_image(float f) {
     if (f != f) return 0xFFFFFFFFu;
@@ -285,12 +288,16 @@ struct TopkArgs {
 struct TopkMaskedArgs : TopkArgs {
     const uint32_t *cand;
 };
+// kTopkNearest's arguments: the candidate ids [N] of the block's columns
+struct TopkNearestArgs : TopkArgs {
+    const int64_t *cand;
+};
 
 // (static: with internal linkage the kTopkPlain instantiation compiles to the very code and LDS layout of the non-template kernel
 // mkb_topk launched before the two other instantiations were added)
 template <int VAR, class Args = TopkArgs>
 static __global__ __launch_bounds__(kTopkThreads) void topk_kernel(Args A) {
-    constexpr bool MASKED = VAR == kTopkMasked, BLOCK = VAR == kTopkBlock;
+    constexpr bool MASKED = VAR == kTopkMasked, NEAREST = VAR == kTopkNearest, BLOCK = VAR == kTopkBlock || NEAREST;
     __shared__ uint32_t s_hist[2048];
     __shared__ uint32_t s_scan[kTopkThreads];
     __shared__ uint64_t s_buf[kTopkCap];
@@ -314,7 +321,8 @@ static __global__ __launch_bounds__(kTopkThreads) void topk_kernel(Args A) {
         __syncthreads();
         const int64_t klo = s_range[0], khi = s_range[1];
         auto fin = [&](float x) {
-            if constexpr (BLOCK) return x;
+            if constexpr (NEAREST) return -x;
+            else if constexpr (BLOCK) return x;
             else return A.c0 + A.c1 * x;
         };
         auto image = [&](int64_t e) { return order_image(fin(row[e])); };
@@ -470,14 +478,47 @@ static __global__ __launch_bounds__(kTopkThreads) void topk_kernel(Args A) {
             const int64_t o = i * A.k + j;
             if ((uint32_t)j < n) {
                 const int64_t e = (int64_t)(uint32_t)~(uint32_t)s_buf[j];
-                A.ids[o] = e;
-                A.scores[o] = fin(row[e]);
+                if constexpr (NEAREST) {
+                    A.ids[o] = A.cand[e];
+                    A.scores[o] = row[e];
+                } else {
+                    A.ids[o] = e;
+                    A.scores[o] = fin(row[e]);
+                }
             } else {
                 A.ids[o] = -1;
-                A.scores[o] = -INFINITY;
+                A.scores[o] = NEAREST ? INFINITY : -INFINITY;
             }
         }
         __syncthreads();
+    }
+}
+
+// ---- exact squared-L2 k nearest rows (mkb_topk_nearest) ------------------------------------------------------------------------
+// S[i, c] = sum_j (Q[i, j] - X[cand[c], j])^2 on the general route (any D, any row strides, any alignment): one lane per candidate,
+// the queries loop over grid.y.  The even elements and the odd ones are summed in two fma chains and added at the end, the order of
+// the register tile's kTileL2 accumulators (score_pool_tile.h), so that both routes give the same bits.  Not a hot path: the
+// product's rows take the tile (D % 4 == 0, D >= 64, contiguous rows).
+__global__ __launch_bounds__(256) void l2_block_kernel(const float *__restrict__ Q, int64_t ldq, const float *__restrict__ X, int64_t ldx,
+                                                       const int64_t *__restrict__ cand, int64_t n_cand, int64_t B, int64_t D,
+                                                       float *__restrict__ S) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cand) return;
+    const float *x = X + cand[c] * ldx;
+    for (int64_t i = blockIdx.y; i < B; i += gridDim.y) {
+        const float *q = Q + i * ldq;
+        float ev = 0.f, od = 0.f;
+        int64_t j = 0;
+        for (; j + 1 < D; j += 2) {
+            const float a = q[j] - x[j], b = q[j + 1] - x[j + 1];
+            ev = fmaf(a, a, ev);
+            od = fmaf(b, b, od);
+        }
+        if (j < D) {
+            const float a = q[j] - x[j];
+            ev = fmaf(a, a, ev);
+        }
+        S[i * n_cand + c] = ev + od;
     }
 }
 
@@ -678,4 +719,72 @@ extern "C" int mkb_topk_block(const float *S, int64_t B, int64_t N, int64_t ld, 
     hipLaunchKernelGGL(topk_kernel<kTopkBlock>, dim3((unsigned)std::min<int64_t>(B, 1 << 20)), dim3(kTopkThreads), 0, (hipStream_t)stream, A);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
+}
+
+// Queries per pass of mkb_topk_nearest: the [rows, n_cand] distance block of one pass is about 2^24 floats (64 MB; 1,152 queries at
+// FB15k-237's 14,541 candidates), a multiple of the tile's 64 rows and at least 64 of them.
+static int64_t nearest_rows(int64_t B, int64_t n_cand) {
+    const int64_t r = ((int64_t)1 << 24) / n_cand / kTileRows * kTileRows;
+    return std::min(B, std::max<int64_t>(r, kTileRows));
+}
+
+extern "C" int64_t mkb_topk_nearest_workspace_bytes(int64_t B, int64_t n_cand, int k) {
+    if (k < 1 || k > MKB_TOPK_MAX_K || B <= 0 || B > INT32_MAX || n_cand < 1 || n_cand > INT32_MAX) return 0;
+    return (int64_t)(((size_t)nearest_rows(B, n_cand) * (size_t)n_cand * 4 + 255) & ~(size_t)255);
+}
+
+// mkb_topk_nearest (block == null) and mkb_topk_nearest_dists: per pass of `rows` queries the distance block S [b, n_cand] in the
+// workspace (register tile or general route), its copy into block, and the kTopkNearest selection on it
+static int nearest_impl(const float *Q, int64_t ldq, const float *X, int64_t ldx, const int64_t *cand, int64_t n_cand, int64_t B,
+                        int64_t D, int k, int64_t *ids, float *dists, float *block, void *ws, int64_t ws_bytes, void *stream) {
+    MKB_REQUIRE(Q && X && cand && ids && dists, "null pointer");
+    MKB_REQUIRE(k >= 1 && k <= MKB_TOPK_MAX_K, "k must lie in [1, %d]", MKB_TOPK_MAX_K);
+    MKB_REQUIRE(B >= 0 && B <= INT32_MAX, "bad B");
+    MKB_REQUIRE(n_cand >= 1 && n_cand <= INT32_MAX, "n_cand must lie in [1, 2^31 - 1]");
+    MKB_REQUIRE(D >= 1 && ldq >= D && ldx >= D, "need D >= 1, ldq >= D and ldx >= D");
+    if (B == 0) return MKB_OK;
+    MKB_REQUIRE(ws && ws_bytes >= mkb_topk_nearest_workspace_bytes(B, n_cand, k) && (((uintptr_t)ws) & 255) == 0,
+                "workspace too small / unaligned");
+    hipStream_t st = (hipStream_t)stream;
+    float *S = (float *)ws;
+    const int64_t rows = nearest_rows(B, n_cand);
+    // the register tile reads rows of D floats, D apart, as float4 (S: the 256-byte aligned workspace)
+    const bool tile = D % 4 == 0 && D >= 64 && D <= INT32_MAX && ldq == D && ldx == D && n_cand < (1 << 30) &&
+                      (((uintptr_t)Q | (uintptr_t)X) & 15) == 0;
+    for (int64_t lo = 0; lo < B; lo += rows) {
+        const int64_t b = std::min(rows, B - lo);
+        const float *q = Q + lo * ldq;
+        if (tile) {  // the pooled forward's register tile, the candidate list as its pool (64 queries x 64 candidates per workgroup)
+            PoolArgs P{};
+            P.ent = X; P.Q = q; P.pool = cand; P.B = (int)b; P.P = (int)n_cand; P.De = D;
+            TileArgs T{};
+            T.part = S; T.Kd = (int)n_cand; T.ks = 1;
+            T.row_tiles = (int)((b + kTileRows - 1) / kTileRows); T.pos_tiles = (int)((n_cand + kTilePos - 1) / kTilePos);
+            hipLaunchKernelGGL((pool_fwd_tile_kernel<kTileL2, false, 2>), dim3((unsigned)T.row_tiles * (unsigned)T.pos_tiles), dim3(256), 0,
+                               st, P, T);
+        } else {
+            hipLaunchKernelGGL(l2_block_kernel, dim3((unsigned)((n_cand + 255) / 256), (unsigned)std::min<int64_t>(b, 1024)), dim3(256), 0,
+                               st, q, ldq, X, ldx, cand, n_cand, b, D, S);
+        }
+        if (block) MKB_CHECK_HIP(hipMemcpyAsync(block + lo * n_cand, S, (size_t)b * (size_t)n_cand * 4, hipMemcpyDeviceToDevice, st));
+        TopkNearestArgs A;
+        static_cast<TopkArgs &>(A) = TopkArgs{S, nullptr, nullptr, ids + lo * k, dists + lo * k, b, n_cand, 0, 0, n_cand, 0, k, 0, 0.f, 1.f};
+        A.cand = cand;
+        hipLaunchKernelGGL((topk_kernel<kTopkNearest, TopkNearestArgs>), dim3((unsigned)std::min<int64_t>(b, 1 << 20)), dim3(kTopkThreads),
+                           0, st, A);
+    }
+    MKB_LAUNCH_CHECK();
+    return MKB_OK;
+}
+
+extern "C" int mkb_topk_nearest(const float *Q, int64_t ldq, const float *X, int64_t ldx, const int64_t *cand, int64_t n_cand, int64_t B,
+                                int64_t D, int k, int64_t *ids, float *dists, void *ws, int64_t ws_bytes, void *stream) {
+    return nearest_impl(Q, ldq, X, ldx, cand, n_cand, B, D, k, ids, dists, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int mkb_topk_nearest_dists(const float *Q, int64_t ldq, const float *X, int64_t ldx, const int64_t *cand, int64_t n_cand,
+                                      int64_t B, int64_t D, int k, int64_t *ids, float *dists, float *block, void *ws, int64_t ws_bytes,
+                                      void *stream) {
+    MKB_REQUIRE(block, "null pointer");
+    return nearest_impl(Q, ldq, X, ldx, cand, n_cand, B, D, k, ids, dists, block, ws, ws_bytes, stream);
 }

@@ -46,6 +46,11 @@ struct TileArgs {
 // term; a chunk = kTileKC / 2 groups either way, so the staging, the LDS images and the 4 x 4 accumulators are shared and only
 // the loads' addresses and the pair function differ.  The real-valued term is 2 VALU operations per element against 8
 // ds_read_b128 per 64 elements and lane: the LDS array is busy about half the time.
+// Squared L2 distance sum_j (q_j - x_j)^2 of two rows (mkb_topk_nearest in rank.hip): an internal tag of the tile, not a model of
+// the library.  It is real-valued like TransE's term and uses the same staging and the same float4 groups.
+constexpr int kTileL2 = 16;
+template <> struct ModelTraits<kTileL2> { static constexpr bool cplx_query = false, cplx_pair = false, uses_gamma = false; };
+
 template <int MODEL, bool HEAD>
 __device__ __forceinline__ f2 tile_pair_term(float4 q, float4 x) {
     if constexpr (ModelTraits<MODEL>::cplx_pair) {
@@ -63,15 +68,31 @@ __device__ __forceinline__ f2 tile_pair_term(float4 q, float4 x) {
     }
 }
 
+// acc += the pair term of one group.  kTileL2: d = q - x; acc = fma(d, d, acc), packed -- 4 VALU operations per group of four
+// elements (TransE's term: 5).  acc.x then sums the squares of the even elements of the row in order, acc.y those of the odd
+// ones, and the distance is acc.x + acc.y (the general route of mkb_topk_nearest adds in the same order: both are bit-identical).
+template <int MODEL, bool HEAD>
+__device__ __forceinline__ void tile_pair_acc(f2 &acc, float4 q, float4 x) {
+    if constexpr (MODEL == kTileL2) {
+        const f2 a = f2{q.x, q.y} - f2{x.x, x.y};
+        const f2 b = f2{q.z, q.w} - f2{x.z, x.w};
+        acc = __builtin_elementwise_fma(b, b, __builtin_elementwise_fma(a, a, acc));
+    } else {
+        acc += tile_pair_term<MODEL, HEAD>(q, x);
+    }
+}
+
 template <int MODEL, bool HEAD, int KPT>
 __global__ __launch_bounds__(256) void pool_fwd_tile_kernel(PoolArgs A, TileArgs T) {
     constexpr bool CP = ModelTraits<MODEL>::cplx_pair;
     extern __shared__ __attribute__((aligned(16))) int lds_tile_dyn[];  // the fringe workgroups' position lists
     const int b = (int)blockIdx.x;
     const int n_fringe = T.fringe_tiles * T.fringe_slices;
-    if (b < n_fringe) {  // (workgroup-uniform)
-        pool_fwd_body<MODEL, HEAD, KPT, 4>(A, b % T.fringe_tiles, T.fringe_tiles, b / T.fringe_tiles, T.fringe_slices, lds_tile_dyn);
-        return;
+    if constexpr (MODEL != kTileL2) {  // (kTileL2: no fringe, the whole candidate list is the dense prefix)
+        if (b < n_fringe) {  // (workgroup-uniform)
+            pool_fwd_body<MODEL, HEAD, KPT, 4>(A, b % T.fringe_tiles, T.fringe_tiles, b / T.fringe_tiles, T.fringe_slices, lds_tile_dyn);
+            return;
+        }
     }
     __shared__ __attribute__((aligned(16))) float sq[2][kTileKC / 2][kTilePitch];
     __shared__ __attribute__((aligned(16))) float sx[2][kTileKC / 2][kTilePitch];
@@ -159,7 +180,7 @@ __global__ __launch_bounds__(256) void pool_fwd_tile_kernel(PoolArgs A, TileArgs
                 for (int a = 0; a < 4; ++a)
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
-                        acc[a][c] += tile_pair_term<MODEL, HEAD>(q[a], x[c]);
+                        tile_pair_acc<MODEL, HEAD>(acc[a][c], q[a], x[c]);
             }
         } else {
             // the real-valued term is ~100 VALU operations per group against the round trip of its eight LDS reads, with two
@@ -177,7 +198,7 @@ __global__ __launch_bounds__(256) void pool_fwd_tile_kernel(PoolArgs A, TileArgs
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[a][c] += tile_pair_term<MODEL, HEAD>(q[a], x[c]);
+                    for (int c = 0; c < 4; ++c) tile_pair_acc<MODEL, HEAD>(acc[a][c], q[a], x[c]);
             };
             lds_group(0, qa, xa);
 #pragma unroll 1

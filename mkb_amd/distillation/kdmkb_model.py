@@ -7,8 +7,10 @@ Per step and dataset: one batch, positive forward, filtered negatives, negative 
 kernels (2-D samples: pooled path for the negatives; 3-D distillation samples: general forward).
 
 Two deliberate differences from the reference, both at its edges: the candidate sampler defaults to ``UniformSampling``
-(the reference hard-wires ``FastTopKSampling``; pass ``sampling_method=distillation.FastTopKSampling`` to train as it does --
-a TransE teacher needs the reference's faiss index there and raises ``ImportError``), and classification datasets (ConvE / BCE) are outside the mkb_amd hot path.
+(the reference hard-wires ``FastTopKSampling``; pass ``sampling_method=functools.partial(distillation.FastTopKSampling,
+transe_sampler=distillation.TopKSamplingTransE)`` to train as it does -- ``distillation.FastTopKSampling`` alone raises
+``ImportError`` for a TransE teacher, as the reference does without faiss -- or ``sampling_method=distillation.TopKSamplingTransE``
+for its un-precomputed form), and classification datasets (ConvE / BCE) are outside the mkb_amd hot path.
 """
 import collections
 

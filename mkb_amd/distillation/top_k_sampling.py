@@ -6,17 +6,19 @@ ground truth is not put into the lists, so ``Distillation`` distils each part of
 The reference loops over the triples on the host with three ``argsort``s per triple.  Here the entity sides are one
 ``mkb_topk_masked`` launch per side and batch (the all-entity score block, restricted to the shared entities by a bitmask), the
 relation side one general forward of the ``[b, shared relations, 3]`` block (as ``Evaluation.relation_ranks`` scores it) and one
-``mkb_topk_block``; the ids are mapped with device tables.  The TransE teacher of ``FastTopKSampling`` takes the reference's faiss
-L2 index (``TopKSamplingTransE``), which is not part of mkb_amd."""
+``mkb_topk_block``; the ids are mapped with device tables.  ``TopKSamplingTransE`` is the reference's sampler for a TransE teacher:
+the shared entities / relations nearest in L2 to the teacher's translated queries, with the device's exact squared-L2 k nearest
+rows (``mkb_topk_nearest``) in place of the reference's faiss ``IndexFlatL2``; ``FastTopKSampling(..., transe_sampler=
+TopKSamplingTransE)`` precomputes it for a TransE teacher."""
 import collections
 
 import numpy as np
 import torch
 
 from .. import _hip
-from ..utils.predict_top_k import _launch, candidate_bits, topk_block
+from ..utils.predict_top_k import _launch, candidate_bits, topk_block, topk_nearest
 
-__all__ = ["FastTopKSampling", "TopKSampling"]
+__all__ = ["FastTopKSampling", "TopKSampling", "TopKSamplingTransE"]
 
 
 def _shared(teacher, student):
@@ -165,6 +167,87 @@ class TopKSampling(_Random):
         return tuple(x.contiguous().to(out_dev) for x in outs)
 
 
+class TopKSamplingTransE(_Random):
+    """The reference's sampler for a TransE teacher (top_k_sampling.py:680-875): for every triple of ``sample`` the
+    ``batch_size_entity`` shared entities nearest in L2 to the teacher's translated queries ``t - r`` (heads) and ``h + r``
+    (tails), the ``batch_size_relation`` shared relations nearest to ``t - h`` (``TransE._top_k``), then ``n_random_entities`` /
+    ``n_random_relations`` random shared ones.  ``get(sample, teacher)`` -> the six int64 tensors of ``TopKSampling.get``.
+
+    The reference's faiss ``IndexFlatL2`` is the device's exact squared-L2 k nearest rows (``mkb_topk_nearest``).  As in the
+    reference, the index holds the shared rows of the teacher's tables as they are when the sampler is built, while the queries
+    use the teacher's current tables (``KdmkbModel.learn`` rebuilds its samplers every ``update_distillation_every`` steps).
+
+    One deviation: equal distances go to the lower teacher id (the index holds the shared rows in ascending teacher id).  The
+    reference's index holds them in the teacher dict's order, and faiss leaves the order of equal distances unspecified.  A top k
+    larger than the number of shared entities / relations raises ``ValueError``, as in ``TopKSampling``; so does a teacher that
+    is not a TransE."""
+
+    supervised = False
+    depends_on_teacher = True
+
+    def __init__(self, teacher_entities, teacher_relations, student_entities, student_relations, teacher, batch_size_entity,
+                 batch_size_relation, n_random_entities, n_random_relations, seed=None, device="cpu", **kwargs):
+        if teacher.name != "TransE":
+            raise ValueError(f"TopKSamplingTransE needs a TransE teacher, got {teacher.name}")
+        self._base = TopKSampling(teacher_entities=teacher_entities, teacher_relations=teacher_relations,
+                                  student_entities=student_entities, student_relations=student_relations,
+                                  batch_size_entity=batch_size_entity, batch_size_relation=batch_size_relation,
+                                  n_random_entities=n_random_entities, n_random_relations=n_random_relations, device=device)
+        self._base._check_teacher(teacher)
+        self.mapping_entities, self.mapping_relations = self._base.mapping_entities, self._base.mapping_relations
+        self.batch_size_entity_top_k, self.batch_size_relation_top_k = batch_size_entity, batch_size_relation
+        self.n_random_entities, self.n_random_relations = n_random_entities, n_random_relations
+        self.device = device
+        self._rng = np.random.RandomState(seed)
+        teacher.sync_parameters()
+        with torch.no_grad():
+            dev = teacher.entity_embedding.device
+            shared = {"entity": torch.tensor(sorted(self.mapping_entities), dtype=torch.int64, device=dev),
+                      "relation": torch.tensor(sorted(self.mapping_relations), dtype=torch.int64, device=dev)}
+            tables = {"entity": teacher.entity_embedding, "relation": teacher.relation_embedding}
+            # part -> (the index: the shared rows, ascending teacher id; their teacher ids; positions 0 .. n - 1)
+            self._index = {part: (tables[part].detach()[ids].contiguous(), ids, torch.arange(ids.numel(), device=dev))
+                           for part, ids in shared.items()}
+
+    def side(self, part, sample, teacher):
+        """-> (teacher ids, student ids) [b, k] of one part ("head", "relation" or "tail") for ``sample`` [b, 3] int64 on the
+        teacher's device: the shared rows nearest to the part's translated query.  No random columns, no synchronisation."""
+        index, t_ids, pos = self._index["relation" if part == "relation" else "entity"]
+        k = self.batch_size_relation_top_k if part == "relation" else self.batch_size_entity_top_k
+        q = teacher._top_k(sample)[("head", "relation", "tail").index(part)]
+        near, _ = topk_nearest(q.reshape(sample.shape[0], -1).contiguous(), index, pos, k)
+        t = t_ids[near]
+        tb = self.tables(sample.device)
+        return t, (tb["rel_map"] if part == "relation" else tb["ent_map"])[t]
+
+    def tables(self, device):
+        """``TopKSampling.tables``: the teacher id -> student id maps."""
+        return self._base.tables(device)
+
+    def _check_teacher(self, teacher):
+        self._base._check_teacher(teacher)
+
+    def get(self, sample, teacher, **kwargs):
+        """-> (head, relation, tail distributions of the teacher, then of the student): int64 on ``sample``'s device."""
+        _hip.require_device(teacher.entity_embedding)
+        if teacher.name != "TransE":
+            raise ValueError(f"TopKSamplingTransE needs a TransE teacher, got {teacher.name}")
+        self._base._check_teacher(teacher)
+        out_dev = sample.device
+        dev = teacher.entity_embedding.device
+        with torch.no_grad():
+            s = sample.to(device=dev, dtype=torch.int64).reshape(-1, 3).contiguous()
+            b = s.shape[0]
+            if b:
+                (ht, hs), (rt, rs), (tt, ts) = (self.side(part, s, teacher) for part in ("head", "relation", "tail"))
+                outs = (ht, rt, tt, hs, rs, ts)
+            else:
+                ke, kr = self.batch_size_entity_top_k, self.batch_size_relation_top_k
+                outs = tuple(torch.empty((0, k), dtype=torch.int64, device=dev) for k in (ke, kr, ke, ke, kr, ke))
+            outs = self._random_columns(b, dev, outs)
+        return tuple(x.contiguous().to(out_dev) for x in outs)
+
+
 class FastTopKSampling(_Random):
     """``TopKSampling`` precomputed over the teacher's training triples when it is built (reference top_k_sampling.py:9-264):
     for every distinct (r, t) of ``dataset_teacher``'s triples the teacher's top heads, for every distinct (h, t) its top
@@ -172,22 +255,25 @@ class FastTopKSampling(_Random):
     a sample up (``KeyError`` for a key that was not precomputed, like the reference's dicts) and appends the random columns.
 
     Building it walks ``dataset_teacher`` once as the reference does (its loaders draw their seeds from torch's global generator
-    when their iterators are created), so a seeded run keeps the reference's batch order.  A TransE teacher raises
-    ``ImportError``: the reference hands it to a faiss L2 index, which mkb_amd does not provide."""
+    when their iterators are created), so a seeded run keeps the reference's batch order.  A TransE teacher takes the sampler the
+    reference hands it to, ``TopKSamplingTransE``, when ``transe_sampler=distillation.TopKSamplingTransE`` is passed; without
+    it a TransE teacher raises ``ImportError``, as the reference does without faiss.  Other teachers ignore ``transe_sampler``."""
 
     supervised = False
     depends_on_teacher = True
 
     def __init__(self, teacher_entities, teacher_relations, student_entities, student_relations, batch_size_entity,
                  batch_size_relation, n_random_entities, n_random_relations, dataset_teacher, teacher, device="cpu", seed=None,
-                 chunk=1024, **kwargs):
-        if teacher.name == "TransE":
+                 chunk=1024, transe_sampler=None, **kwargs):
+        transe = teacher.name == "TransE"
+        if transe and transe_sampler is None:
             raise ImportError("FastTopKSampling with a TransE teacher needs the faiss L2 index of the reference's "
-                              "TopKSamplingTransE (No module named 'faiss'); use another teacher or TopKSampling")
-        base = TopKSampling(teacher_entities=teacher_entities, teacher_relations=teacher_relations,
-                            student_entities=student_entities, student_relations=student_relations,
-                            batch_size_entity=batch_size_entity, batch_size_relation=batch_size_relation, n_random_entities=0,
-                            n_random_relations=0, device=device, seed=seed)
+                              "TopKSamplingTransE (No module named 'faiss'); pass transe_sampler=distillation.TopKSamplingTransE "
+                              "for the device's exact L2 index, or use another teacher or TopKSampling")
+        kw = dict(teacher_entities=teacher_entities, teacher_relations=teacher_relations, student_entities=student_entities,
+                  student_relations=student_relations, batch_size_entity=batch_size_entity, batch_size_relation=batch_size_relation,
+                  n_random_entities=0, n_random_relations=0, device=device, seed=seed)
+        base = transe_sampler(teacher=teacher, **kw) if transe else TopKSampling(**kw)
         self.mapping_entities, self.mapping_relations = base.mapping_entities, base.mapping_relations
         self.batch_size_entity_top_k, self.batch_size_relation_top_k = batch_size_entity, batch_size_relation
         self.n_random_entities, self.n_random_relations = n_random_entities, n_random_relations
@@ -206,6 +292,21 @@ class FastTopKSampling(_Random):
         h, r, t = tri[:, 0], tri[:, 1], tri[:, 2]
         teacher.sync_parameters()
         self._keys = {}
+        self._N, self._R = N, R
+        if transe:  # the shared rows nearest to each distinct key's translated query (TopKSamplingTransE.side)
+            with torch.no_grad():
+                zero = torch.zeros_like
+                for part, key, row in (("head", r * N + t, lambda u: (zero(u), u // N, u % N)),
+                                       ("relation", h * N + t, lambda u: (u // N, zero(u), u % N)),
+                                       ("tail", h * R + r, lambda u: (u // R, u % R, zero(u)))):
+                    u = torch.unique(key)
+                    q = torch.stack(row(u), 1).contiguous()
+                    k = batch_size_relation if part == "relation" else batch_size_entity
+                    t_ids, s_ids = (torch.empty((u.numel(), k), dtype=torch.int64, device=dev) for _ in range(2))
+                    for lo in range(0, u.numel(), chunk):
+                        t_ids[lo: lo + chunk], s_ids[lo: lo + chunk] = base.side(part, q[lo: lo + chunk], teacher)
+                    self._keys[part] = (u, t_ids, s_ids)
+            return
         with torch.no_grad():
             tb = base.tables(dev)
             ke, kr = batch_size_entity, batch_size_relation
@@ -233,7 +334,6 @@ class FastTopKSampling(_Random):
                 score = teacher(block.contiguous()).reshape(s.shape[0], n_rel).float().contiguous()
                 topk_block(score, kr, ids=pos[lo: lo + chunk])
             self._keys["relation"] = (u, rel_t[pos], tb["rel_s"][pos])
-        self._N, self._R = N, R
 
     def _rows(self, part, key):
         keys, t, s = self._keys[part]

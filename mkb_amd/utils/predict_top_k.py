@@ -131,3 +131,35 @@ def topk_block(S, k, ids=None, scores=None):
             _hip.check(_hip.lib().mkb_topk_block(_hip.ptr(S), B, N, max(S.stride(0), N), k, _hip.ptr(ids), _hip.ptr(scores),
                                                  _hip.stream_ptr()), "mkb_topk_block")
     return ids, scores
+
+
+def topk_nearest(Q, X, cand, k, ids=None, dists=None, block=None):
+    """-> ``(ids, dists)`` [B, k]: for each row of the fp32 device block ``Q`` [B, D] the k candidates of ``cand`` (int64 row ids
+    of the fp32 device table ``X`` [n, D]) with the smallest squared L2 distance, nearest first; equal distances go to the lower
+    position in ``cand``, NaN first; -1 / +inf past the candidates (``mkb_topk_nearest``).  ``ids`` hold the ``cand`` values.
+    ``block``: a [B, len(cand)] fp32 device tensor that receives the whole distance block (``mkb_topk_nearest_dists``)."""
+    _hip.require_device(Q, X, cand)
+    for name, t in (("Q", Q), ("X", X)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{name} must be a 2-D float32 device tensor with unit column stride")
+    if Q.shape[1] != X.shape[1]:
+        raise ValueError(f"Q and X must have the same number of columns, got {Q.shape[1]} and {X.shape[1]}")
+    cand = _hip.contiguous(cand.reshape(-1), torch.int64)
+    (B, D), n = Q.shape, cand.numel()
+    if ids is None:
+        ids = torch.empty((B, k), dtype=torch.int64, device=Q.device)
+    if dists is None:
+        dists = torch.empty((B, k), dtype=torch.float32, device=Q.device)
+    if B:
+        lib = _hip.lib()
+        need = lib.mkb_topk_nearest_workspace_bytes(B, n, k)
+        ws = _hip.aligned_bytes(need, Q.device) if need > 0 else None
+        args = (_hip.ptr(Q), Q.stride(0) if B > 1 else D, _hip.ptr(X), X.stride(0) if X.shape[0] > 1 else D, _hip.ptr(cand), n, B, D, k,
+                _hip.ptr(ids), _hip.ptr(dists))
+        with _hip.on_device(Q.device):
+            if block is None:
+                _hip.check(lib.mkb_topk_nearest(*args, _hip.ptr(ws), need, _hip.stream_ptr()), "mkb_topk_nearest")
+            else:
+                _hip.check(lib.mkb_topk_nearest_dists(*args, _hip.ptr(block), _hip.ptr(ws), need, _hip.stream_ptr()),
+                           "mkb_topk_nearest_dists")
+    return ids, dists

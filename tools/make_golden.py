@@ -568,6 +568,135 @@ def gen_topk_sampling():
     (OUT / "topk_sampling.json").write_text(json.dumps(js, indent=1))
 
 
+def _faiss_stub():
+    """A stand-in for faiss (absent offline) with the one index the reference uses, ``IndexFlatL2``: ``add`` appends rows,
+    ``search(x, k)`` returns ``(D, I)`` -- exact float64 squared distances, equal ones to the lower insertion position.
+    gen_topk_sampling_transe installs it into ``sys.modules`` for its own run only."""
+    faiss = types.ModuleType("faiss")
+
+    class IndexFlatL2:
+        def __init__(self, d):
+            self.d, self.rows = d, np.zeros((0, d), dtype=np.float32)
+
+        def add(self, x):
+            self.rows = np.concatenate([self.rows, np.asarray(x, dtype=np.float32).reshape(-1, self.d)])
+
+        def search(self, x, k):
+            q = np.asarray(x, dtype=np.float64).reshape(-1, self.d)
+            d = ((q[:, None, :] - self.rows.astype(np.float64)[None, :, :]) ** 2).sum(-1)
+            order = np.argsort(d, axis=1, kind="stable")[:, :k]
+            return np.take_along_axis(d, order, axis=1).astype(np.float32), order.astype(np.int64)
+
+    faiss.IndexFlatL2 = IndexFlatL2
+    return faiss
+
+
+def _l2_gaps(teacher, sample, ents, rels, k_e, k_r):
+    """Smallest relative gap (d_k+1 - d_k) / d_k+1 between the k-th and (k+1)-th float64 squared L2 distance of the translated
+    queries of `sample` (TransE._top_k) to the shared entity rows `ents` / relation rows `rels`: above 1e-4, an fp32 near-tie
+    cannot reorder the device's selection."""
+    with torch.no_grad():
+        qh, qr, qt = (x.reshape(sample.shape[0], -1).double() for x in teacher._top_k(sample))
+    ent, rel = teacher.entity_embedding.detach().double()[ents], teacher.relation_embedding.detach().double()[rels]
+    gaps = []
+    for q, x, k in ((qh, ent, k_e), (qt, ent, k_e), (qr, rel, k_r)):
+        if x.shape[0] > k:
+            d = ((q[:, None, :] - x[None, :, :]) ** 2).sum(-1).sort(dim=1).values
+            gaps.append(((d[:, k] - d[:, k - 1]) / d[:, k]).min().item())
+    return min(gaps)
+
+
+def gen_topk_sampling_transe():
+    """TransE teacher top-k samplers (distillation/top_k_sampling.py:680-875) captured from the live reference with the exact
+    faiss stand-in above: (a) TopKSamplingTransE.get on CountriesS1 batches, the teacher dict in a shuffled insertion order and a
+    student dict that renumbers the labels and drops some (tree position, teacher id and student id all differ), random columns
+    on; (b) FastTopKSampling with a TransE teacher over the training split, looked up for a few batches; (c) KdmkbModel.forward,
+    3 steps, a TransE and a RotatE model teaching each other with the reference's default sampler.  Each case records its
+    smallest relative L2 gap between the k-th and (k+1)-th shared row (and, for the RotatE teacher, the score gap of
+    _topk_gaps)."""
+    sys.modules["faiss"] = _faiss_stub()
+    try:
+        _gen_topk_sampling_transe()
+    finally:
+        del sys.modules["faiss"]
+
+
+def _gen_topk_sampling_transe():
+    from mkb import distillation
+    out, js = {}, {"gaps": {}}
+    ds = datasets.CountriesS1(batch_size=6, seed=42, shuffle=False)
+    rs = np.random.RandomState(5)
+    labels = list(ds.entities)
+    t_ents = {labels[i]: ds.entities[labels[i]] for i in rs.permutation(len(labels))}  # shuffled insertion order
+    kept = [labels[i] for i in rs.permutation(len(labels))[: len(labels) - 40]]  # 40 labels dropped, the rest renumbered
+    s_ents = {lab: j for j, lab in enumerate(kept)}
+    t_rels = dict(ds.relations)
+    s_rels = {lab: j for j, lab in enumerate(reversed(list(ds.relations)))}
+    js["get"] = {"t_ents": list(t_ents.items()), "s_ents": list(s_ents.items()), "t_rels": list(t_rels.items()),
+                 "s_rels": list(s_rels.items())}
+    it = iter(ds)
+    batches = [next(it)["sample"] for _ in range(4)]
+    out["get/samples"] = np.stack([npy(b) for b in batches])
+    torch.manual_seed(21)
+    teacher = models.TransE(hidden_dim=8, entities=ds.entities, relations=ds.relations, gamma=4)
+    out["get/ent"], out["get/rel"] = npy(teacher.entity_embedding), npy(teacher.relation_embedding)
+    sampler = distillation.TopKSamplingTransE(teacher_entities=t_ents, teacher_relations=t_rels, student_entities=s_ents,
+                                              student_relations=s_rels, teacher=teacher, batch_size_entity=5, batch_size_relation=1,
+                                              n_random_entities=3, n_random_relations=1, seed=7)
+    shared_e = sorted(i for lab, i in t_ents.items() if lab in s_ents)
+    shared_r = sorted(i for lab, i in t_rels.items() if lab in s_rels)
+    for j, b in enumerate(batches):
+        got = sampler.get(sample=b, teacher=teacher)
+        for name, x in zip(("head_t", "rel_t", "tail_t", "head_s", "rel_s", "tail_s"), got):
+            out[f"get/{j}/{name}"] = npy(x)
+    js["gaps"]["get"] = min(_l2_gaps(teacher, b, shared_e, shared_r, 5, 1) for b in batches)
+
+    # (b) FastTopKSampling, TransE teacher, teacher and student the same graph
+    d1 = datasets.CountriesS1(batch_size=16, seed=42, shuffle=False)
+    torch.manual_seed(25)
+    teacher = models.TransE(hidden_dim=8, entities=d1.entities, relations=d1.relations, gamma=4)
+    out["fast/ent"], out["fast/rel"] = npy(teacher.entity_embedding), npy(teacher.relation_embedding)
+    fast = distillation.FastTopKSampling(teacher_entities=d1.entities, teacher_relations=d1.relations, student_entities=d1.entities,
+                                         student_relations=d1.relations, batch_size_entity=4, batch_size_relation=1,
+                                         n_random_entities=2, n_random_relations=1, dataset_teacher=d1, teacher=teacher, seed=3)
+    train = torch.tensor(d1.train)
+    js["gaps"]["fast"] = _l2_gaps(teacher, train, sorted(d1.entities.values()), sorted(d1.relations.values()), 4, 1)
+    looked = [train[i: i + 10] for i in (0, 100, 500)]
+    out["fast/samples"] = np.stack([npy(b) for b in looked])
+    for j, b in enumerate(looked):
+        for name, x in zip(("head_t", "rel_t", "tail_t", "head_s", "rel_s", "tail_s"), fast.get(sample=b)):
+            out[f"fast/{j}/{name}"] = npy(x)
+
+    # (c) KdmkbModel with the reference's default sampler: TransE (its faiss sampler) and RotatE (TopKSampling) teach each other
+    from mkb.distillation import kdmkb_model as km
+    d1 = datasets.CountriesS1(batch_size=8, seed=42)
+    d2 = datasets.CountriesS1(batch_size=8, seed=42)
+    torch.manual_seed(61)  # (after the datasets, which seed torch themselves: top-k gaps above 1e-4 for both teachers)
+    m1 = models.TransE(hidden_dim=8, entities=d1.entities, relations=d1.relations, gamma=3)
+    m2 = models.RotatE(hidden_dim=4, entities=d2.entities, relations=d2.relations, gamma=3)
+    out["kd/m1_ent"], out["kd/m1_rel"], out["kd/m2_ent"], out["kd/m2_rel"] = (npy(m1.entity_embedding), npy(m1.relation_embedding),
+                                                                              npy(m2.entity_embedding), npy(m2.relation_embedding))
+    train = torch.tensor(d1.train)
+    ents, rels = sorted(d1.entities.values()), sorted(d1.relations.values())
+    js["gaps"]["kd_transe"] = _l2_gaps(m1, train, ents, rels, 4, 1)
+    js["gaps"]["kd_rotate"] = _topk_gaps(m2, train, ents, rels, 4, 1)
+    mods, dsets = collections.OrderedDict(a=m1, b=m2), collections.OrderedDict(a=d1, b=d2)
+    kd = km.KdmkbModel(models=mods, datasets=dsets, lr={"a": 1e-2, "b": 1e-2}, alpha_kl={"a": 0.3, "b": 0.6},
+                       alpha_adv={"a": 0.5, "b": 0.5}, negative_sampling_size={"a": 4, "b": 4}, batch_size_entity={"a": 4, "b": 4},
+                       batch_size_relation={"a": 1, "b": 1}, n_random_entities={"a": 3, "b": 2}, n_random_relations={"a": 1, "b": 1},
+                       device="cpu", seed=42)
+    steps = []
+    for step in range(3):
+        kd.forward(dsets, mods, {"a": 0.3, "b": 0.6})
+        steps.append({k: kd.metrics[k].w[-1] for k in mods})
+        out[f"kd/m1_ent_step{step}"], out[f"kd/m1_rel_step{step}"] = npy(m1.entity_embedding), npy(m1.relation_embedding)
+    js["kd_step_losses"] = steps
+    out["kd/m1_ent_after"], out["kd/m2_ent_after"] = npy(m1.entity_embedding), npy(m2.entity_embedding)
+    out["kd/m1_rel_after"], out["kd/m2_rel_after"] = npy(m1.relation_embedding), npy(m2.relation_embedding)
+    np.savez_compressed(OUT / "topk_sampling_transe.npz", **out)
+    (OUT / "topk_sampling_transe.json").write_text(json.dumps(js, indent=1))
+
+
 if __name__ == "__main__":
     OUT.mkdir(parents=True, exist_ok=True)
     which = sys.argv[1:] or ["models", "init", "sampler", "weights", "pipeline", "eval", "headline_slice", "distill", "eval_headline"]
