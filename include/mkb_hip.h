@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MKB_ABI_VERSION 7
+#define MKB_ABI_VERSION 8
 
 typedef enum {
     MKB_OK = 0,
@@ -115,7 +115,7 @@ int mkb_adversarial(const float *pos, const float *neg, const float *weight, con
  *   neg [B,K] int64 out; optional outs for the pooled scoring path: pool [2K] int64 (the shared candidate
  *   draw), pos [B,K] int32 (neg[i,j] == pool[pos[i,j]]), cnt [B,2K] uint16 (multiplicity of each pool
  *   position in row i), touched [2K + 2B] int64 (the entity rows a training step on this batch reads: the pool,
- *   then the batch's heads, then its tails -- the id list of mkb_adam_rows_catchup / _step).  status [1] int32 device out: 0 / MKB_ERR_KEY / MKB_ERR_EMPTY (first failing row
+ *   then the batch's heads, then its tails -- the id list of mkb_adam_rows_advance / _step).  status [1] int32 device out: 0 / MKB_ERR_KEY / MKB_ERR_EMPTY (first failing row
  *   in status[1]); checked lazily by the host with mkb_sampler_status.
  */
 typedef struct mkb_sampler mkb_sampler_t;
@@ -191,28 +191,6 @@ int mkb_kl_divergence(const float *student, const float *teacher, int64_t n, int
 int mkb_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, float lr,
                   float beta1, float beta2, float eps, int zero_grad, void *stream);
 
-/* Row-lazy form of the same dense Adam (identical arithmetic, see mkb_amd/csrc/adam.hip): `last` [n_rows] int32
- * (zero-initialised) holds the step each row is current through, `consts` [capacity, 2] float holds the per-step
- * scalars recorded by mkb_adam_rows_step.
- *   mkb_adam_rows_catchup: replay the pending zero-gradient steps of the rows in ids (null = every row, i.e. a
- *     flush) so that they are current through step_upto;
- *   mkb_adam_rows_step: apply step `step` with the real gradient to the rows in ids (duplicates allowed; they must
- *     be current through step-1) and clear their gradient rows.
- */
-/* draw_ahead: null, or a sampler whose NEXT pool draw (the single-workgroup MT19937 kernel every mkb_sampler_generate
- * starts with) runs as one more workgroup of the catch-up launch (ids != null); the next mkb_sampler_generate on that
- * sampler then only filters.  Same stream as the sampler's other calls; the negatives are bit-identical to drawing at
- * generate time, and mkb_sampler_get_state keeps reporting the state before the pool drawn ahead. */
-int mkb_adam_rows_catchup(float *param, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts, int64_t n_rows,
-                          int64_t D, const int64_t *ids, int64_t n_ids, int64_t step_upto, float beta1, float beta2,
-                          float eps, mkb_sampler_t *draw_ahead, void *stream);
-/* mkb_sampler_generate(sampler, sample, B, mode, neg, pool, pos, cnt, touched) and mkb_adam_rows_catchup over the rows
- * that batch touches (its pool, heads and tails) as ONE launch that also draws the sampler's next pool: the whole
- * sampler runs in the shadow of the optimizer's catch-up.  Same outputs, bit for bit, as the two calls (size <= 512). */
-int mkb_adam_rows_catchup_generate(float *param, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                   int64_t n_rows, int64_t D, int64_t step_upto, float beta1, float beta2, float eps,
-                                   mkb_sampler_t *sampler, const int64_t *sample, int64_t B, int mode, int64_t *neg,
-                                   int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched, void *stream);
 typedef struct {
     float *param, *grad, *exp_avg, *exp_avg_sq; /* a small dense tensor (e.g. the relation table), 16-byte aligned */
     int64_t n;                                  /* elements */
@@ -220,28 +198,52 @@ typedef struct {
 } mkb_adam_dense_t;
 /* mkb_adam_step for up to 8 parameter tensors in ONE launch (each with its own step count): what an optimizer over a model's
  * few dense tensors does per step -- small models are bound by launches, not by bytes (Umls TransE-64: 9 launches of ~5 us).
- * draw_ahead: as in mkb_adam_rows_catchup (the sampler's next pool draw as one more workgroup of this launch), or null. */
+ * draw_ahead: null, or a sampler whose next pool draw runs as one more workgroup of this launch (see below). */
 int mkb_adam_step_multi(const mkb_adam_dense_t *tensors_host, int n_tensors, float lr, float beta1, float beta2, float eps,
                         int zero_grad, mkb_sampler_t *draw_ahead, void *stream);
-/* rider: null, or one dense tensor that takes its mkb_adam_step (with zero_grad) inside the same launch. */
+
+/* ---- row-lazy Adam: the same dense Adam, bit for bit, with the steps of untouched rows deferred (mkb_amd/csrc/adam.hip) ----
+ * State of a table param [n_rows, D] besides exp_avg / exp_avg_sq: `last` [n_rows] int32 (zero-initialised; 0 = never
+ * touched) = the step each row is current through; `consts` [capacity > step, 2] float = the per-step scalars
+ * (-lr / (1 - beta1^s), sqrt(1 - beta2^s)), recorded by the launch that applies step s.
+ *
+ * mkb_adam_rows_step: apply step `step` with the real gradient to the rows in ids (duplicates allowed; they must be
+ *   current through step - 1) and clear their gradient rows.  rider: null, or one dense tensor that takes its
+ *   mkb_adam_step (with zero_grad) inside the same launch.
+ * mkb_adam_rows_advance: make the listed rows current through step_upto by replaying their pending steps.
+ *   grad == null, the plain catch-up: every pending step is a zero-gradient step; lr is ignored, a rider is refused.
+ *   grad != null, the advance form: step step_upto itself was deferred (its mkb_adam_rows_step never ran).  The rows of
+ *     that step's batch were made current through step_upto - 1 before its forward pass, so after backward they are
+ *     "current through step_upto - 1, gradient of step_upto in the gradient row": the replay takes a row's gradient row
+ *     (grad [n_rows, D]) for its FIRST pending step (zero for rows that were not touched then: the zero-gradient step, bit
+ *     for bit) and clears it.  lr = learning rate of step_upto (recorded into consts[step_upto] by this launch); rider:
+ *     null, or the small dense tensor that takes ITS step (rider->step) in the same launch.  mkb_adam_rows_step is then
+ *     only needed for the very first step.  Callers must bring a row current BEFORE a backward pass writes its gradient row.
+ *   The rows, in this order:
+ *     global_ids [n_global > 0], world >= 1: GLOBAL entity ids of a row-sharded table (next section; e.g. the candidate
+ *       pool, the same on every rank); entries another rank owns are skipped.  null, 0, 0, 0: the table is not sharded.
+ *     ids [n_ids]: row (shard) indices; duplicates allowed, negative entries and entries >= n_rows are skipped; may be null.
+ *     Both null: every row of the table (a flush: every direct read of the table must be preceded by one).
+ *   draw_ahead: null, or a sampler whose NEXT pool draw (the single-workgroup kernel every mkb_sampler_generate starts
+ *     with) runs as one more workgroup of this launch (ignored on a flush); the next mkb_sampler_generate on that sampler
+ *     then only filters.  Same stream as the sampler's other calls; the negatives are bit-identical to drawing at generate
+ *     time, and mkb_sampler_get_state keeps reporting the state before the pool drawn ahead.
+ * mkb_adam_rows_advance_generate: mkb_sampler_generate(sampler, sample, B, mode, neg, pool, pos, cnt, touched) and
+ *   mkb_adam_rows_advance over the rows that batch reads as ONE launch that also draws the sampler's next pool: the whole
+ *   sampler runs in the shadow of the optimizer's replay.  Same outputs, bit for bit, as the two calls (size <= 512).
+ *   world == 0: the rows are the batch's pool, heads and tails.  world >= 1 (shard of a row-sharded table; the sampler's
+ *   pool holds global ids): the pool entries this rank owns, then the shard indices local_ids [n_local_ids].
+ */
 int mkb_adam_rows_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
                        int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step, float lr, float beta1,
                        float beta2, float eps, const mkb_adam_dense_t *rider, void *stream);
-/* "Advance" form of mkb_adam_rows_catchup / _catchup_generate: the real step of the touched rows is deferred too.  The rows
- * of step t's batch were made current through t-1 before its forward pass, so after backward their state is "current
- * through t-1, gradient of step t in the gradient row" -- and stays that way until the row is next read: the replay takes
- * the row's gradient row for its FIRST pending step (zero for rows that were not touched then, which is the
- * zero-gradient step bit for bit) and clears it.  mkb_adam_rows_step is then only needed for the very first step
- * (`last` = 0 means "never touched").  grad: the table's dense gradient [n_rows, D]; lr: learning rate of step
- * step_upto (recorded into consts[step_upto] by the launch); rider: the small dense tensor that takes ITS step
- * (rider->step) in the same launch, or null.  Callers must bring a row current (catch-up / advance) BEFORE a backward
- * pass writes its gradient row, and route every read of the tables through an advance with ids = null (flush). */
 int mkb_adam_rows_advance(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                          int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr,
-                          float beta1, float beta2, float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead,
-                          void *stream);
+                          int64_t n_rows, int64_t D, const int64_t *global_ids, int64_t n_global, int world, int rank,
+                          const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr, float beta1, float beta2,
+                          float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead, void *stream);
 int mkb_adam_rows_advance_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                   int64_t n_rows, int64_t D, int64_t step_upto, float lr, float beta1, float beta2, float eps,
+                                   int64_t n_rows, int64_t D, int world, int rank, const int64_t *local_ids,
+                                   int64_t n_local_ids, int64_t step_upto, float lr, float beta1, float beta2, float eps,
                                    const mkb_adam_dense_t *rider, mkb_sampler_t *sampler, const int64_t *sample, int64_t B,
                                    int mode, int64_t *neg, int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched,
                                    void *stream);
@@ -284,23 +286,7 @@ int mkb_rows_gather(const float *shard, int64_t n_local, int64_t D, const mkb_ro
 int mkb_rows_scatter_add(float *grad, int64_t n_local, int64_t D, const mkb_row_seg_t *segs, int n_segs, float *dense_dst,
                          const float *dense_src, int64_t dense_n, float *copy_dst, const float *copy_src, int64_t copy_n,
                          uint32_t *occ, int32_t *bad, void *stream);
-/* mkb_adam_rows_advance (grad != null) / mkb_adam_rows_catchup (grad == null) for a shard of such a table: the rows to visit
- * are global_ids [n_global] (entries other ranks own are skipped) followed by local_ids [n_local_ids] (shard indices).
- * Negative entries of any id list of the row-lazy calls are skipped. */
-int mkb_adam_rows_advance_sharded(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                  int64_t n_rows, int64_t D, const int64_t *global_ids, int64_t n_global, int world, int rank,
-                                  const int64_t *local_ids, int64_t n_local_ids, int64_t step_upto, float lr, float beta1,
-                                  float beta2, float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead,
-                                  void *stream);
-
-/* ... and with this rank's mkb_sampler_generate riding the same launch (the pool ids are the sampler's own): the sharded
- * counterpart of mkb_adam_rows_advance_generate / _catchup_generate (grad == null). */
-int mkb_adam_rows_advance_sharded_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last,
-                                           float *consts, int64_t n_rows, int64_t D, int world, int rank,
-                                           const int64_t *local_ids, int64_t n_local_ids, int64_t step_upto, float lr,
-                                           float beta1, float beta2, float eps, const mkb_adam_dense_t *rider,
-                                           mkb_sampler_t *sampler, const int64_t *sample, int64_t B, int mode, int64_t *neg,
-                                           int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched, void *stream);
+/* The owner's row-lazy optimizer visits its shard with mkb_adam_rows_advance / _advance_generate at world >= 1 (above). */
 
 /* ---- the row-sharded step's collectives, issued by the library (no reference counterpart: mkb is single-process) ------------
  * mkb_amd/table_rows.py used to issue the step's six collectives through torch.distributed and to read the all-to-alls' split

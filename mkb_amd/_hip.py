@@ -14,7 +14,7 @@ import os
 
 # MKB_HIP_LIB selects an experimental build of the same ABI (tools/kbench.py); default = the in-tree product library
 _LIB_PATH = pathlib.Path(os.environ.get("MKB_HIP_LIB") or (pathlib.Path(__file__).resolve().parent / "libmkb_hip.so"))
-ABI_VERSION = 7  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a symbol or a signature changes)
+ABI_VERSION = 8  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a symbol or a signature changes)
 
 MODEL_IDS = {"TransE": 0, "RotatE": 1, "ComplEx": 2, "DistMult": 3, "pRotatE": 4}
 MODE_DEFAULT, MODE_HEAD, MODE_TAIL = 0, 1, 2
@@ -37,7 +37,7 @@ class Grads(Structure):  # mkb_grads_t; rows_clear (default 0): see include/mkb_
     _fields_ = [("g_ent", c_void_p), ("g_rel", c_void_p), ("g_modulus", c_void_p), ("rows_clear", c_int32)]
 
 
-class AdamDense(Structure):  # mkb_adam_dense_t: a small dense tensor stepped inside mkb_adam_rows_step's launch
+class AdamDense(Structure):  # mkb_adam_dense_t: a small dense tensor stepped inside another launch
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
                 ("n", c_int64), ("step", c_int64)]
 
@@ -53,6 +53,14 @@ class HipLibraryError(RuntimeError):
 
 _lib = None
 
+# The argument groups the row-lazy Adam calls (mkb_adam_rows_*) share, spelled once so that they cannot drift apart:
+#   param, grad, exp_avg, exp_avg_sq, last, consts, n_rows, D
+_ROWS_TABLE = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]
+#   step, lr, beta1, beta2, eps, rider
+_ROWS_STEP = [c_int64, c_float, c_float, c_float, c_float, POINTER(AdamDense)]
+#   sampler, sample, B, mode, neg, pool, pos, cnt, touched, stream (the arguments of mkb_sampler_generate)
+_SAMPLER_TAIL = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+
 _SIGNATURES = {
     "mkb_abi_version": (c_int, []),
     "mkb_last_error": (c_char_p, []),
@@ -64,8 +72,7 @@ _SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "mkb_sampler_create": (c_int, [POINTER(c_void_p), c_int64, c_int64, c_int64, c_uint32, c_void_p, c_int64, c_void_p,
                                    c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "mkb_sampler_generate": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p]),
+    "mkb_sampler_generate": (c_int, _SAMPLER_TAIL),
     "mkb_sampler_status": (c_int, [c_void_p, c_void_p]),
     "mkb_sampler_set_rng": (c_int, [c_void_p, c_int, ctypes.c_uint64, ctypes.c_uint64]),
     "mkb_sampler_get_rng": (c_int, [c_void_p, POINTER(c_int), POINTER(ctypes.c_uint64), POINTER(ctypes.c_uint64)]),
@@ -89,20 +96,10 @@ _SIGNATURES = {
     "mkb_adam_step_multi": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
     "mkb_profile_enable": (c_int, [c_int, c_int]),
     "mkb_profile_read": (c_int, [c_int, POINTER(c_int64), POINTER(ctypes.c_double)]),
-    "mkb_adam_rows_catchup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
-                                      c_int64, c_float, c_float, c_float, c_void_p, c_void_p]),
-    "mkb_adam_rows_catchup_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
-                                               c_float, c_float, c_float, c_void_p, c_void_p, c_int64, c_int, c_void_p,
-                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "mkb_adam_rows_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
-                                   c_int64, c_int64, c_float, c_float, c_float, c_float, POINTER(AdamDense), c_void_p]),
-    "mkb_adam_rows_advance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
-                                      c_int64, c_int64, c_float, c_float, c_float, c_float, POINTER(AdamDense), c_void_p,
-                                      c_void_p]),
-    "mkb_adam_rows_advance_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                               c_int64, c_float, c_float, c_float, c_float, POINTER(AdamDense), c_void_p,
-                                               c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                               c_void_p]),
+    "mkb_adam_rows_step": (c_int, _ROWS_TABLE + [c_void_p, c_int64] + _ROWS_STEP + [c_void_p]),
+    "mkb_adam_rows_advance": (c_int, _ROWS_TABLE + [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64] + _ROWS_STEP
+                              + [c_void_p, c_void_p]),
+    "mkb_adam_rows_advance_generate": (c_int, _ROWS_TABLE + [c_int, c_int, c_void_p, c_int64] + _ROWS_STEP + _SAMPLER_TAIL),
     "mkb_rows_route": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
     "mkb_rows_gather": (c_int, [c_void_p, c_int64, c_int64, POINTER(RowSeg), c_int, c_void_p, c_int64, c_void_p, c_void_p,
@@ -123,13 +120,6 @@ _SIGNATURES = {
     "mkb_rows_comm_take": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mkb_rows_comm_exchange": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mkb_rows_comm_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
-    "mkb_adam_rows_advance_sharded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                              c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_float, c_float,
-                                              c_float, c_float, POINTER(AdamDense), c_void_p, c_void_p]),
-    "mkb_adam_rows_advance_sharded_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                                       c_int, c_int, c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_float,
-                                                       POINTER(AdamDense), c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
-                                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "mkb_check_ids": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "mkb_kl_divergence": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mkb_debug_sclk_mhz": (c_int, [c_void_p, c_void_p]),

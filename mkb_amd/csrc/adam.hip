@@ -63,26 +63,45 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, float 
                      neg_step, sqrt_bc2, eps, zero_grad);
 }
 
+// The scalars of step `step`: (-lr / (1 - beta1^step), sqrt(1 - beta2^step)), in double, rounded once.  Every launch of this
+// file takes them from here, and the replays read back what a launch recorded: dense and row-lazy Adam step with the same bits.
+struct StepScalars {
+    float neg_step, sqrt_bc2;
+};
+static StepScalars step_scalars(float lr, float beta1, float beta2, int64_t step) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    return {(float)(-((double)lr / bc1)), (float)sqrt(bc2)};
+}
+
+// One dense tensor of a launch, checked: its step's scalars and the workgroups that stream it (`threads` lanes x float4,
+// grid-stride over 1 .. max_blocks of them).
+struct DenseWork {
+    StepScalars s;
+    int64_t blocks;
+};
+static int dense_work(DenseWork &w, const mkb_adam_dense_t &T, float lr, float beta1, float beta2, int threads, int64_t max_blocks) {
+    MKB_REQUIRE(T.param && T.grad && T.exp_avg && T.exp_avg_sq, "dense tensor: null pointer");
+    MKB_REQUIRE(T.n >= 0 && T.step >= 1, "dense tensor: bad n / step");
+    MKB_REQUIRE((((uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.exp_avg | (uintptr_t)T.exp_avg_sq) & 15) == 0,
+                "buffers must be 16-byte aligned");
+    w.s = step_scalars(lr, beta1, beta2, T.step);
+    w.blocks = std::min(std::max(((T.n >> 2) + threads - 1) / threads, (int64_t)1), max_blocks);
+    return MKB_OK;
+}
+
 }  // namespace mkb
 
 extern "C" int mkb_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step,
                              float lr, float beta1, float beta2, float eps, int zero_grad, void *stream) {
-    MKB_REQUIRE(param && grad && exp_avg && exp_avg_sq, "null pointer");
-    MKB_REQUIRE(n >= 0 && step >= 1, "bad n / step");
-    MKB_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
-                "buffers must be 16-byte aligned");
+    mkb::DenseWork w;
+    const mkb_adam_dense_t T{param, grad, exp_avg, exp_avg_sq, n, step};
+    if (int rc = mkb::dense_work(w, T, lr, beta1, beta2, 256, 2048)) return rc;
     if (n == 0) return MKB_OK;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float neg_step = (float)(-((double)lr / bc1));
-    const float sqrt_bc2 = (float)sqrt(bc2);
     const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-    int64_t blocks = ((n >> 2) + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
     mkb::ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
-    hipLaunchKernelGGL(mkb::adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                       exp_avg_sq, n, w1, beta2, w2, neg_step, sqrt_bc2, eps, zero_grad);
+    hipLaunchKernelGGL(mkb::adam_kernel, dim3((unsigned)w.blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                       exp_avg_sq, n, w1, beta2, w2, w.s.neg_step, w.s.sqrt_bc2, eps, zero_grad);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
@@ -123,18 +142,12 @@ extern "C" int mkb_adam_step_multi(const mkb_adam_dense_t *tensors, int n_tensor
     int blocks = 0;
     for (int t = 0; t < n_tensors; ++t) {
         const mkb_adam_dense_t &T = tensors[t];
-        MKB_REQUIRE(T.param && T.grad && T.exp_avg && T.exp_avg_sq && T.n >= 0 && T.step >= 1, "bad tensor %d", t);
-        MKB_REQUIRE((((uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.exp_avg | (uintptr_t)T.exp_avg_sq) & 15) == 0,
-                    "buffers must be 16-byte aligned");
+        mkb::DenseWork w;
+        if (int rc = mkb::dense_work(w, T, lr, beta1, beta2, 256, 2048)) return rc;
         A.p[t] = T.param; A.g[t] = T.grad; A.m[t] = T.exp_avg; A.v[t] = T.exp_avg_sq; A.n[t] = T.n;
-        const double bc1 = 1.0 - pow((double)beta1, (double)T.step), bc2 = 1.0 - pow((double)beta2, (double)T.step);
-        A.neg_step[t] = (float)(-((double)lr / bc1));  // (the same scalars, computed the same way, as mkb_adam_step: same bits)
-        A.sqrt_bc2[t] = (float)sqrt(bc2);
-        int64_t nb = ((T.n >> 2) + 255) / 256;
-        if (nb < 1) nb = 1;
-        if (nb > 2048) nb = 2048;
+        A.neg_step[t] = w.s.neg_step; A.sqrt_bc2[t] = w.s.sqrt_bc2;
         A.first_block[t] = blocks;
-        blocks += (int)nb;
+        blocks += (int)w.blocks;
     }
     A.first_block[n_tensors] = blocks;
     size_t lds = 0;
@@ -159,7 +172,7 @@ extern "C" int mkb_adam_step_multi(const mkb_adam_dense_t *tensors, int n_tensor
 // Rows that were never touched have m = v = 0, for which a dense step is the identity: they are skipped.
 // consts[s] = (-lr / (1 - beta1^s), sqrt(1 - beta2^s)) is recorded by the step kernel for later replays.
 //
-// "Advance" form (mkb_adam_rows_advance*): the REAL step is deferred as well.  A row the batch of step t touched was made
+// "Advance" form (mkb_adam_rows_advance* with grad != null): the REAL step is deferred as well.  A row the batch of step t touched was made
 // current through t-1 before the forward pass, so after backward it is the one row state "current through t-1, gradient of
 // step t in its gradient row".  Nothing forces that step to be applied before the row is next read: the replay of a row
 // simply takes the row's gradient for its FIRST pending step (a zero row for rows that were not touched then: adam_one at
@@ -196,7 +209,7 @@ struct AdamRowArgs {
     int32_t n_rows_listed;  // catch-up kernel: rows to visit (n_ids row blocks of rows_per_block rows each)
     int32_t rows_per_block; // power of two <= 16: kCatchThreads / rows_per_block lanes x (float4 | float2) cover one row
     int32_t vec4;           // rows are read as float4 per lane (D % 4 == 0, 16-byte aligned arrays), else float2 / scalar
-    // row-sharded table (mkb_adam_rows_advance_sharded): the first own_n listed rows are GLOBAL entity ids of a table whose
+    // row-sharded table (mkb_adam_rows_advance* at world >= 1): the first own_n listed rows are GLOBAL entity ids of a table whose
     // row e lives on rank e % own_world at index e / own_world; entries another rank owns are skipped.  `ids` follows them.
     const int64_t *own_ids;
     int32_t own_n, own_world, own_rank;
@@ -206,22 +219,11 @@ struct AdamRowArgs {
     int64_t n_table;
 };
 
-__device__ __forceinline__ void adam_zero_grad_step(float &p, float &m, float &v, float w1, float b2, float neg_step,
-                                                    float sqrt_bc2, float eps) {
-#pragma clang fp contract(off)
-    m = fmaf(w1, 0.f - m, m);  // the dense kernel's fmaf(w1, g - m, m) at g = 0
-    v = v * b2;                // ... + (w2 * 0) * 0 adds +0
-    // v_sqrt_f32 / v_rcp_f32 (1 ulp each) instead of the correctly rounded sqrtf and '/' (~30 instructions per
-    // element): the update is lr-sized, so the deviation from torch's result is ~1e-7 of 5e-5 per step.  The dense
-    // and the row-lazy kernels share this code, which is what keeps them bit-identical to each other.
-    const float denom = __builtin_amdgcn_sqrtf(v) * __builtin_amdgcn_rcpf(sqrt_bc2) + eps;
-    p = p + (neg_step * m) * __builtin_amdgcn_rcpf(denom);
-}
-
 // workgroup size of the catch-up / advance kernel (the sampler's filter and draw blocks that ride it are sized by it too)
 // 512 lanes: one 2000-float row per workgroup, two workgroups per CU (107 VGPRs): their phases -- ownership exchange, loads, replay,
 // stores -- interleave.  Round 4, same box, 1024 -> 512 lanes: headline step 0.2273 -> 0.2242 ms, WN18RR 0.1302 -> 0.1262, YAGO3-10
-// 0.1933 -> 0.1862 (256 lanes: better still for YAGO3-10's long replays, worse at the headline; tools/_kb_catch.sh)
+// 0.1933 -> 0.1862 (256 lanes: better still for YAGO3-10's long replays, worse at the headline; variants built with
+// -DMKB_CATCH_THREADS / -DMKB_REPLAY_UNROLL by tools/kbench.py)
 #ifndef MKB_CATCH_THREADS
 #define MKB_CATCH_THREADS 512
 #endif
@@ -232,7 +234,7 @@ constexpr int kCatchThreads = MKB_CATCH_THREADS;
 constexpr int kReplayUnroll = MKB_REPLAY_UNROLL;  // pending zero-gradient steps replayed side by side
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// adam_one / adam_zero_grad_step on two elements at once (v_pk_* where the scalar code has v_*: the same IEEE operations,
+// adam_one (with a gradient, and at g = 0) on two elements at once (v_pk_* where the scalar code has v_*: the same IEEE operations,
 // element-wise, so the results are the scalar ones bit for bit); inv_bc2 = v_rcp_f32(sqrt_bc2), taken once per step
 __device__ __forceinline__ void adam_pair(f2 &p, f2 g, f2 &m, f2 &v, float w1, float b2, float w2, float neg_step, float inv_bc2,
                                           float eps) {
@@ -324,13 +326,7 @@ __device__ __forceinline__ void replay_finish(const AdamRowArgs &A, int64_t row,
     }
     int s = from + 1;
     bool clear = false;
-#if defined(MKB_ADAM_MEASURE) && (MKB_ADAM_MEASURE & 1)  // (measurement builds, WRONG results: rows move, nothing is replayed)
-    s = to + 1;
-    if (false)
-#else
-    if (A.g)
-#endif
-    {  // the row's first pending step is the one its gradient row belongs to
+    if (A.g) {  // the row's first pending step is the one its gradient row belongs to
         const float2 cs = replay_consts(A, s);
         const float inv = __builtin_amdgcn_rcpf(cs.y);
 #pragma unroll
@@ -408,11 +404,7 @@ __device__ __forceinline__ void replay_row_block(const AdamRowArgs &A, int64_t r
     // 32-bit lane offset instead of four 64-bit vector addresses (registers: the point is a fourth workgroup per CU)
     row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)row);
     valid = __builtin_amdgcn_readfirstlane((int)valid) != 0;
-#if defined(MKB_ADAM_MEASURE) && (MKB_ADAM_MEASURE & 2)  // (measurement builds, WRONG results: no ownership exchange)
-    if (lane == 0 && valid) *s_old = A.step - 2;
-#else
     if (lane == 0 && valid) *s_old = atomicExch(&A.last[row], A.step);  // first claimant of a duplicated id does the work
-#endif
     const int k0 = lane * EPL, D = (int)A.D;  // (row lengths fit 31 bits: fill_args)
     RowChunk<EPL> c;
     if (valid && k0 < D) replay_load<EPL>(A, row, k0, c);
@@ -563,15 +555,10 @@ static int fill_args(AdamRowArgs &A, float *param, float *grad, float *m, float 
     A.p = param; A.g = grad; A.m = m; A.v = v; A.last = last; A.consts = (float2 *)consts; A.ids = ids; A.D = D;
     A.step = (int32_t)step;
     A.w1 = (float)(1.0 - (double)beta1); A.b2 = beta2; A.w2 = (float)(1.0 - (double)beta2); A.eps = eps;
-    const double s = step > 0 ? (double)step : 1.0;
-    A.neg_step = (float)(-((double)lr / (1.0 - pow((double)beta1, s))));
-    A.sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, s));
+    const StepScalars s = step_scalars(lr, beta1, beta2, step > 0 ? step : 1);
+    A.neg_step = s.neg_step; A.sqrt_bc2 = s.sqrt_bc2;
     return MKB_OK;
 }
-
-}  // namespace mkb
-
-namespace mkb {
 
 // Sweep.  Exact dense Adam moves every parameter every step, so the replay's arithmetic is N x D element-steps per step no
 // matter when it happens (measured: ~85 ns per wave and pending step at 4 elements per lane: WN18RR +16 us, FB15k-237
@@ -617,19 +604,16 @@ static void set_row_blocks(AdamRowArgs &A, int64_t rows, int64_t n_table = 0) {
     A.n_ids = (int32_t)((rows + A.rows_per_block - 1) / A.rows_per_block);
 }
 
-// dense rider of an advance launch -> number of extra workgroups (0 = none)
+// dense rider of a row-lazy launch (its extra workgroups have `threads` lanes) -> their number (0 = none)
 static int attach_rider(AdamRowArgs &A, const mkb_adam_dense_t *rider, float lr, float beta1, float beta2, int threads,
                         int64_t *extra) {
     *extra = 0;
     if (!rider || rider->n <= 0) return MKB_OK;
-    MKB_REQUIRE(rider->param && rider->grad && rider->exp_avg && rider->exp_avg_sq && rider->step >= 1, "bad dense rider");
-    MKB_REQUIRE((((uintptr_t)rider->param | (uintptr_t)rider->grad | (uintptr_t)rider->exp_avg | (uintptr_t)rider->exp_avg_sq) & 15) == 0,
-                "buffers must be 16-byte aligned");
+    DenseWork w;
+    if (int rc = dense_work(w, *rider, lr, beta1, beta2, threads, 1024)) return rc;
     A.dp = rider->param; A.dg = rider->grad; A.dm = rider->exp_avg; A.dv = rider->exp_avg_sq; A.dn = rider->n;
-    A.d_neg_step = (float)(-((double)lr / (1.0 - pow((double)beta1, (double)rider->step))));
-    A.d_sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, (double)rider->step));
-    int64_t e = ((rider->n >> 2) + threads - 1) / threads;
-    *extra = e < 1 ? 1 : (e > 1024 ? 1024 : e);
+    A.d_neg_step = w.s.neg_step; A.d_sqrt_bc2 = w.s.sqrt_bc2;
+    *extra = w.blocks;
     return MKB_OK;
 }
 
@@ -638,83 +622,18 @@ static bool short_gaps(const AdamRowArgs &A) {
     return A.n_table > 0 && A.n_batch_rows > 0 && (int64_t)A.n_table < (int64_t)12 * A.n_batch_rows;
 }
 
-static int rows_advance(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                        int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr, float beta1,
-                        float beta2, float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead, void *stream,
-                        const int64_t *own_ids = nullptr, int64_t own_n = 0, int own_world = 0, int own_rank = 0) {
-    AdamRowArgs A{};
-    if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, ids, D, step_upto, lr, beta1, beta2, eps)) return rc;
-    int64_t n = ids ? n_ids : n_rows;
-    if (own_ids) {
-        MKB_REQUIRE(own_n > 0 && own_n <= INT32_MAX && own_world >= 1 && own_rank >= 0 && own_rank < own_world, "bad ownership");
-        MKB_REQUIRE(ids || n_ids == 0, "null local id list");
-        A.own_ids = own_ids; A.own_n = (int32_t)own_n; A.own_world = own_world; A.own_rank = own_rank;
-        n = own_n + n_ids;
-    }
-    if (n <= 0 || step_upto <= 0) n = 0;  // nothing can be pending before the first step
-    MKB_REQUIRE(n <= INT32_MAX, "too many rows");
-    set_row_blocks(A, n, (ids || own_ids) ? n_rows : 0);  // (a flush walks the whole table anyway)
-    n = A.n_ids;
-    int64_t extra = 0;
-    if (!ids && !own_ids && A.n_rows_listed > 0) {  // the whole table
-        if (int rc = attach_rider(A, rider, lr, beta1, beta2, 256, &extra)) return rc;
-        ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
-        hipLaunchKernelGGL(adam_rows_flush_kernel, dim3((unsigned)(A.n_rows_listed + extra)), dim3(256), 0, (hipStream_t)stream, A);
-        MKB_LAUNCH_CHECK();
-        return MKB_OK;
-    }
-    if (int rc = attach_rider(A, rider, lr, beta1, beta2, kCatchThreads, &extra)) return rc;
-    if (n + extra == 0) return MKB_OK;
-    size_t lds = 0;
-    if (draw_ahead && (ids || own_ids) && sampler_draw_ahead(draw_ahead, &A.draw, &lds)) A.first_row_block = 1;
-    ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
-    if (short_gaps(A))
-        hipLaunchKernelGGL(adam_rows_catchup_kernel<1>, dim3((unsigned)(n + extra + A.first_row_block)), dim3(kCatchThreads), lds,
-                           (hipStream_t)stream, A);
-    else
-        hipLaunchKernelGGL(adam_rows_catchup_kernel<kReplayUnroll>, dim3((unsigned)(n + extra + A.first_row_block)), dim3(kCatchThreads),
-                           lds, (hipStream_t)stream, A);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-static int rows_advance_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                 int64_t n_rows, int64_t D, int64_t step_upto, float lr, float beta1, float beta2, float eps,
-                                 const mkb_adam_dense_t *rider, mkb_sampler_t *sampler, const int64_t *sample, int64_t B,
-                                 int mode, int64_t *neg, int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched,
-                                 void *stream, int own_world = 0, int own_rank = 0, const int64_t *local_ids = nullptr,
-                                 int64_t n_local_ids = 0) {
-    hipStream_t st = (hipStream_t)stream;
-    AdamRowArgs A{};
-    if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, nullptr, D, step_upto > 0 ? step_upto : 0, lr,
-                           beta1, beta2, eps)) return rc;
-    size_t lds = 0;
-    ProfScope ps(MKB_PROF_SAMPLER, st);
-    if (int rc = sampler_ride(sampler, sample, B, mode, neg, pool, pos, cnt, touched, &A.filt, &A.draw, &A.seg_pool, &lds, st, kCatchThreads))
-        return rc;
-    A.first_row_block = 1;
-    A.n_filter = (int32_t)((B + A.filt.rows_per_wg - 1) / A.filt.rows_per_wg);  // one wave per row, <= kCatchThreads / 64 rows per workgroup
-    A.seg_sample = sample; A.seg_P = A.filt.P; A.seg_B = (int32_t)B;
-    if (own_world > 0) {
-        // shard of a row-sharded table: the rows to visit are the pool ids this rank owns (the sampler's pool buffer holds
-        // GLOBAL ids) followed by the shard indices other ranks asked for; the batch's own heads / tails live elsewhere
-        MKB_REQUIRE(own_rank >= 0 && own_rank < own_world && (local_ids || n_local_ids == 0) && n_local_ids >= 0, "bad ownership");
-        A.own_ids = A.seg_pool; A.own_n = A.filt.P; A.own_world = own_world; A.own_rank = own_rank;
-        A.ids = local_ids; A.seg_pool = nullptr;
-        set_row_blocks(A, step_upto > 0 ? (int64_t)A.own_n + n_local_ids : 0, n_rows);
-    } else
-    set_row_blocks(A, step_upto > 0 ? (int64_t)A.seg_P + 2 * B : 0, n_rows);  // nothing is pending before the first step
-    const int64_t rows = A.n_ids;
-    int64_t extra = 0;
-    if (int rc = attach_rider(A, rider, lr, beta1, beta2, kCatchThreads, &extra)) return rc;
-    static LdsOptIn big_lds[2];  // 16 rows per filter workgroup need ~73 KB of dynamic LDS: opt in once per device (160 KB per CU)
-    const dim3 grid((unsigned)(1 + A.n_filter + rows + extra));
+// need_big_lds: the sampler's filter blocks ride (16 rows per filter workgroup need ~73 KB of dynamic LDS: opt in once per
+// device and instance; 160 KB per CU)
+static int launch_catchup(const AdamRowArgs &A, int64_t grid, size_t lds, hipStream_t st, bool need_big_lds) {
+    static LdsOptIn big_lds[2];
     if (short_gaps(A)) {
-        if (int rc = big_lds[0].ensure(reinterpret_cast<const void *>(&adam_rows_catchup_kernel<1>), 96 * 1024)) return rc;
-        hipLaunchKernelGGL(adam_rows_catchup_kernel<1>, grid, dim3(kCatchThreads), lds, st, A);
+        if (need_big_lds)
+            if (int rc = big_lds[0].ensure(reinterpret_cast<const void *>(&adam_rows_catchup_kernel<1>), 96 * 1024)) return rc;
+        hipLaunchKernelGGL(adam_rows_catchup_kernel<1>, dim3((unsigned)grid), dim3(kCatchThreads), lds, st, A);
     } else {
-        if (int rc = big_lds[1].ensure(reinterpret_cast<const void *>(&adam_rows_catchup_kernel<kReplayUnroll>), 96 * 1024)) return rc;
-        hipLaunchKernelGGL(adam_rows_catchup_kernel<kReplayUnroll>, grid, dim3(kCatchThreads), lds, st, A);
+        if (need_big_lds)
+            if (int rc = big_lds[1].ensure(reinterpret_cast<const void *>(&adam_rows_catchup_kernel<kReplayUnroll>), 96 * 1024)) return rc;
+        hipLaunchKernelGGL(adam_rows_catchup_kernel<kReplayUnroll>, dim3((unsigned)grid), dim3(kCatchThreads), lds, st, A);
     }
     MKB_LAUNCH_CHECK();
     return MKB_OK;
@@ -722,73 +641,77 @@ static int rows_advance_generate(float *param, float *grad, float *exp_avg, floa
 
 }  // namespace mkb
 
-extern "C" int mkb_adam_rows_catchup(float *param, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                     int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step_upto,
-                                     float beta1, float beta2, float eps, mkb_sampler_t *draw_ahead, void *stream) {
-    return mkb::rows_advance(param, nullptr, exp_avg, exp_avg_sq, last, consts, n_rows, D, ids, n_ids, step_upto, 0.f, beta1,
-                             beta2, eps, nullptr, draw_ahead, stream);
-}
-
-// mkb_sampler_generate and mkb_adam_rows_catchup(ids = the batch's pool | heads | tails) as ONE launch, plus the draw of
-// the next pool: block 0 draws, the next ceil(B / 16) blocks filter this batch's rows, the rest replay the pending steps.
-extern "C" int mkb_adam_rows_catchup_generate(float *param, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                              int64_t n_rows, int64_t D, int64_t step_upto, float beta1, float beta2, float eps,
-                                              mkb_sampler_t *sampler, const int64_t *sample, int64_t B, int mode, int64_t *neg,
-                                              int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched, void *stream) {
-    return mkb::rows_advance_generate(param, nullptr, exp_avg, exp_avg_sq, last, consts, n_rows, D, step_upto, 0.f, beta1, beta2, eps,
-                                      nullptr, sampler, sample, B, mode, neg, pool, pos, cnt, touched, stream);
-}
-
-// Advance form of the two calls above (see the top of the row-lazy section): `grad` = the table's dense gradient, whose
-// rows the replay consumes (first pending step of each row) and clears; `lr` = learning rate of step `step_upto` (the
-// step whose own launch was skipped); rider = the small dense tensor of that step, or null.
 extern "C" int mkb_adam_rows_advance(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                     int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr,
-                                     float beta1, float beta2, float eps, const mkb_adam_dense_t *rider,
-                                     mkb_sampler_t *draw_ahead, void *stream) {
-    MKB_REQUIRE(grad, "null gradient (use mkb_adam_rows_catchup)");
-    return mkb::rows_advance(param, grad, exp_avg, exp_avg_sq, last, consts, n_rows, D, ids, n_ids, step_upto, lr, beta1, beta2,
-                             eps, rider, draw_ahead, stream);
-}
-
-// Row-sharded table: the rows to visit are given as GLOBAL entity ids (the candidate pool, the same on every rank: entries
-// another rank owns are skipped) followed by shard indices (the rows other ranks asked this owner for).  grad == null: the
-// plain catch-up (no deferred real step).
-extern "C" int mkb_adam_rows_advance_sharded(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last,
-                                             float *consts, int64_t n_rows, int64_t D, const int64_t *global_ids,
-                                             int64_t n_global, int world, int rank, const int64_t *local_ids,
-                                             int64_t n_local_ids, int64_t step_upto, float lr, float beta1, float beta2,
-                                             float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead, void *stream) {
-    MKB_REQUIRE(global_ids && n_global > 0, "null global id list (use mkb_adam_rows_advance)");
+                                     int64_t n_rows, int64_t D, const int64_t *global_ids, int64_t n_global, int world, int rank,
+                                     const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr, float beta1, float beta2,
+                                     float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead, void *stream) {
+    using namespace mkb;
     MKB_REQUIRE(grad || !rider, "a dense rider needs the advance form (grad != null)");
-    return mkb::rows_advance(param, grad, exp_avg, exp_avg_sq, last, consts, n_rows, D, local_ids, n_local_ids, step_upto,
-                             grad ? lr : 0.f, beta1, beta2, eps, rider, draw_ahead, stream, global_ids, n_global, world, rank);
+    AdamRowArgs A{};
+    if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, ids, D, step_upto, grad ? lr : 0.f, beta1, beta2, eps))
+        return rc;
+    int64_t n = ids ? n_ids : n_rows;
+    if (global_ids) {
+        MKB_REQUIRE(n_global > 0 && n_global <= INT32_MAX && world >= 1 && rank >= 0 && rank < world, "bad ownership");
+        MKB_REQUIRE(ids || n_ids == 0, "null local id list");
+        A.own_ids = global_ids; A.own_n = (int32_t)n_global; A.own_world = world; A.own_rank = rank;
+        n = n_global + n_ids;
+    } else
+        MKB_REQUIRE(n_global == 0 && world == 0, "null global id list");
+    if (n <= 0 || step_upto <= 0) n = 0;  // nothing can be pending before the first step
+    MKB_REQUIRE(n <= INT32_MAX, "too many rows");
+    const bool listed = ids || global_ids;
+    set_row_blocks(A, n, listed ? n_rows : 0);  // (a flush walks the whole table anyway)
+    int64_t extra = 0;
+    if (!listed && A.n_rows_listed > 0) {  // the whole table
+        if (int rc = attach_rider(A, rider, lr, beta1, beta2, 256, &extra)) return rc;
+        ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
+        hipLaunchKernelGGL(adam_rows_flush_kernel, dim3((unsigned)(A.n_rows_listed + extra)), dim3(256), 0, (hipStream_t)stream, A);
+        MKB_LAUNCH_CHECK();
+        return MKB_OK;
+    }
+    if (int rc = attach_rider(A, rider, lr, beta1, beta2, kCatchThreads, &extra)) return rc;
+    if (A.n_ids + extra == 0) return MKB_OK;
+    size_t lds = 0;
+    if (draw_ahead && listed && sampler_draw_ahead(draw_ahead, &A.draw, &lds)) A.first_row_block = 1;
+    ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
+    return launch_catchup(A, A.n_ids + extra + A.first_row_block, lds, (hipStream_t)stream, false);
 }
 
 extern "C" int mkb_adam_rows_advance_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last,
-                                              float *consts, int64_t n_rows, int64_t D, int64_t step_upto, float lr, float beta1,
-                                              float beta2, float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *sampler,
-                                              const int64_t *sample, int64_t B, int mode, int64_t *neg, int64_t *pool,
-                                              int32_t *pos, uint16_t *cnt, int64_t *touched, void *stream) {
-    MKB_REQUIRE(grad, "null gradient (use mkb_adam_rows_catchup_generate)");
-    return mkb::rows_advance_generate(param, grad, exp_avg, exp_avg_sq, last, consts, n_rows, D, step_upto, lr, beta1, beta2, eps, rider,
-                                      sampler, sample, B, mode, neg, pool, pos, cnt, touched, stream);
-}
-
-// mkb_adam_rows_advance_sharded with this rank's mkb_sampler_generate (filter of its rows + the next pool's draw) in the same
-// launch: global_ids are the sampler's own pool.  grad == null: plain catch-up.
-extern "C" int mkb_adam_rows_advance_sharded_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last,
-                                                      float *consts, int64_t n_rows, int64_t D, int world, int rank,
-                                                      const int64_t *local_ids, int64_t n_local_ids, int64_t step_upto, float lr,
-                                                      float beta1, float beta2, float eps, const mkb_adam_dense_t *rider,
-                                                      mkb_sampler_t *sampler, const int64_t *sample, int64_t B, int mode,
-                                                      int64_t *neg, int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched,
-                                                      void *stream) {
-    MKB_REQUIRE(world >= 1, "bad world");
+                                              float *consts, int64_t n_rows, int64_t D, int world, int rank,
+                                              const int64_t *local_ids, int64_t n_local_ids, int64_t step_upto, float lr,
+                                              float beta1, float beta2, float eps, const mkb_adam_dense_t *rider,
+                                              mkb_sampler_t *sampler, const int64_t *sample, int64_t B, int mode, int64_t *neg,
+                                              int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched, void *stream) {
+    using namespace mkb;
+    hipStream_t st = (hipStream_t)stream;
     MKB_REQUIRE(grad || !rider, "a dense rider needs the advance form (grad != null)");
-    return mkb::rows_advance_generate(param, grad, exp_avg, exp_avg_sq, last, consts, n_rows, D, step_upto, grad ? lr : 0.f, beta1, beta2,
-                                      eps, rider, sampler, sample, B, mode, neg, pool, pos, cnt, touched, stream, world, rank,
-                                      local_ids, n_local_ids);
+    MKB_REQUIRE(world >= 0 && n_local_ids >= 0 && (world > 0 ? rank >= 0 && rank < world && (local_ids || n_local_ids == 0)
+                                                             : n_local_ids == 0),
+                "bad ownership");
+    AdamRowArgs A{};
+    if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, nullptr, D, step_upto > 0 ? step_upto : 0,
+                           grad ? lr : 0.f, beta1, beta2, eps)) return rc;
+    size_t lds = 0;
+    ProfScope ps(MKB_PROF_SAMPLER, st);
+    if (int rc = sampler_ride(sampler, sample, B, mode, neg, pool, pos, cnt, touched, &A.filt, &A.draw, &A.seg_pool, &lds, st, kCatchThreads))
+        return rc;
+    A.first_row_block = 1;
+    A.n_filter = (int32_t)((B + A.filt.rows_per_wg - 1) / A.filt.rows_per_wg);  // one wave per row, <= kCatchThreads / 64 rows per workgroup
+    A.seg_sample = sample; A.seg_P = A.filt.P; A.seg_B = (int32_t)B;
+    int64_t n = (int64_t)A.seg_P + 2 * B;  // the batch's pool | heads | tails
+    if (world > 0) {
+        // shard of a row-sharded table: the rows to visit are the pool ids this rank owns (the sampler's pool buffer holds
+        // GLOBAL ids) followed by the shard indices other ranks asked for; the batch's own heads / tails live elsewhere
+        A.own_ids = A.seg_pool; A.own_n = A.filt.P; A.own_world = world; A.own_rank = rank;
+        A.ids = local_ids; A.seg_pool = nullptr;
+        n = (int64_t)A.own_n + n_local_ids;
+    }
+    set_row_blocks(A, step_upto > 0 ? n : 0, n_rows);  // nothing is pending before the first step
+    int64_t extra = 0;
+    if (int rc = attach_rider(A, rider, lr, beta1, beta2, kCatchThreads, &extra)) return rc;
+    return launch_catchup(A, 1 + A.n_filter + A.n_ids + extra, lds, st, true);
 }
 
 extern "C" int mkb_adam_rows_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
@@ -800,16 +723,7 @@ extern "C" int mkb_adam_rows_step(float *param, float *grad, float *exp_avg, flo
     A.n_ids = (int32_t)n_ids;
     A.n_table = n_rows;  // (ids past the table are skipped, not stepped out of bounds)
     int64_t extra = 0;
-    if (rider && rider->n > 0) {
-        MKB_REQUIRE(rider->param && rider->grad && rider->exp_avg && rider->exp_avg_sq && rider->step >= 1, "bad dense rider");
-        MKB_REQUIRE((((uintptr_t)rider->param | (uintptr_t)rider->grad | (uintptr_t)rider->exp_avg | (uintptr_t)rider->exp_avg_sq) & 15) == 0,
-                    "buffers must be 16-byte aligned");
-        A.dp = rider->param; A.dg = rider->grad; A.dm = rider->exp_avg; A.dv = rider->exp_avg_sq; A.dn = rider->n;
-        A.d_neg_step = (float)(-((double)lr / (1.0 - pow((double)beta1, (double)rider->step))));
-        A.d_sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, (double)rider->step));
-        extra = ((rider->n >> 2) + 255) / 256;
-        extra = extra < 1 ? 1 : (extra > 1024 ? 1024 : extra);
-    }
+    if (int rc = mkb::attach_rider(A, rider, lr, beta1, beta2, 256, &extra)) return rc;
     mkb::ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
     hipLaunchKernelGGL(mkb::adam_rows_step_kernel, dim3((unsigned)(n_ids + extra)), dim3(256), 0, (hipStream_t)stream, A);
     MKB_LAUNCH_CHECK();

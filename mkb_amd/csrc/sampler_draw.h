@@ -1,7 +1,7 @@
 // The pool draw of the negative sampler (numpy legacy MT19937 + masked rejection + the per-batch helper tables) as a
 // device function of ONE workgroup of NT lanes, so that it can run as its own kernel (mkb_sampler_generate) or ride as
-// block 0 of another launch (mkb_adam_rows_step's draw_ahead: the next step's pool is drawn in the shadow of the
-// optimizer kernel, one launch and ~13 us of serial latency fewer per training step).
+// a block of another launch (draw_ahead of mkb_adam_rows_advance / mkb_adam_step_multi: the next step's pool is drawn in the
+// shadow of the optimizer kernel, one launch and ~13 us of serial latency fewer per training step).
 #pragma once
 #include "common.h"
 

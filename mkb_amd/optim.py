@@ -8,7 +8,7 @@ reference -- rows with a zero gradient still decay ``exp_avg`` / ``exp_avg_sq`` 
 momentum.
 
 ``Adam(..., lazy_rows=True)`` keeps those semantics bit for bit but defers the zero-gradient steps of the rows a
-step does not touch (``mkb_adam_rows_catchup`` / ``mkb_adam_rows_step``, see mkb_amd/csrc/adam.hip): the fused
+step does not touch (``mkb_adam_rows_advance`` / ``mkb_adam_rows_step``, see mkb_amd/csrc/adam.hip): the fused
 training step tells the optimizer which entity rows it reads (candidate pool + heads + tails); those rows are
 brought up to date before the forward pass and take the real step afterwards; everything else is replayed when
 it is next needed or at ``flush()`` (``compose.Pipeline`` / ``evaluation`` / ``model(...)`` outside the fused
@@ -83,6 +83,23 @@ class Adam:
     def _lr_of(self, st, step):
         return st.get("lrs", {}).get(step, self.lr)
 
+    def _advance(self, p, st, upto, rows, sampler_tail=None, draw_ahead=None):
+        """One ``mkb_adam_rows_advance`` launch (``mkb_adam_rows_advance_generate`` when ``sampler_tail``, that call's sampler
+        arguments, is given) that makes ``rows`` -- the call's row-listing arguments -- of ``p`` current through ``upto``.  With a
+        deferred step pending (``st["defer"]``) it is the advance form: it carries the gradient, that step's learning rate and
+        the dense rider of the step; otherwise it is the plain catch-up."""
+        c, defer, lib = self._consts(st, max(upto, 1)), st.get("defer"), _hip.lib()
+        with _hip.on_device(p.device):
+            table = (_hip.ptr(p.data), _hip.ptr(st["g"]) if defer else None, _hip.ptr(st["m"]), _hip.ptr(st["v"]),
+                     _hip.ptr(st["last"]), _hip.ptr(c), p.shape[0], p.shape[1])
+            step = (upto, self._lr_of(st, upto) if defer else 0.0, self.betas[0], self.betas[1], self.eps,
+                    self._take_dense() if defer else None)
+            if sampler_tail is None:
+                _hip.check(lib.mkb_adam_rows_advance(*table, *rows, *step, draw_ahead, _hip.stream_ptr()), "mkb_adam_rows_advance")
+            else:
+                _hip.check(lib.mkb_adam_rows_advance_generate(*table, *rows, *step, *sampler_tail, _hip.stream_ptr()),
+                           "mkb_adam_rows_advance_generate")
+
     def catch_up(self, p, ids, upto=None):
         """Make the rows ``ids`` of ``p`` current through step ``upto`` (default: every step taken so far)."""
         st = self._state(p)
@@ -91,20 +108,12 @@ class Adam:
             return
         ids = _hip.contiguous(ids, torch.int64)
         st["caught_up"] = (ids, upto)
-        lib, c = _hip.lib(), self._consts(st, upto)
-        with _hip.on_device(p.device):
-            if st.get("defer"):
-                _hip.check(lib.mkb_adam_rows_advance(_hip.ptr(p.data), _hip.ptr(st["g"]), _hip.ptr(st["m"]), _hip.ptr(st["v"]),
-                                                     _hip.ptr(st["last"]), _hip.ptr(c), p.shape[0], p.shape[1], _hip.ptr(ids),
-                                                     ids.numel(), upto, self._lr_of(st, upto), self.betas[0], self.betas[1],
-                                                     self.eps, self._take_dense(), self._sampler_handle(p.device),
-                                                     _hip.stream_ptr()), "mkb_adam_rows_advance")
-            else:
-                _hip.check(lib.mkb_adam_rows_catchup(_hip.ptr(p.data), _hip.ptr(st["m"]), _hip.ptr(st["v"]),
-                                                     _hip.ptr(st["last"]), _hip.ptr(c), p.shape[0], p.shape[1], _hip.ptr(ids),
-                                                     ids.numel(), upto, self.betas[0], self.betas[1], self.eps,
-                                                     self._sampler_handle(p.device), _hip.stream_ptr()),
-                           "mkb_adam_rows_catchup")
+        self._advance(p, st, upto, (None, 0, 0, 0, _hip.ptr(ids), ids.numel()), draw_ahead=self._sampler_handle(p.device))
+
+    @staticmethod
+    def _shard_rows(world, rank, local_ids):
+        n_loc = 0 if local_ids is None else local_ids.numel()
+        return world, rank, _hip.ptr(local_ids) if n_loc else None, n_loc
 
     def catch_up_sharded(self, p, global_ids, world, rank, local_ids):
         """``catch_up`` for a ROW SHARD of a table (``mkb_amd.table_rows``): the rows to make current are the entries of
@@ -115,83 +124,43 @@ class Adam:
         if upto <= 0:
             return
         st["caught_up"] = (None, upto)
-        lib, c = _hip.lib(), self._consts(st, upto)
-        defer = bool(st.get("defer"))
-        n_loc = 0 if local_ids is None else local_ids.numel()
-        with _hip.on_device(p.device):
-            _hip.check(lib.mkb_adam_rows_advance_sharded(
-                _hip.ptr(p.data), _hip.ptr(st["g"]) if defer else None, _hip.ptr(st["m"]), _hip.ptr(st["v"]), _hip.ptr(st["last"]),
-                _hip.ptr(c), p.shape[0], p.shape[1], _hip.ptr(global_ids), global_ids.numel(), world, rank,
-                _hip.ptr(local_ids) if n_loc else None, n_loc, upto, self._lr_of(st, upto), self.betas[0], self.betas[1],
-                self.eps, self._take_dense() if defer else None, self._sampler_handle(p.device), _hip.stream_ptr()),
-                "mkb_adam_rows_advance_sharded")
+        self._advance(p, st, upto, (_hip.ptr(global_ids), global_ids.numel(), *self._shard_rows(world, rank, local_ids)),
+                      draw_ahead=self._sampler_handle(p.device))
 
     def catch_up_sharded_generate(self, p, world, rank, local_ids, sampler_handle, sample, B, mode_id, neg, pool, pos, cnt, touched):
         """``catch_up_sharded(p, the sampler's pool, world, rank, local_ids)`` fused with the sampler's filter of this rank's rows
-        and the draw of the next pool: one launch (``mkb_adam_rows_advance_sharded_generate``)."""
+        and the draw of the next pool: one launch (``mkb_adam_rows_advance_generate`` at ``world >= 1``)."""
         st = self._state(p)
-        upto = st["n"]
-        st["caught_up"] = (None, upto)
-        lib, c = _hip.lib(), self._consts(st, max(upto, 1))
-        defer = bool(st.get("defer"))
-        n_loc = 0 if local_ids is None else local_ids.numel()
-        with _hip.on_device(p.device):
-            _hip.check(lib.mkb_adam_rows_advance_sharded_generate(
-                _hip.ptr(p.data), _hip.ptr(st["g"]) if defer else None, _hip.ptr(st["m"]), _hip.ptr(st["v"]), _hip.ptr(st["last"]),
-                _hip.ptr(c), p.shape[0], p.shape[1], world, rank, _hip.ptr(local_ids) if n_loc else None, n_loc, upto,
-                self._lr_of(st, upto), self.betas[0], self.betas[1], self.eps, self._take_dense() if defer else None,
-                sampler_handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg), _hip.ptr(pool), _hip.ptr(pos), _hip.ptr(cnt),
-                _hip.ptr(touched), _hip.stream_ptr()), "mkb_adam_rows_advance_sharded_generate")
+        st["caught_up"] = (None, st["n"])
+        self._advance(p, st, st["n"], self._shard_rows(world, rank, local_ids),
+                      (sampler_handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg), _hip.ptr(pool), _hip.ptr(pos), _hip.ptr(cnt),
+                       _hip.ptr(touched)))
 
     def catch_up_generate(self, p, sampler_handle, sample, B, mode_id, neg, pool, pos, cnt, touched):
         """``catch_up(p, rows of this batch)`` fused with the sampler's filter + next-pool draw (one launch; see
         ``sampling.NegativeSampling.generate_with_catch_up``)."""
         st = self._state(p)
-        upto = st["n"]
-        lib, c = _hip.lib(), self._consts(st, max(upto, 1))
-        tail = (sampler_handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg), _hip.ptr(pool), _hip.ptr(pos), _hip.ptr(cnt),
-                _hip.ptr(touched), _hip.stream_ptr())
-        with _hip.on_device(p.device):
-            if st.get("defer"):
-                _hip.check(lib.mkb_adam_rows_advance_generate(
-                    _hip.ptr(p.data), _hip.ptr(st["g"]), _hip.ptr(st["m"]), _hip.ptr(st["v"]), _hip.ptr(st["last"]), _hip.ptr(c),
-                    p.shape[0], p.shape[1], upto, self._lr_of(st, upto), self.betas[0], self.betas[1], self.eps,
-                    self._take_dense(), *tail), "mkb_adam_rows_advance_generate")
-            else:
-                _hip.check(lib.mkb_adam_rows_catchup_generate(
-                    _hip.ptr(p.data), _hip.ptr(st["m"]), _hip.ptr(st["v"]), _hip.ptr(st["last"]), _hip.ptr(c), p.shape[0],
-                    p.shape[1], upto, self.betas[0], self.betas[1], self.eps, *tail), "mkb_adam_rows_catchup_generate")
-        st["caught_up"] = (touched, upto)
+        self._advance(p, st, st["n"], (0, 0, None, 0),
+                      (sampler_handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg), _hip.ptr(pool), _hip.ptr(pos), _hip.ptr(cnt),
+                       _hip.ptr(touched)))
+        st["caught_up"] = (touched, st["n"])
 
     def flush(self, p=None):
         """Replay everything that is pending: afterwards the tables equal what dense Adam would hold."""
-        lib = _hip.lib()
         for q in ([p] if p is not None else self.params):
             if _links.owner(q) is not self:
                 continue
             st = self._state(q)
             if st["n"] <= 0 or st.get("flushed") == st["n"]:
                 continue
-            c = self._consts(st, st["n"])
-            with _hip.on_device(q.device):
-                if st.get("defer"):
-                    _hip.check(lib.mkb_adam_rows_advance(_hip.ptr(q.data), _hip.ptr(st["g"]), _hip.ptr(st["m"]),
-                                                         _hip.ptr(st["v"]), _hip.ptr(st["last"]), _hip.ptr(c), q.shape[0],
-                                                         q.shape[1], None, 0, st["n"], self._lr_of(st, st["n"]), self.betas[0],
-                                                         self.betas[1], self.eps, self._take_dense(), None, _hip.stream_ptr()),
-                               "mkb_adam_rows_advance")
-                else:
-                    _hip.check(lib.mkb_adam_rows_catchup(_hip.ptr(q.data), _hip.ptr(st["m"]), _hip.ptr(st["v"]),
-                                                         _hip.ptr(st["last"]), _hip.ptr(c), q.shape[0], q.shape[1], None, 0,
-                                                         st["n"], self.betas[0], self.betas[1], self.eps, None,
-                                                         _hip.stream_ptr()), "mkb_adam_rows_catchup")
+            self._advance(q, st, st["n"], (None, 0, 0, 0, None, 0))  # no row list: the whole table
             st["flushed"] = st["n"]
         pend, self._pending_dense = self._pending_dense, None
         if pend is not None:  # no launch above carried it (its table was already flushed): step it on its own
             q, d, lr, _ = pend
             with _hip.on_device(q.device):
-                _hip.check(lib.mkb_adam_step(d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n, d.step, lr, self.betas[0],
-                                             self.betas[1], self.eps, 1, _hip.stream_ptr()), "mkb_adam_step")
+                _hip.check(_hip.lib().mkb_adam_step(d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n, d.step, lr, self.betas[0],
+                                                    self.betas[1], self.eps, 1, _hip.stream_ptr()), "mkb_adam_step")
 
     def stop_deferring(self):
         """Apply whatever ``defer_step`` left pending and switch it off for good (callers whose gradient rows are not

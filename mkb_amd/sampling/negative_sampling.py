@@ -144,6 +144,14 @@ class NegativeSampling:
         if self.rng == "rocrand":
             _hip.check(_hip.lib().mkb_sampler_set_rng(handle, 1, int(self.seed) & 0xFFFFFFFFFFFFFFFF, 0), "mkb_sampler_set_rng")
 
+    def _outputs(self, B, dev):
+        """Fresh outputs of one generate call: neg [B, K], pool [2K], pos [B, K], cnt [B, 2K] and touched [2K + 2B] (pool | heads
+        | tails: the rows a row-lazy Adam catches up)."""
+        K = self.size
+        return (torch.empty((B, K), dtype=torch.int64, device=dev), torch.empty(2 * K, dtype=torch.int64, device=dev),
+                torch.empty((B, K), dtype=torch.int32, device=dev), torch.empty((B, 2 * K), dtype=torch.uint16, device=dev),
+                torch.empty(2 * K + 2 * B, dtype=torch.int64, device=dev))
+
     def generate(self, sample, mode):
         """-> LongTensor [B, size] on ``sample``'s device (reference: CPU tensor; ``.to(device)`` is then free)."""
         if mode not in ("head-batch", "tail-batch"):
@@ -154,14 +162,10 @@ class NegativeSampling:
         sample = _hip.contiguous(sample, torch.int64)
         dev = sample.device
         self._ensure_handle(dev)
-        B, K = sample.shape[0], self.size
+        B = sample.shape[0]
         if B == 0:
             self._empty_batch()
-        neg = torch.empty((B, K), dtype=torch.int64, device=dev)
-        pool = torch.empty(2 * K, dtype=torch.int64, device=dev)
-        pos = torch.empty((B, K), dtype=torch.int32, device=dev)
-        cnt = torch.empty((B, 2 * K), dtype=torch.uint16, device=dev)
-        touched = torch.empty(2 * K + 2 * B, dtype=torch.int64, device=dev)  # pool | heads | tails (row-lazy Adam)
+        neg, pool, pos, cnt, touched = self._outputs(B, dev)
         mode_id = _hip.mode_id(mode)
         with _hip.on_device(dev):
             _hip.check(_hip.lib().mkb_sampler_generate(self._handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg),
@@ -170,53 +174,43 @@ class NegativeSampling:
         if origin != dev:
             self.check()
             return neg.to(origin)
-        neg._mkb_pool = PoolInfo(pool, pos, cnt, K, mode_id, sample)
+        neg._mkb_pool = PoolInfo(pool, pos, cnt, self.size, mode_id, sample)
         neg._mkb_pool.touched = touched
         return neg
 
-    def generate_with_catch_up(self, sample, mode, optimizer, param):
-        """``generate(sample, mode)`` and ``optimizer.catch_up(param, rows this batch touches)`` as ONE launch that also
-        draws the next pool (``mkb_adam_rows_catchup_generate``): the sampler costs no launch of its own.  ``optimizer``:
-        a ``mkb_amd.optim.Adam(lazy_rows=True)`` holding ``param`` (the entity table) row-lazily.  Same negatives, pool
-        and multiplicities, bit for bit, as ``generate``."""
+    def _generate_riding(self, sample, mode, optimizer, param, shard=None):
+        """``generate`` inside ``optimizer``'s catch-up launch for ``param``; ``shard``: None, or (world, rank, local_ids) when
+        ``param`` is a row shard."""
         if mode not in ("head-batch", "tail-batch"):
             raise ValueError("mode must be 'head-batch' or 'tail-batch'")
         sample = _hip.contiguous(sample, torch.int64)
         _hip.require_device(param, sample)
         dev = sample.device
         self._ensure_handle(dev)
-        B, K = sample.shape[0], self.size
-        neg = torch.empty((B, K), dtype=torch.int64, device=dev)
-        pool = torch.empty(2 * K, dtype=torch.int64, device=dev)
-        pos = torch.empty((B, K), dtype=torch.int32, device=dev)
-        cnt = torch.empty((B, 2 * K), dtype=torch.uint16, device=dev)
-        touched = torch.empty(2 * K + 2 * B, dtype=torch.int64, device=dev)
+        B = sample.shape[0]
+        neg, pool, pos, cnt, touched = self._outputs(B, dev)
         mode_id = _hip.mode_id(mode)
-        optimizer.catch_up_generate(param, self._handle, sample, B, mode_id, neg, pool, pos, cnt, touched)
-        neg._mkb_pool = PoolInfo(pool, pos, cnt, K, mode_id, sample)
-        neg._mkb_pool.touched = touched
+        if shard is None:
+            optimizer.catch_up_generate(param, self._handle, sample, B, mode_id, neg, pool, pos, cnt, touched)
+        else:
+            optimizer.catch_up_sharded_generate(param, *shard, self._handle, sample, B, mode_id, neg, pool, pos, cnt, touched)
+        neg._mkb_pool = PoolInfo(pool, pos, cnt, self.size, mode_id, sample)
+        if shard is None:  # (a shard's list holds global ids: its caller lists the shard's rows itself)
+            neg._mkb_pool.touched = touched
         return neg
+
+    def generate_with_catch_up(self, sample, mode, optimizer, param):
+        """``generate(sample, mode)`` and ``optimizer.catch_up(param, rows this batch touches)`` as ONE launch that also
+        draws the next pool (``mkb_adam_rows_advance_generate``): the sampler costs no launch of its own.  ``optimizer``:
+        a ``mkb_amd.optim.Adam(lazy_rows=True)`` holding ``param`` (the entity table) row-lazily.  Same negatives, pool
+        and multiplicities, bit for bit, as ``generate``."""
+        return self._generate_riding(sample, mode, optimizer, param)
 
     def generate_with_sharded_catch_up(self, sample, mode, optimizer, param, world, rank, local_ids):
         """``generate(sample, mode)`` for this rank's rows of a global batch and ``optimizer.catch_up_sharded(param, pool, world,
         rank, local_ids)`` for a ROW SHARD of the entity table (``mkb_amd.table_rows``) as one launch that also draws the next
         pool.  Same negatives, pool and multiplicities, bit for bit, as ``generate``."""
-        if mode not in ("head-batch", "tail-batch"):
-            raise ValueError("mode must be 'head-batch' or 'tail-batch'")
-        sample = _hip.contiguous(sample, torch.int64)
-        _hip.require_device(param, sample)
-        dev = sample.device
-        self._ensure_handle(dev)
-        B, K = sample.shape[0], self.size
-        neg = torch.empty((B, K), dtype=torch.int64, device=dev)
-        pool = torch.empty(2 * K, dtype=torch.int64, device=dev)
-        pos = torch.empty((B, K), dtype=torch.int32, device=dev)
-        cnt = torch.empty((B, 2 * K), dtype=torch.uint16, device=dev)
-        touched = torch.empty(2 * K + 2 * B, dtype=torch.int64, device=dev)  # (global ids: unused by the sharded caller)
-        mode_id = _hip.mode_id(mode)
-        optimizer.catch_up_sharded_generate(param, world, rank, local_ids, self._handle, sample, B, mode_id, neg, pool, pos, cnt, touched)
-        neg._mkb_pool = PoolInfo(pool, pos, cnt, K, mode_id, sample)
-        return neg
+        return self._generate_riding(sample, mode, optimizer, param, (world, rank, local_ids))
 
     def check(self):
         """Raise what the reference would have raised for the batches generated so far (synchronises)."""

@@ -11,7 +11,7 @@
        however many of the batch's triples hold it) and groups them by owner; the per-owner counts are
        exchanged and read back on a side stream, the id lists follow -- so the all-to-alls of step t have host-known split
        sizes without the host ever waiting on the compute stream;
-    1. the owners bring the rows about to be read up to date (``mkb_adam_rows_advance_sharded``) and read them
+    1. the owners bring the rows about to be read up to date (``mkb_adam_rows_advance`` at ``world >= 1``) and read them
        (``mkb_rows_gather``: pool rows they hold -- zero rows otherwise -- straight into the compact table, requested rows
        into the all-to-all's send buffer; the same launch sums the batch's weights and clears the compact gradient);
     2. ONE all-reduce completes the pool block everywhere (disjoint supports: the sum IS the gather; the weight sum rides in
@@ -646,7 +646,7 @@ class TableRowShardedStep:
 
     def sampled(self, sample, weight, sampler, mode, next_sample=None):
         """``step(sample, weight, sampler.generate(sample, mode), mode, next_sample)`` with the sampler folded into the shard's
-        optimizer launch when the shard steps row-lazily (``mkb_adam_rows_advance_sharded_generate``: filter of this rank's rows
+        optimizer launch when the shard steps row-lazily (``mkb_adam_rows_advance_generate`` at ``world >= 1``: filter of this rank's rows
         + draw of the next pool + catch-up of the rows about to be read, one launch); identical negatives.  They stay
         available as ``self.negative_sample``."""
         opt = _links.owner(self.table.data)

@@ -582,7 +582,7 @@ def test_row_sharded_table_training_equals_single_device(name, hidden, world, si
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "tests" / "tr_worker.py"), name, str(hidden), "16", size]
     # "big": FB15k-237 -- shards of > 4096 rows, so each shard steps row-lazily with the real step deferred
-    # (mkb_adam_rows_advance_sharded), against the single-process run with the same optimizer settings
+    # (mkb_adam_rows_advance at world >= 1), against the single-process run with the same optimizer settings
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ))
     assert out.returncode == 0 and "TR_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 

@@ -85,7 +85,7 @@ def test_gather_and_scatter_add_equal_the_torch_restatement(D):
 
 @pytest.mark.parametrize("defer", [True, False])
 def test_sharded_catch_up_is_the_plain_catch_up_on_the_materialised_list(defer):
-    """mkb_adam_rows_advance_sharded(global ids filtered by ownership | shard indices) == mkb_adam_rows_advance / _catchup on
+    """mkb_adam_rows_advance(global ids filtered by ownership | shard indices) == the same call without global ids on
     the list [e // world for owned e] + shard indices: the same rows, the same replay -> identical bits."""
     from mkb_amd import _links, optim
 

@@ -140,7 +140,7 @@ def test_empty_batch_behaves_like_the_reference():
 
 
 def test_pool_drawn_ahead_inside_the_optimizer_launch_is_bit_identical():
-    """mkb_adam_rows_catchup(draw_ahead=sampler): the next pool is drawn by one more workgroup of the optimizer's
+    """mkb_adam_rows_advance(draw_ahead=sampler): the next pool is drawn by one more workgroup of the optimizer's
     catch-up launch instead of the stand-alone kernel.  Negatives, pools and the reported generator state must
     equal those of a sampler that draws at generate() time, step after step; set_state discards a pool drawn ahead."""
     from mkb_amd import datasets, optim, sampling
@@ -176,7 +176,7 @@ def test_pool_drawn_ahead_inside_the_optimizer_launch_is_bit_identical():
 
 @pytest.mark.parametrize("size", [24, 512])
 def test_sampler_riding_the_catch_up_launch_is_bit_identical(size):
-    """mkb_adam_rows_catchup_generate: draw-ahead + this batch's filter + the row catch-up in one launch.  Every output
+    """mkb_adam_rows_advance_generate: draw-ahead + this batch's filter + the row catch-up in one launch.  Every output
     of generate (negatives, pool, position map, multiplicities, touched rows) and the optimizer's tables must equal the
     separate calls', step after step, including the first step (nothing pending, pool not drawn ahead yet)."""
     from mkb_amd import datasets, optim, sampling
