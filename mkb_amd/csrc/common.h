@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/mkb_hip.h"
 
@@ -61,6 +62,21 @@ inline int validate_tables(const mkb_tables_t *tb) {
 }
 
 inline bool mode_is_head(int mode) { return mode == MKB_MODE_HEAD; }
+
+// f(std::integral_constant<int, MODEL>{}, std::bool_constant<HEAD>{}) for a run-time model id and side: the one place that
+// turns them into template arguments (`[&](auto m, auto h) { return run<m(), h()>(...); }`)
+template <class F>
+int dispatch_model_side(int model, bool head, F &&f) {
+    auto side = [&](auto m) { return head ? f(m, std::true_type{}) : f(m, std::false_type{}); };
+    switch (model) {
+        case MKB_TRANSE: return side(std::integral_constant<int, MKB_TRANSE>{});
+        case MKB_ROTATE: return side(std::integral_constant<int, MKB_ROTATE>{});
+        case MKB_COMPLEX: return side(std::integral_constant<int, MKB_COMPLEX>{});
+        case MKB_DISTMULT: return side(std::integral_constant<int, MKB_DISTMULT>{});
+        case MKB_PROTATE: return side(std::integral_constant<int, MKB_PROTATE>{});
+    }
+    return set_error(MKB_ERR_INVALID, "unknown model");
+}
 
 // Brackets a kernel launch with hipEvents on the launch stream when profiling of `kind` is enabled
 // (mkb_profile_enable).  Usage:  { ProfScope ps(MKB_PROF_ADAM, st); hipLaunchKernelGGL(...); }

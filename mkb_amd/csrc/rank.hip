@@ -598,20 +598,6 @@ extern "C" int64_t mkb_rank_workspace_bytes(const mkb_tables_t *tb, int64_t B) {
            (int64_t)(tb->n_entity + 3) * 8;
 }
 
-// run_rank<MODEL, HEAD> for the tables' model and the mode's side
-template <class Finish>
-static int run_all(const mkb_tables_t *tb, const int64_t *sample, int64_t B, bool head, float *Q, float *S, int64_t *ids, hipStream_t st,
-                   const Finish &fin) {
-    switch (tb->model) {
-        case MKB_TRANSE: return head ? run_rank<MKB_TRANSE, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_TRANSE, false>(tb, sample, B, Q, S, ids, st, fin);
-        case MKB_ROTATE: return head ? run_rank<MKB_ROTATE, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_ROTATE, false>(tb, sample, B, Q, S, ids, st, fin);
-        case MKB_COMPLEX: return head ? run_rank<MKB_COMPLEX, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_COMPLEX, false>(tb, sample, B, Q, S, ids, st, fin);
-        case MKB_DISTMULT: return head ? run_rank<MKB_DISTMULT, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_DISTMULT, false>(tb, sample, B, Q, S, ids, st, fin);
-        case MKB_PROTATE: return head ? run_rank<MKB_PROTATE, true>(tb, sample, B, Q, S, ids, st, fin) : run_rank<MKB_PROTATE, false>(tb, sample, B, Q, S, ids, st, fin);
-    }
-    return set_error(MKB_ERR_INVALID, "unknown model");
-}
-
 // workspace carve-up shared by mkb_rank and mkb_topk: Q [B, De], S [B, N (+3)], the id list [N + 3]
 struct RankWs {
     float *Q, *S;
@@ -646,7 +632,7 @@ static int rank_impl(const mkb_tables_t *tb, const int64_t *sample, int64_t B, i
             hipLaunchKernelGGL(export_scores_kernel, dim3((unsigned)std::min<int64_t>((tb->n_entity + 255) / 256, 64), (unsigned)B), dim3(256), 0, st,
                                S, scores, tb->n_entity, ld, f0, f1);
     };
-    return run_all(tb, sample, B, head, w.Q, S, w.ids, st, finish);
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return run_rank<m(), h()>(tb, sample, B, w.Q, S, w.ids, st, finish); });
 }
 
 extern "C" int mkb_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys,
@@ -694,7 +680,7 @@ static int topk_impl(const mkb_tables_t *tb, const int64_t *sample, int64_t B, i
             hipLaunchKernelGGL(topk_kernel<kTopkPlain>, grid, dim3(kTopkThreads), 0, st, A);
         }
     };
-    return run_all(tb, sample, B, head, w.Q, w.S, w.ids, st, finish);
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish); });
 }
 
 extern "C" int mkb_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const int64_t *true_keys, int64_t n_true,

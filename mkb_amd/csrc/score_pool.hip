@@ -1,10 +1,11 @@
 // Pooled scoring path: host driver, row kernels and the C-ABI entry points (mkb_pool_step / mkb_pool_score_fwd /
 // mkb_pool_score_bwd).  The three tile kernels live in score_pool_kernels.h and are instantiated per model in
 // score_pool_<model>.hip (parallel compilation); see the header for the design.
-#include "score_pool_kernels.h"
+#include "score_pool_plan.h"
 #include "gemm_mfma.h"
 
 #include <stdlib.h>
+#include <algorithm>
 
 namespace mkb {
 
@@ -336,196 +337,207 @@ struct Workspace {
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static int units_of(const mkb_tables_t *tb) { return tb->model == MKB_ROTATE ? tb->hidden_dim : (int)tb->entity_dim; }
+static int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// Kernel configuration for a table shape: units per lane (vector width of the loads), waves per workgroup, and how
-// many workgroups share a row tile / position tile so that the grid fills 256 CUs with 16-32 waves each.
-// ComplEx / DistMult: the pair function is a dot product, so the pooled block is three dense fp32 GEMMs on the matrix
-// cores (gemm_mfma.h) instead of the lane-owns-dims VALU kernels.  MKB_POOL_NO_MFMA=1 keeps the VALU kernels (the tests'
-// independent route).
-// (The two per-call switches -- MKB_POOL_NO_MFMA, MKB_POOL_DENSE -- change the workspace layout.  Callers cache a workspace
-// per table shape, so mkb_pool_step_workspace_bytes reports the LARGEST layout over the switches' settings: g_force_* let it
-// ask pick_config for each.  Found in round 4 by filling freed device memory with NaN between calls: a workspace sized for the
-// matrix route was handed to the VALU route of the same shape -- tests that flipped the switch had been reading and writing past it.)
-static thread_local int g_force_mfma = -1, g_force_dense = -1;  // -1: as the environment says
-
-static bool use_mfma(const mkb_tables_t *tb) {
-    const char *e = getenv("MKB_POOL_NO_MFMA");  // read per call: the tests switch it within one process
-    const bool off = g_force_mfma >= 0 ? g_force_mfma == 0 : (e && e[0] == '1');
-    return !off && (tb->model == MKB_COMPLEX || tb->model == MKB_DISTMULT) && tb->entity_dim >= 16;
+// read once per ABI call (the tests switch them within one process)
+static PoolSwitches switches_from_env() {
+    const char *m = getenv("MKB_POOL_NO_MFMA"), *d = getenv("MKB_POOL_DENSE");
+    return PoolSwitches{m && m[0] == '1', !d ? PoolSwitches::kDenseDefault : (d[0] == '1' ? PoolSwitches::kDenseOn : PoolSwitches::kDenseOff)};
 }
 
-static bool pick_config(const mkb_tables_t *tb, int64_t B, int64_t P, PoolLaunch &L) {
-    // relation-gradient copies of the row backward: when a relation averages >= 16 rows of the batch, spread them so that
-    // ~4 rows share a copy, within 1 MB of scratch (WN18RR B = 1024: 11 relations -> 23 copies; FB15k-237: none)
-    L.rel_elems = tb->n_relation * tb->relation_dim;
-    L.rel_copies = 1;
-    L.n_entity = tb->n_entity;
-    {
-        const int64_t per_rel = tb->n_relation > 0 ? B / tb->n_relation : 0;
-        if (per_rel >= 16 && L.rel_elems > 0) {
-            int64_t c = per_rel / 4;
-            const int64_t cap = (1 << 18) / L.rel_elems;  // 1 MB of floats
-            if (c > cap) c = cap;
-            if (c > 64) c = 64;
-            if (c >= 2) L.rel_copies = (int)c;
-        }
-    }
-    const int NU = units_of(tb);
+// What the plan's decisions know about a table row
+struct RowShape {
+    int NU;           // units per row: complex numbers for RotatE, floats otherwise
+    bool cp, al16;    // RotatE's complex units; 16-byte aligned table
+    bool k4;          // 4 units per lane possible (pRotatE: no 4-units-per-lane instantiations, see launch_shape)
+    int row_tiles, pos_tiles;
+};
+
+// relation-gradient copies of the row backward: when a relation averages >= 16 rows of the batch, spread them so that
+// ~4 rows share a copy, within 1 MB of scratch (WN18RR B = 1024: 11 relations -> 23 copies; FB15k-237: none)
+static int plan_rel_copies(const mkb_tables_t *tb, int64_t B) {
+    const int64_t rel_elems = tb->n_relation * tb->relation_dim;
+    const int64_t per_rel = tb->n_relation > 0 ? B / tb->n_relation : 0;
+    if (per_rel < 16 || rel_elems <= 0) return 1;
+    int64_t c = per_rel / 4;
+    const int64_t cap = (1 << 18) / rel_elems;  // 1 MB of floats
+    if (c > cap) c = cap;
+    if (c > 64) c = 64;
+    return c >= 2 ? (int)c : 1;
+}
+
+// units per lane: vector loads + packed math need even dims; waves: smallest workgroup that covers the row
+static bool plan_row_shape(const mkb_tables_t *tb, int64_t B, int64_t P, RowShape &R, PoolPlan &L) {
     const int64_t De = tb->entity_dim, d = tb->hidden_dim;
-    const bool cp = tb->model == MKB_ROTATE;
-    const bool al16 = (((uintptr_t)tb->ent) & 15) == 0;
-    const bool even2 = al16 && NU % 2 == 0 && De % 2 == 0 && (!cp || d % 2 == 0);
-    const bool even4 = al16 && NU % 4 == 0 && De % 4 == 0 && (!cp || d % 4 == 0);
-    // units per lane: vector loads + packed math need even dims; waves: smallest workgroup that covers the row
-    const bool k4 = even4 && tb->model != MKB_PROTATE;  // (pRotatE: no 4-units-per-lane instantiations, see launch_head)
-    if (even2 && NU >= 64 && NU <= 2048) L.kpt = 2;
-    else if (k4 && NU > 2048 && NU <= 4096) L.kpt = 4;
-    else if (NU <= 1024) L.kpt = 1;
+    R.NU = tb->model == MKB_ROTATE ? tb->hidden_dim : (int)tb->entity_dim;
+    R.cp = tb->model == MKB_ROTATE;
+    R.al16 = (((uintptr_t)tb->ent) & 15) == 0;
+    const bool even2 = R.al16 && R.NU % 2 == 0 && De % 2 == 0 && (!R.cp || d % 2 == 0);
+    const bool even4 = R.al16 && R.NU % 4 == 0 && De % 4 == 0 && (!R.cp || d % 4 == 0);
+    R.k4 = even4 && tb->model != MKB_PROTATE;
+    R.row_tiles = (int)((B + TI - 1) / TI);
+    R.pos_tiles = (int)((P + TI - 1) / TI);
+    if (even2 && R.NU >= 64 && R.NU <= 2048) L.kpt = 2;
+    else if (R.k4 && R.NU > 2048 && R.NU <= 4096) L.kpt = 4;
+    else if (R.NU <= 1024) L.kpt = 1;
     else return false;
-    const int lanes = (NU + L.kpt - 1) / L.kpt;
+    const int lanes = (R.NU + L.kpt - 1) / L.kpt;
     if (L.kpt == 1) L.nw = lanes <= 64 ? 1 : (lanes <= 128 ? 2 : (lanes <= 256 ? 4 : 16));
     else if (L.kpt == 2) L.nw = lanes <= 64 ? 1 : (lanes <= 128 ? 2 : (lanes <= 256 ? 4 : (lanes <= 512 ? 8 : 16)));
     else L.nw = 16;
-    // forward: 4 units per lane when the row allows it (measured 91 -> 77 us at the headline shape: the per-position
-    // wave reduction is amortised over twice the pair evaluations); the backward kernels gain nothing from it
-    L.fkpt = L.kpt; L.fnw = L.nw;
-    if (k4 && NU > 512 && NU <= 1024) { L.fkpt = 4; L.fnw = 4; }
-    // Forward of the complex-modulus models: dense prefix [0, Kd) of the pool on the outer-product register tile, the sparse
-    // fringe on the row-tile kernel in the same launch (score_pool_tile.h).  Needs the 4-wave forward configuration (rows of
-    // 257 .. 1024 complex dims), whole 64-position tiles in the prefix (K = P / 2 >= 64) and 16-byte rows.
-    L.tile = 0; L.tile_kd = 0; L.tile_ks = 1; L.tile_fringe_slices = 1;
-    {
-        const int64_t Kd = (P / 2) / 64 * 64;
-        // (round 5: TransE's |q - x| on the same tile -- its "dims" are pairs of floats, so that a chunk is 32 floats either way)
-        const bool te = tb->model == MKB_TRANSE && De % 4 == 0;
-        const int64_t dt = cp ? d : De / 2;
-        if ((te || (cp && d % 4 == 0)) && !use_mfma(tb) && al16 && L.fnw == 4 && (L.fkpt == 4 || L.fkpt == 2) && Kd >= 64 && B >= 64) {
-            L.tile = 1;
-            L.tile_kd = (int)Kd;
-            const int tiles = (int)((B + 63) / 64) * (int)(Kd / 64);
-            int ks = 1;
-            while (tiles * ks < 512 && ks < 16 && dt / (ks * 2) >= 32) ks *= 2;  // fill the chip; >= 2 chunks of 16 dims per split
-            L.tile_ks = ks;
-            L.tile_fringe_slices = 2;
-        }
+    return true;
+}
+
+// ComplEx / DistMult: the pair function is a dot product, so the pooled block is three dense fp32 GEMMs on the matrix
+// cores (gemm_mfma.h) instead of the lane-owns-dims VALU kernels.
+static bool wants_matrix(const mkb_tables_t *tb, const PoolSwitches &sw) {
+    return !sw.no_mfma && (tb->model == MKB_COMPLEX || tb->model == MKB_DISTMULT) && tb->entity_dim >= 16;
+}
+
+static void plan_forward(const mkb_tables_t *tb, int64_t B, int64_t P, const RowShape &R, const PoolSwitches &sw, PoolPlan &L) {
+    if (wants_matrix(tb, sw)) { L.fwd = FwdRoute::Matrix; return; }
+    // 4 units per lane when the row allows it (measured 91 -> 77 us at the headline shape: the per-position wave
+    // reduction is amortised over twice the pair evaluations); the backward kernels gain nothing from it
+    const bool wide = R.k4 && R.NU > 512 && R.NU <= 1024;
+    const int fkpt = wide ? 4 : L.kpt, fnw = wide ? 4 : L.nw;
+    // Complex-modulus models and TransE (its "dims" are pairs of floats, so that a chunk is 32 floats either way): dense
+    // prefix [0, Kd) of the pool on the outer-product register tile, the sparse fringe on the row-tile kernel in the same
+    // launch (score_pool_tile.h).  Needs the 4-wave forward configuration (rows of 257 .. 1024 complex dims), whole
+    // 64-position tiles in the prefix (K = P / 2 >= 64) and 16-byte rows.
+    const int64_t De = tb->entity_dim, d = tb->hidden_dim, Kd = (P / 2) / 64 * 64;
+    const bool te = tb->model == MKB_TRANSE && De % 4 == 0;
+    if ((te || (R.cp && d % 4 == 0)) && R.al16 && fnw == 4 && (fkpt == 4 || fkpt == 2) && Kd >= 64 && B >= 64) {
+        const int64_t dt = R.cp ? d : De / 2;
+        const int tiles = (int)((B + 63) / 64) * (int)(Kd / 64);
+        int ks = 1;
+        while (tiles * ks < 512 && ks < 16 && dt / (ks * 2) >= 32) ks *= 2;  // fill the chip; >= 2 chunks of 16 dims per split
+        L.fwd = FwdRoute::Tile;
+        L.tile = {fkpt, (int)Kd, ks, 2};
+        return;
     }
+    // ~32 waves per CU (short rows: 99 -> 79 us at the 8-GPU shard; flat at the headline shape)
+    L.fwd = FwdRoute::RowTile;
+    L.rows = {fkpt, fnw, clampi((256 * 32 / fnw + R.row_tiles - 1) / R.row_tiles, 1, kMaxSlices)};
+}
+
+// Slice counts of the two-pass backward, swept on the headline shape and on the dimension shards of 2 / 4 / 8 GPUs
+// (tools/shard_emulate.py: rows grow, rows get shorter, workgroups shrink to 4 / 2 / 1 waves).
+static void plan_two_pass(int64_t B, const RowShape &R, PoolPlan &L) {
     const int target = 256 * 16 / L.nw;  // workgroups for ~16 waves per CU
-    const int row_tiles = (int)((B + TI - 1) / TI), pos_tiles = (int)((P + TI - 1) / TI);
-    auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    // Slice counts, swept on the headline shape and on the dimension shards of 2 / 4 / 8 GPUs (tools/shard_emulate.py:
-    // rows grow, rows get shorter, workgroups shrink to 4 / 2 / 1 waves).
-    // forward: ~32 waves per CU (short rows: 99 -> 79 us at the 8-GPU shard; flat at the headline shape)
-    L.fwd_slices = clampi((256 * 32 / L.fnw + row_tiles - 1) / row_tiles, 1, kMaxSlices);
-    L.mfma = use_mfma(tb) ? 1 : 0;
     // dq pass: it shares its launch with the dx pass, so with big workgroups half the waves suffice (headline: 2 slices
     // instead of 4 keep the merged kernel at 160 us and save row_bwd 4 us of partial-buffer reads); 1- and 2-wave
-    // workgroups want the full count (8-GPU shard: 210 -> 185 us).  GEMM route: complete dQ rows.
+    // workgroups want the full count (8-GPU shard: 210 -> 185 us).
     const int q_target = L.nw >= 4 ? target / 2 : target;
-    L.q_slices = L.mfma ? 1 : clampi((q_target + row_tiles - 1) / row_tiles, 1, kMaxSlices);
+    L.two.q_slices = clampi((q_target + R.row_tiles - 1) / R.row_tiles, 1, kMaxSlices);
     // x pass: rows of a slice are listed in LDS (40 B each): keep a slice <= 256 rows so several workgroups fit a CU;
     // single-wave workgroups do better with 256-row slices than with 128 (8-GPU shard: 209 -> 192 us)
     const int min_x = (int)((B + 255) / 256);
     const int x_target = L.nw == 1 ? target / 2 : target;
-    L.x_slices = clampi((x_target + pos_tiles - 1) / pos_tiles, min_x > 2 ? min_x : 2, 1 << 20);
-    // Single-pass backward (pool_bwd1_kernel; VALU models only): dims are cut into slices of 64 * kpt units, positions into
-    // blocks of <= 64 * halves (LDS accumulator <= 128 KB), row tiles into groups of 16 waves.  Position blocks are doubled
-    // until the grid holds ~4096 waves (16 per CU); each block costs one dQ partial buffer.
-    {
-        L.bwd1 = L.mfma ? 0 : 1;
-        L.row_groups = 0; L.cplx = cp ? 1 : 0; L.pb_halves = 0; L.tiles_per_wave = 1;
-        // units per lane of the single-pass backward: 2 (1 for odd rows); real-valued models with long rows take 4 -- the
-        // same 4 floats per lane and position as RotatE's two complex dims, half the per-position bookkeeping of 2
-        const int k1 = (!cp && k4 && NU >= 512) ? 4 : (L.kpt >= 2 ? 2 : 1), nc = k1 * (cp ? 2 : 1);
-        L.bkpt = k1;
-        const int lanes1 = (NU + k1 - 1) / k1;
-        L.dim_slices = (lanes1 + 63) / 64;
-        const int max_halves = 128 * 1024 / (64 * nc * 64 * 4);  // 2 at nc = 4, 4 at nc = 2, 8 at nc = 1
-        int npb = 1;
-        while (((P + npb - 1) / npb + 63) / 64 > max_halves) npb *= 2;
-        while (npb < kMaxSlices && (int64_t)row_tiles * L.dim_slices * npb < 4096 && (P + npb - 1) / npb > 32) npb *= 2;
-        if (npb > kMaxSlices) {  // too many positions for the single-pass kernel: the two-pass one (pool_bwd_kernel)
-            L.bwd1 = 0;
-            // (compiled only where a shape can reach it; the check keeps a route with no kernel from being picked)
-            if (!L.mfma && !pool_two_pass_compiled(tb->model, L.kpt)) return false;
-        }
-        if (L.bwd1) {
-            L.q_slices = npb;
-            // halves: ROUNDED UP to a power of two.  The kernel cuts its 16 chunks into 16 / halves lanes per half, the seed
-            // layout (common.h) shifts by log2(halves), and carve() sizes G / dXp with the same value: 3, 5, 6, 7 would break
-            // all three (e.g. TransE hidden 500, B 2048, K 384: 192 positions per block = 3 halves).  max_halves is a power
-            // of two, so the rounded value still fits the LDS accumulator; slots past P are masked in the kernel.
-            int halves = (int)(((P + npb - 1) / npb + 63) / 64), h2 = 1;
-            while (h2 < halves) h2 *= 2;
-            L.pb_halves = h2;
-            if (h2 > max_halves || (npb & (npb - 1)) != 0) L.bwd1 = 0;  // (cannot happen: both loops above keep the invariants)
-        }
-        L.dense_lanes = 0;
-        if (L.bwd1) {
-            // Dense pass (pool_bwd1_kernel<..., DENSE>).  Every row takes its first K = P / 2 surviving candidates, so positions
-            // p < K are used by (nearly) every row.  Slot (h, l) holds position block + npb * (l * halves + h): lanes
-            // l < K / (npb * halves) of every half are dense; rounded down to whole lanes per chunk (a chunk = every cph-th lane
-            // of a half).  Round 3: the same gradients; per step, same box, general vs dense pass:
-            // headline 0.242 -> 0.240 ms, WN18RR 0.150 -> 0.143, YAGO3-10 0.206 -> 0.202, TransE-1000 0.183 -> 0.185.  So: on
-            // for the complex-modulus pair function; the real-valued ones have no dense form (round 4: their ten instantiations
-            // were 0.6 MB of the library for a path that measured slower); MKB_POOL_DENSE=0 switches it off (read per call: the
-            // tests switch it within one process).
-            const char *e = getenv("MKB_POOL_DENSE");
-            const int cph = 16 / L.pb_halves;
-            const int ld = (int)((P / 2) / ((int64_t)npb * L.pb_halves)) / cph * cph;
-            // (round 5: TransE as well -- with its pair term down to 5 VALU operations the general pass's per-position bookkeeping is a
-            // quarter of the loop: 62.7 -> 59.5 us at the headline shape, same call; DistMult / ComplEx / pRotatE never had the form)
-            const bool dense_model = cp || tb->model == MKB_TRANSE;
-            const bool on = dense_model && (g_force_dense >= 0 ? g_force_dense == 1 : (e ? e[0] == '1' : true));  // (launch_bwd1 compiles the dense form for the complex-modulus models only)
-            if (on && cph >= 1 && ld > 0 && ld <= 32) L.dense_lanes = ld;
-        }
-        // Small problems: when the single-pass grid would be a handful of 16-wave workgroups, its ring and its prologue ARE the
-        // launch (Umls TransE-64, K 16, B 256: two workgroups, 43 us for 0.5 MFLOP).  One wave per (row tile, <= 64 positions,
-        // 64 * kpt units) instead: pool_bwd_wave_kernel; position slices until ~1024 waves are in flight.
-        L.small = 0; L.skpt = 1; L.schunks = 1;
-        if (L.bwd1) {
-            const int groups1 = (row_tiles + 15) / 16;
-            const int skpt = L.kpt >= 2 ? 2 : 1;
-            const int chunks = (NU + 64 * skpt - 1) / (64 * skpt);
-            int nsl = (int)((P + 63) / 64);
-            while (nsl < kMaxSlices && (int64_t)row_tiles * chunks * nsl < 1024 && P / nsl > 2) ++nsl;
-            if ((int64_t)groups1 * npb * L.dim_slices <= 32 && nsl <= kMaxSlices) {
-                L.small = 1; L.bwd1 = 0; L.skpt = skpt; L.schunks = chunks; L.q_slices = nsl;
-                L.dense_lanes = 0; L.pb_halves = 0;
-            }
-        }
-        if (L.bwd1) {
-            const int64_t waves = (int64_t)row_tiles * L.dim_slices * npb;
-            L.tiles_per_wave = (int)(waves >= 3 * 4096 ? waves / (2 * 4096) : 1);
-            L.row_groups = (row_tiles + 16 * L.tiles_per_wave - 1) / (16 * L.tiles_per_wave);
-            L.cplx = cp ? 1 : 0;
-        }
-    }
+    L.two.x_slices = clampi((x_target + R.pos_tiles - 1) / R.pos_tiles, min_x > 2 ? min_x : 2, 1 << 20);
+    L.dq_parts = L.two.q_slices;
+}
+
+// Small problems: when the single-pass grid would be a handful of 16-wave workgroups, its ring and its prologue ARE the
+// launch (Umls TransE-64, K 16, B 256: two workgroups, 43 us for 0.5 MFLOP).  One wave per (row tile, <= 64 positions,
+// 64 * kpt units) instead: pool_bwd_wave_kernel; position slices until ~1024 waves are in flight.
+static bool plan_wave(int64_t P, const RowShape &R, const Bwd1Layout &Y, PoolPlan &L) {
+    const int groups1 = (R.row_tiles + kBwd1Waves - 1) / kBwd1Waves;
+    const int kpt = L.kpt >= 2 ? 2 : 1;
+    const int chunks = (R.NU + 64 * kpt - 1) / (64 * kpt);
+    int nsl = (int)((P + 63) / 64);
+    while (nsl < kMaxSlices && (int64_t)R.row_tiles * chunks * nsl < 1024 && P / nsl > 2) ++nsl;
+    if ((int64_t)groups1 * Y.blocks * Y.dim_slices > 32 || nsl > kMaxSlices) return false;
+    L.wave = {kpt, chunks, nsl};
+    L.dq_parts = nsl;
     return true;
 }
 
-static Workspace carve(void *ws, int64_t B, int64_t P, int64_t De, const PoolLaunch &L) {
+// Dense pass (pool_bwd1_kernel<..., DENSE>).  Every row takes its first K = P / 2 surviving candidates, so positions
+// p < K are used by (nearly) every row.  Slot (h, l) holds position block + blocks * (l * halves + h): lanes
+// l < K / (blocks * halves) of every half are dense; rounded down to whole lanes per chunk (a chunk = every cph-th lane
+// of a half).  DESIGN.md section 8: the same gradients; per step, same box, general vs dense pass:
+// headline 0.242 -> 0.240 ms, WN18RR 0.150 -> 0.143, YAGO3-10 0.206 -> 0.202, TransE-1000 0.183 -> 0.185.  So: on
+// for the complex-modulus pair function and for TransE (with its pair term down to 5 VALU operations the general pass's
+// per-position bookkeeping is a quarter of the loop: 62.7 -> 59.5 us at the headline shape, same call); the other
+// real-valued models have no dense form (their ten instantiations were 0.6 MB of the library for a path that measured slower).
+static int plan_dense_lanes(const mkb_tables_t *tb, int64_t P, const Bwd1Layout &Y, const PoolSwitches &sw) {
+    const bool dense_model = tb->model == MKB_ROTATE || tb->model == MKB_TRANSE;
+    if (!dense_model || sw.dense == PoolSwitches::kDenseOff) return 0;
+    const int cph = kChunks / Y.halves;
+    const int ld = (int)((P / 2) / ((int64_t)Y.blocks * Y.halves)) / cph * cph;
+    return cph >= 1 && ld > 0 && ld <= 32 ? ld : 0;
+}
+
+// VALU models.  Single-pass backward: position blocks are doubled until the halves fit the LDS accumulator, then until the
+// grid holds ~4096 waves (16 per CU); each block costs one dQ partial buffer.  More blocks than dQ buffers: the two-pass
+// kernel; a handful of workgroups: the wave kernel.
+static bool plan_backward(const mkb_tables_t *tb, int64_t B, int64_t P, const RowShape &R, const PoolSwitches &sw, PoolPlan &L) {
+    if (wants_matrix(tb, sw)) { L.bwd = BwdRoute::Matrix; L.dq_parts = kMfmaDqSlices; return true; }
+    Bwd1Layout Y{};
+    // units per lane: 2 (1 for odd rows); real-valued models with long rows take 4 -- the same 4 floats per lane and
+    // position as RotatE's two complex dims, half the per-position bookkeeping of 2
+    Y.kpt = (!R.cp && R.k4 && R.NU >= 512) ? 4 : (L.kpt >= 2 ? 2 : 1);
+    Y.cplx = R.cp ? 1 : 0;
+    Y.dim_slices = ((R.NU + Y.kpt - 1) / Y.kpt + 63) / 64;
+    int npb = 1;
+    while (Bwd1Layout::halves_for(P, npb) > Bwd1Layout::max_halves(Y.nc())) npb *= 2;
+    while (npb < kMaxSlices && (int64_t)R.row_tiles * Y.dim_slices * npb < 4096 && (P + npb - 1) / npb > 32) npb *= 2;
+    Y.blocks = npb;
+    if (npb > kMaxSlices) {
+        // (compiled only where a shape can reach it; the check keeps a route with no kernel from being picked)
+        if (!pool_two_pass_compiled(tb->model, L.kpt)) return false;
+        L.bwd = BwdRoute::TwoPass;
+        plan_two_pass(B, R, L);
+        return true;
+    }
+    if (plan_wave(P, R, Y, L)) { L.bwd = BwdRoute::Wave; return true; }
+    Y.halves = Bwd1Layout::halves_for(P, npb);
+    Y.dense_lanes = plan_dense_lanes(tb, P, Y, sw);
+    const int64_t waves = (int64_t)R.row_tiles * Y.dim_slices * npb;
+    Y.tiles_per_wave = (int)(waves >= 3 * 4096 ? waves / (2 * 4096) : 1);
+    Y.row_groups = (R.row_tiles + kBwd1Waves * Y.tiles_per_wave - 1) / (kBwd1Waves * Y.tiles_per_wave);
+    if (!Y.valid()) return false;
+    L.bwd = BwdRoute::SinglePass;
+    L.single = Y;
+    L.dq_parts = npb;
+    return true;
+}
+
+// Kernel configuration for a table shape: units per lane (vector width of the loads), waves per workgroup, the routes, and
+// how many workgroups share a row tile / position tile so that the grid fills 256 CUs with 16-32 waves each.
+static bool plan_pool(const mkb_tables_t *tb, int64_t B, int64_t P, const PoolSwitches &sw, PoolPlan &L) {
+    L = PoolPlan{};
+    L.rel_elems = tb->n_relation * tb->relation_dim;
+    L.rel_copies = plan_rel_copies(tb, B);
+    L.n_entity = tb->n_entity;
+    RowShape R;
+    if (!plan_row_shape(tb, B, P, R, L)) return false;
+    plan_forward(tb, B, P, R, sw, L);
+    return plan_backward(tb, B, P, R, sw, L);
+}
+
+// Callers cache a workspace per table shape while the per-call switches change the layout: mkb_pool_step_workspace_bytes
+// reports the largest layout over the switches' settings.
+static Workspace carve(void *ws, int64_t B, int64_t P, int64_t De, const PoolPlan &L) {
     Workspace w;
     unsigned char *p = (unsigned char *)ws;
     size_t off = 0;
     auto take = [&](size_t n) { void *r = p ? p + off : nullptr; off += align256(n); return (float *)r; };
+    const bool sp = L.single_pass();
     w.Q = take((size_t)B * De * 4);
-    w.dQ = take((size_t)(L.mfma ? kMfmaDqSlices : L.q_slices) * B * De * 4);  // (MFMA route: room for the dQ product's K split)
-    // gradient seeds: plain [B, P], or the tile-blocked layout of the single-pass backward (rows padded to tiles of 8,
-    // positions to blocks * halves * 64 slots)
-    const size_t g_plain = (size_t)B * P, g_blocked = L.bwd1 ? (size_t)((B + 7) / 8) * L.q_slices * L.pb_halves * 64 * 8 : 0;
+    w.dQ = take((size_t)L.dq_parts * B * De * 4);
+    // gradient seeds: plain [B, P], or the tile-blocked layout of the single-pass backward
+    const size_t g_plain = (size_t)B * P, g_blocked = sp ? L.single.seed_elems(B) : 0;
     w.G = take((g_plain > g_blocked ? g_plain : g_blocked) * 4);
     w.dpos = take((size_t)B * 4);
     w.scratch = take((size_t)(B + 1) * 4);
-    w.gemm_part = take(L.mfma ? (size_t)8 * B * (P > De ? P : De) * 4 : 0);  // split-K partials of the MFMA path
-    // single-pass backward: dx partials per row group [groups][blocks][slots][dim slices][64 lanes][NC] + used-slot masks
-    const size_t nc = (size_t)L.bkpt * (L.cplx ? 2 : 1);
-    w.dXp = take(L.bwd1 ? (size_t)L.row_groups * L.q_slices * L.pb_halves * 64 * L.dim_slices * 64 * nc * 4 : 0);
-    w.xused = (unsigned long long *)take(L.bwd1 ? (size_t)L.row_groups * L.q_slices * 8 * 8 : 0);
+    w.gemm_part = take(L.matrix() ? (size_t)8 * B * (P > De ? P : De) * 4 : 0);  // split-K partials of the MFMA path
+    w.dXp = take(sp ? L.single.dxp_elems() * 4 : 0);
+    w.xused = (unsigned long long *)take(sp ? L.single.xused_words() * 8 : 0);
     w.rel_rep = take(L.rel_copies > 1 ? (size_t)L.rel_copies * L.rel_elems * 4 : 0);
     w.occ = (int *)take((size_t)L.n_entity * 4);
-    w.depth = (int *)take(L.mfma ? (size_t)B * 4 : 0);
-    w.tile_part = take(L.tile ? (size_t)L.tile_ks * B * L.tile_kd * 4 : 0);  // dim-split partial scores of the dense prefix
+    w.depth = (int *)take(L.matrix() ? (size_t)B * 4 : 0);
+    w.tile_part = take(L.fwd == FwdRoute::Tile ? (size_t)L.tile.ks * B * L.tile.kd * 4 : 0);  // dim-split partial scores of the dense prefix
     w.bytes = off;
     return w;
 }
@@ -536,191 +548,142 @@ static int g_trace_kind = 2;
 extern "C" void mkb_debug_set_trace(void *p, int kind) { g_trace = (unsigned long long *)p; g_trace_kind = kind; }
 #endif
 
-static SeedLayout seed_layout(const PoolLaunch &L) {
-    if (!L.bwd1) return SeedLayout{-1, 0};
-    auto lg = [](int v) { int b = 0; while ((1 << b) < v) ++b; return b; };
-    return SeedLayout{lg(L.q_slices), lg(L.pb_halves)};
-}
-
+// every PoolArgs field that follows from the tables, the workspace and the plan (bwd: of the plan's backward route)
 static PoolArgs make_args(const mkb_tables_t *tb, const int64_t *pool, const uint16_t *cnt, int64_t B, int64_t P,
-                          const Workspace &w, const PoolLaunch &L) {
+                          const Workspace &w, const PoolPlan &L, bool bwd) {
     PoolArgs A{};
     A.ent = tb->ent; A.Q = w.Q; A.pool = pool; A.cnt = cnt; A.G = w.G; A.dQ = w.dQ;
     A.B = (int)B; A.P = (int)P; A.d = tb->hidden_dim; A.De = tb->entity_dim; A.kd = tb->phase_div;
-    A.modulus = tb->modulus; A.x_slices = L.x_slices; A.q_slices = L.q_slices;
-    A.dXp = w.dXp; A.xused = w.xused;
-    A.g_blocked = L.bwd1 ? 1 : 0;
+    A.modulus = tb->modulus;
     const bool g = tb->model == MKB_TRANSE || tb->model == MKB_ROTATE || tb->model == MKB_PROTATE;
     A.c0 = g ? tb->gamma : 0.f;
     A.c1 = g ? -1.f : 1.f;
+    if (bwd) switch (L.bwd) {
+        case BwdRoute::SinglePass:
+            A.q_slices = L.single.blocks; A.dim_slices = L.single.dim_slices; A.pb_halves = L.single.halves;
+            A.tiles_per_wave = L.single.tiles_per_wave; A.dense_lanes = L.single.dense_lanes;
+            A.lds_ids_off = L.single.lds_ids_off();
+            A.dXp = w.dXp; A.xused = w.xused; A.g_blocked = 1;
+            break;
+        case BwdRoute::Wave: A.q_slices = L.wave.slices; break;
+        case BwdRoute::TwoPass: A.q_slices = L.two.q_slices; A.x_slices = L.two.x_slices; break;
+        case BwdRoute::Matrix: break;
+    }
 #ifdef MKB_TRACE_WG
     A.trace = g_trace; A.trace_kind = g_trace_kind;
 #endif
     return A;
 }
 
-static pool_launch_fn launcher_of(int model) {
-    switch (model) {
-        case MKB_TRANSE: return pool_launch_transe;
-        case MKB_ROTATE: return pool_launch_rotate;
-        case MKB_COMPLEX: return pool_launch_complex;
-        case MKB_DISTMULT: return pool_launch_distmult;
-        case MKB_PROTATE: return pool_launch_protate;
-    }
-    return nullptr;
+static int launch_tiles(const mkb_tables_t *tb, bool head, int which, const PoolPlan &L, const PoolArgs &A, hipStream_t st) {
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return pool_launch<m(), h()>(which, L, A, st); });
 }
 
-template <int MODEL, bool HEAD>
-static int run_query_build(const RowArgs &ra, int64_t B, hipStream_t st) {
-    hipLaunchKernelGGL((query_build_kernel<MODEL, HEAD>), dim3((unsigned)B), dim3(256), 0, st, ra);
+// The row kernels for the tables' model and the call's side: one workgroup of 256 lanes per batch row
+template <class Args>
+static int launch_rows(void (*kernel)(Args), unsigned blocks, const Args &ra, hipStream_t st) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, ra);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
-
-template <int MODEL, bool HEAD>
-static int run_query_bwd(const RowArgs &ra, int64_t B, hipStream_t st) {
-    hipLaunchKernelGGL((query_bwd_kernel<MODEL, HEAD>), dim3((unsigned)B), dim3(256), 0, st, ra);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
+static int launch_query_build(const mkb_tables_t *tb, bool head, const RowArgs &ra, hipStream_t st) {
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return launch_rows(query_build_kernel<m(), h()>, (unsigned)ra.B, ra, st); });
+}
+static int launch_query_bwd(const mkb_tables_t *tb, bool head, const RowArgs &ra, hipStream_t st) {
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return launch_rows(query_bwd_kernel<m(), h()>, (unsigned)ra.B, ra, st); });
+}
+static int launch_row_fwd(const mkb_tables_t *tb, bool head, const RowStepArgs &ra, hipStream_t st) {
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return launch_rows(row_fwd_kernel<m(), h()>, (unsigned)ra.B, ra, st); });
+}
+static int launch_row_bwd(const mkb_tables_t *tb, bool head, const RowStepArgs &ra, hipStream_t st) {
+    const unsigned blocks = (unsigned)(ra.B + ra.dx.blocks + (ra.sc.kind == 2 ? ra.sc.M : 0));  // (the riders' workgroups come first)
+    return dispatch_model_side(tb->model, head, [&](auto m, auto h) { return launch_rows(row_bwd_kernel<m(), h()>, blocks, ra, st); });
 }
 
-template <int MODEL, bool HEAD>
-static int run_row_fwd(const RowStepArgs &ra, int64_t B, hipStream_t st) {
-    hipLaunchKernelGGL((row_fwd_kernel<MODEL, HEAD>), dim3((unsigned)B), dim3(256), 0, st, ra);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-template <int MODEL, bool HEAD>
-static int run_row_bwd(const RowStepArgs &ra, int64_t B, hipStream_t st) {
-    hipLaunchKernelGGL((row_bwd_kernel<MODEL, HEAD>), dim3((unsigned)(B + ra.dx.blocks + (ra.sc.kind == 2 ? ra.sc.M : 0))), dim3(256),
-                       0, st, ra);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-#define MKB_DISPATCH(fn, model, head, ...)                                                            \
-    switch (model) {                                                                                  \
-        case MKB_TRANSE: return (head) ? fn<MKB_TRANSE, true>(__VA_ARGS__) : fn<MKB_TRANSE, false>(__VA_ARGS__);       \
-        case MKB_ROTATE: return (head) ? fn<MKB_ROTATE, true>(__VA_ARGS__) : fn<MKB_ROTATE, false>(__VA_ARGS__);       \
-        case MKB_COMPLEX: return (head) ? fn<MKB_COMPLEX, true>(__VA_ARGS__) : fn<MKB_COMPLEX, false>(__VA_ARGS__);    \
-        case MKB_DISTMULT: return (head) ? fn<MKB_DISTMULT, true>(__VA_ARGS__) : fn<MKB_DISTMULT, false>(__VA_ARGS__); \
-        case MKB_PROTATE: return (head) ? fn<MKB_PROTATE, true>(__VA_ARGS__) : fn<MKB_PROTATE, false>(__VA_ARGS__);    \
-    }                                                                                                 \
-    return set_error(MKB_ERR_INVALID, "unknown model")
-
-static int dispatch_query_build(const mkb_tables_t *tb, bool head, const RowArgs &ra, int64_t B, hipStream_t st) {
-    MKB_DISPATCH(run_query_build, tb->model, head, ra, B, st);
-}
-static int dispatch_query_bwd(const mkb_tables_t *tb, bool head, const RowArgs &ra, int64_t B, hipStream_t st) {
-    MKB_DISPATCH(run_query_bwd, tb->model, head, ra, B, st);
-}
-
-static int dispatch_row_fwd(const mkb_tables_t *tb, bool head, const RowStepArgs &ra, int64_t B, hipStream_t st) {
-    MKB_DISPATCH(run_row_fwd, tb->model, head, ra, B, st);
-}
-static int dispatch_row_bwd(const mkb_tables_t *tb, bool head, const RowStepArgs &ra, int64_t B, hipStream_t st) {
-    MKB_DISPATCH(run_row_bwd, tb->model, head, ra, B, st);
+// Q = the rows' queries; matrix route: + the used pool depth per row (GEMM cuts)
+static int build_queries(const mkb_tables_t *tb, bool head, const int64_t *sample, const uint16_t *cnt, int64_t B, int64_t P,
+                         const Workspace &w, const PoolPlan &L, hipStream_t st) {
+    RowArgs ra{tb->ent, tb->rel, sample, w.Q, nullptr, nullptr, tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, 1,
+               tb->phase_div};
+    if (L.matrix()) { ra.cnt = cnt; ra.depth = w.depth; ra.P = (int)P; }
+    return launch_query_build(tb, head, ra, st);
 }
 
 static int pooled_fwd(const mkb_tables_t *tb, bool head, const int64_t *sample, const int64_t *pool, const uint16_t *cnt,
-                      int64_t B, int64_t P, float *S, const Workspace &w, const PoolLaunch &L, hipStream_t st,
-                      bool build_queries = true, GemmTail *s_tail = nullptr, int *occ = nullptr, bool *occ_counted = nullptr) {
+                      int64_t B, int64_t P, float *S, const Workspace &w, const PoolPlan &L, hipStream_t st,
+                      GemmTail *s_tail = nullptr, int *occ = nullptr) {
     if (s_tail) s_tail->kind = 0;
-    if (occ_counted) *occ_counted = false;
-    const bool mfma = use_mfma(tb);  // (the GEMMs multiply only the pool positions each row uses: depth cuts)
-    if (build_queries) {
-        RowArgs ra{tb->ent, tb->rel, sample, w.Q, nullptr, nullptr, tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B,
-                   1, tb->phase_div};
-        if (mfma) { ra.cnt = cnt; ra.depth = w.depth; ra.P = (int)P; }
-        if (int rc = dispatch_query_build(tb, head, ra, B, st)) return rc;
-    }
-    if (mfma) {  // S = Q . ent[pool]^T on the matrix cores, over the pool positions the row tile uses (cnt masks later)
+    ProfScope ps(MKB_PROF_POOL_FWD, st);
+    if (L.fwd == FwdRoute::Matrix) {  // S = Q . ent[pool]^T on the matrix cores, over the pool positions the row tile uses (cnt masks later)
         GemmArgs g{};
         g.A = w.Q; g.lda = tb->entity_dim; g.B = tb->ent; g.ldb = tb->entity_dim; g.b_idx = pool; g.b_rows = tb->n_entity;
         g.C = S; g.ldc = P; g.M = (int)B; g.N = (int)P; g.K = (int)tb->entity_dim; g.c0 = 0.f; g.c1 = 1.f;
         g.depth = w.depth; g.depth_mode = 1; g.n_depth = (int)B;
-        ProfScope ps(MKB_PROF_POOL_FWD, st);
         return launch_gemm<true, true, GEMM_STORE_AFFINE>(g, st, w.gemm_part, s_tail, s_tail ? 500 : 0);
     }
-    PoolArgs A = make_args(tb, pool, cnt, B, P, w, L);  // (the kernel also zero-fills the entries no row uses)
+    PoolArgs A = make_args(tb, pool, cnt, B, P, w, L, /*bwd=*/false);  // (the kernel also zero-fills the entries no row uses)
     A.S = S;
-    if (occ) { A.occ = occ; A.occ_sample = sample; if (occ_counted) *occ_counted = true; }
-    ProfScope ps(MKB_PROF_POOL_FWD, st);
-    if (L.tile) {  // (s_tail: the loss rows of mkb_pool_step add the prefix's partial sums up; otherwise S is finished here)
+    if (occ) { A.occ = occ; A.occ_sample = sample; }
+    if (L.fwd == FwdRoute::Tile) {  // (s_tail: the loss rows of mkb_pool_step add the prefix's partial sums up; otherwise S is finished here)
         A.tile_part = w.tile_part;
         A.tile_tail = s_tail;
-        return launcher_of(tb->model)(kPoolFwdTile, head, L, A, st);
     }
-    return launcher_of(tb->model)(kPoolFwd, head, L, A, st);
+    return launch_tiles(tb, head, kPoolFwd, L, A, st);
 }
 
-// dq_slices (out): how many [B, De] partial products the dQ buffer holds (the consumer -- row / query backward -- adds them up)
-static int pooled_bwd(const mkb_tables_t *tb, bool head, const mkb_grads_t *gr, const int64_t *sample, const int64_t *pool,
-                      const uint16_t *cnt, int64_t B, int64_t P, const Workspace &w, const PoolLaunch &L, hipStream_t st,
-                      bool chain_queries = true, DxReduce *dx_out = nullptr, GemmTail *x_tail = nullptr, int *dq_slices = nullptr) {
-    int dq_used = L.q_slices;
+// the two products of the matrix route; dq_parts (out): how many [B, De] partial products the dQ buffer holds
+static int matrix_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *pool, int64_t B, int64_t P, const Workspace &w,
+                      hipStream_t st, GemmTail *x_tail, int *dq_parts) {
+    // dQ [B, De] = G [B, P] . ent[pool]   (w.depth was written by this call's row_fwd / query_build)
+    GemmArgs gq{};
+    gq.A = w.G; gq.lda = P; gq.B = tb->ent; gq.ldb = tb->entity_dim; gq.b_idx = pool; gq.b_rows = tb->n_entity;
+    gq.C = w.dQ; gq.ldc = tb->entity_dim; gq.M = (int)B; gq.N = (int)tb->entity_dim; gq.K = (int)P;
+    gq.depth = w.depth; gq.depth_mode = 2; gq.n_depth = (int)B;  // (G is exactly 0 beyond a row's depth)
+    // g_ent[pool[p]] += (G^T [P, B] . Q [B, De])[p]
+    GemmArgs gx{};
+    gx.A = w.G; gx.lda = P; gx.B = w.Q; gx.ldb = tb->entity_dim; gx.b_idx = nullptr;
+    gx.C = gr->g_ent; gx.ldc = tb->entity_dim; gx.c_idx = pool; gx.M = (int)P; gx.N = (int)tb->entity_dim; gx.K = (int)B;
+    gx.depth = w.depth; gx.depth_mode = 3; gx.n_depth = (int)B;
+    bool paired = false;
+    {   // both products in ONE launch where they qualify (profiled as the POOL_BWD_Q class)
+        ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
+        if (int rc = launch_gemm_bwd_pair(gq, kMfmaDqSlices, dq_parts, gx, w.gemm_part, x_tail, st, &paired)) return rc;
+    }
+    if (paired) return MKB_OK;
+    {
+        ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
+        // a K split of this product leaves its partials in the dQ slices: the row backward sums them (it does so for the
+        // VALU route's position blocks anyway) instead of a reduction launch in between (DistMult: 6.5 us)
+        if (int rc = launch_gemm<true, false, GEMM_STORE>(gq, st, w.gemm_part, nullptr, 0, kMfmaDqSlices, dq_parts)) return rc;
+    }
+    ProfScope ps(MKB_PROF_POOL_BWD_X, st);
+    return launch_gemm<false, false, GEMM_ATOMIC_ROWS>(gx, st, w.gemm_part, x_tail, x_tail ? 500 : 0);
+}
+
+// dq_parts (out): how many [B, De] partial products the dQ buffer holds (the consumer -- row / query backward -- adds them up)
+static int pooled_bwd(const mkb_tables_t *tb, bool head, const mkb_grads_t *gr, const int64_t *pool, const uint16_t *cnt, int64_t B,
+                      int64_t P, const Workspace &w, const PoolPlan &L, hipStream_t st, DxReduce *dx_out, GemmTail *x_tail,
+                      int *dq_parts) {
+    *dq_parts = L.dq_parts;
     if (x_tail) x_tail->kind = 0;
-    if (use_mfma(tb)) {  // (w.depth was written by this call's row_fwd / query_build)
-        // dQ [B, De] = G [B, P] . ent[pool]
-        GemmArgs gq{};
-        gq.A = w.G; gq.lda = P; gq.B = tb->ent; gq.ldb = tb->entity_dim; gq.b_idx = pool; gq.b_rows = tb->n_entity;
-        gq.C = w.dQ; gq.ldc = tb->entity_dim; gq.M = (int)B; gq.N = (int)tb->entity_dim; gq.K = (int)P;
-        gq.depth = w.depth; gq.depth_mode = 2; gq.n_depth = (int)B;  // (G is exactly 0 beyond a row's depth)
-        // g_ent[pool[p]] += (G^T [P, B] . Q [B, De])[p]
-        GemmArgs gx{};
-        gx.A = w.G; gx.lda = P; gx.B = w.Q; gx.ldb = tb->entity_dim; gx.b_idx = nullptr;
-        gx.C = gr->g_ent; gx.ldc = tb->entity_dim; gx.c_idx = pool; gx.M = (int)P; gx.N = (int)tb->entity_dim; gx.K = (int)B;
-        gx.depth = w.depth; gx.depth_mode = 3; gx.n_depth = (int)B;
-        bool paired = false;
-        {   // round 5: both products in ONE launch where they qualify (profiled as the POOL_BWD_Q class)
-            ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launch_gemm_bwd_pair(gq, kMfmaDqSlices, &dq_used, gx, w.gemm_part, x_tail, st, &paired)) return rc;
-        }
-        if (!paired) {
-            {
-                ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-                // a K split of this product leaves its partials in the dQ slices: the row backward sums them (it does so for the
-                // VALU route's position blocks anyway) instead of a reduction launch in between (DistMult: 6.5 us)
-                if (int rc = launch_gemm<true, false, GEMM_STORE>(gq, st, w.gemm_part, nullptr, 0, kMfmaDqSlices, &dq_used)) return rc;
-            }
-            ProfScope ps(MKB_PROF_POOL_BWD_X, st);
-            if (int rc = launch_gemm<false, false, GEMM_ATOMIC_ROWS>(gx, st, w.gemm_part, x_tail, x_tail ? 500 : 0)) return rc;
-        }
-    } else {
-        PoolArgs A = make_args(tb, pool, cnt, B, P, w, L);
-        A.g_modulus = gr->g_modulus;
-        A.g_ent = gr->g_ent;
-        A.dx_reduce_out = dx_out;
-        if (L.bwd1) {  // every pair term evaluated once (pool_bwd1_kernel); profiled as the POOL_BWD_Q class
-            ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launcher_of(tb->model)(kPoolBwd1, head, L, A, st)) return rc;
-        } else if (L.small) {  // a small problem: one wave per piece, every pair evaluated once (pool_bwd_wave_kernel)
-            ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launcher_of(tb->model)(kPoolBwdSmall, head, L, A, st)) return rc;
-        } else {  // dq and dx passes in one grid (pool_bwd_kernel); profiled as the POOL_BWD_Q class
-            ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-            if (int rc = launcher_of(tb->model)(kPoolBwd, head, L, A, st)) return rc;
-        }
-    }
-    if (dq_slices) *dq_slices = dq_used;
-    if (chain_queries) {
-        RowArgs ra{tb->ent, tb->rel, sample, w.dQ, gr->g_ent, gr->g_rel, tb->entity_dim, tb->relation_dim, tb->hidden_dim,
-                   (int)B, dq_used, tb->phase_div};
-        if (int rc = dispatch_query_bwd(tb, head, ra, B, st)) return rc;
-    }
-    return MKB_OK;
+    if (L.matrix()) return matrix_bwd(tb, gr, pool, B, P, w, st, x_tail, dq_parts);
+    PoolArgs A = make_args(tb, pool, cnt, B, P, w, L, /*bwd=*/true);
+    A.g_modulus = gr->g_modulus;
+    A.g_ent = gr->g_ent;
+    A.dx_reduce_out = dx_out;
+    ProfScope ps(MKB_PROF_POOL_BWD_Q, st);  // (all three tile routes are profiled as the POOL_BWD_Q class)
+    return launch_tiles(tb, head, kPoolBwd, L, A, st);
 }
 
 static int check_pool_call(const mkb_tables_t *tb, const int64_t *sample, const int64_t *pool, const uint16_t *cnt, int64_t B,
-                           int64_t K, int mode, const void *ws, PoolLaunch &L) {
+                           int64_t K, int mode, const void *ws, PoolPlan &L) {
     if (int rc = validate_tables(tb)) return rc;
     MKB_REQUIRE(sample && pool && cnt && ws, "null pointer");
     MKB_REQUIRE(B > 0 && K > 0 && B <= INT32_MAX, "bad B / K");
     MKB_REQUIRE(tb->n_entity <= INT32_MAX, "n_entity too large");
     MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "the pooled path needs head-batch or tail-batch");
     MKB_REQUIRE((((uintptr_t)ws) & 255) == 0, "workspace must be 256-byte aligned");
-    if (2 * K > kMaxP || !pick_config(tb, B, 2 * K, L))
+    if (2 * K > kMaxP || !plan_pool(tb, B, 2 * K, switches_from_env(), L))
         return set_error(MKB_ERR_UNSUPPORTED, "shape not covered by the pooled kernels (size <= 1024, rows <= 4096 units, "
                                               "even dims above 256 units); use the general path");
     return MKB_OK;
@@ -731,59 +694,57 @@ static int check_pool_call(const mkb_tables_t *tb, const int64_t *sample, const 
 using namespace mkb;
 
 extern "C" int mkb_pool_supported(const mkb_tables_t *tb, int64_t B, int64_t K) {
-    PoolLaunch L;
-    return tb && B > 0 && K > 0 && 2 * K <= kMaxP && tb->n_entity <= INT32_MAX && pick_config(tb, B, 2 * K, L);
+    PoolPlan L;
+    return tb && B > 0 && K > 0 && 2 * K <= kMaxP && tb->n_entity <= INT32_MAX && plan_pool(tb, B, 2 * K, switches_from_env(), L);
 }
 
 extern "C" int64_t mkb_pool_step_workspace_bytes(const mkb_tables_t *tb, int64_t B, int64_t K) {
     if (!tb || B <= 0 || K <= 0) return 0;
+    PoolPlan L;
+    if (!plan_pool(tb, B, 2 * K, switches_from_env(), L)) return 0;  // (the shape must be supported as the environment stands)
     int64_t best = 0;
-    bool any = false;
-    for (int fm = 0; fm <= 1; ++fm)
-        for (int fd = 0; fd <= 1; ++fd) {  // the largest layout over the per-call switches (see g_force_mfma)
-            PoolLaunch L;
-            g_force_mfma = fm; g_force_dense = fd;
-            const bool ok = pick_config(tb, B, 2 * K, L);
-            const int64_t n = ok ? (int64_t)carve(nullptr, B, 2 * K, tb->entity_dim, L).bytes : 0;
-            g_force_mfma = -1; g_force_dense = -1;
-            any = any || ok;
-            if (n > best) best = n;
-        }
-    PoolLaunch L;
-    if (!pick_config(tb, B, 2 * K, L)) return 0;  // (the shape must be supported as the environment stands)
-    return any ? best : 0;
+    for (bool no_mfma : {false, true})
+        for (PoolSwitches::Dense dense : {PoolSwitches::kDenseOff, PoolSwitches::kDenseOn})
+            if (plan_pool(tb, B, 2 * K, PoolSwitches{no_mfma, dense}, L))
+                best = std::max(best, (int64_t)carve(nullptr, B, 2 * K, tb->entity_dim, L).bytes);
+    return best;
 }
 
 extern "C" int mkb_pool_score_fwd(const mkb_tables_t *tb, const int64_t *sample, const int64_t *pool, const uint16_t *cnt,
                                   int64_t B, int64_t K, int mode, float *pool_score, void *ws, void *stream) {
-    PoolLaunch L;
+    PoolPlan L;
     if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
     MKB_REQUIRE(pool_score != nullptr, "pool_score is null");
     const Workspace w = carve(ws, B, 2 * K, tb->entity_dim, L);
-    return pooled_fwd(tb, mode_is_head(mode), sample, pool, cnt, B, 2 * K, pool_score, w, L, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = build_queries(tb, mode_is_head(mode), sample, cnt, B, 2 * K, w, L, st)) return rc;
+    return pooled_fwd(tb, mode_is_head(mode), sample, pool, cnt, B, 2 * K, pool_score, w, L, st);
 }
 
 extern "C" int mkb_pool_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const int64_t *pool,
                                   const uint16_t *cnt, int64_t B, int64_t K, int mode, const float *dpool_score, void *ws,
                                   void *stream) {
-    PoolLaunch L;
+    PoolPlan L;
     if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
     MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && dpool_score, "null pointer");
     MKB_REQUIRE(tb->model != MKB_PROTATE || gr->g_modulus, "pRotatE needs g_modulus");
-    Workspace w = carve(ws, B, 2 * K, tb->entity_dim, L);
+    const int64_t P = 2 * K;
+    const Workspace w = carve(ws, B, P, tb->entity_dim, L);
     hipStream_t st = (hipStream_t)stream;
+    const bool head = mode_is_head(mode);
     // rebuild the queries (the forward's copy may have been overwritten by another call sharing the workspace)
-    RowArgs ra{tb->ent, tb->rel, sample, w.Q, nullptr, nullptr, tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, 1,
-               tb->phase_div};
-    if (use_mfma(tb)) { ra.cnt = cnt; ra.depth = w.depth; ra.P = (int)(2 * K); }  // used pool depth per row (GEMM cuts)
-    if (int rc = dispatch_query_build(tb, mode_is_head(mode), ra, B, st)) return rc;
+    if (int rc = build_queries(tb, head, sample, cnt, B, P, w, L, st)) return rc;
     // G = caller's gradient with the entries no row uses forced to 0 (the single-pass backward reads the mask off G)
-    const SeedLayout sl = seed_layout(L);
-    const int64_t n_pad = sl.log2_blocks >= 0 ? (B + 7) / 8 * 8 * 2 * K : B * 2 * K;
+    const int64_t n_pad = (L.single_pass() ? Bwd1Layout::padded_rows(B) : B) * P;
     hipLaunchKernelGGL(masked_copy_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, dpool_score, cnt, w.G,
-                       B * 2 * K, n_pad, 2 * K, sl);
+                       B * P, n_pad, P, L.seeds());
     MKB_LAUNCH_CHECK();
-    return pooled_bwd(tb, mode_is_head(mode), gr, sample, pool, cnt, B, 2 * K, w, L, st);
+    int dq_parts = 0;
+    if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, nullptr, nullptr, &dq_parts)) return rc;
+    // chain dQ into the fixed operands' gradient rows
+    RowArgs ra{tb->ent, tb->rel, sample, w.dQ, gr->g_ent, gr->g_rel, tb->entity_dim, tb->relation_dim, tb->hidden_dim,
+               (int)B, dq_parts, tb->phase_div};
+    return launch_query_bwd(tb, head, ra, st);
 }
 
 // The two halves of mkb_pool_step.  Between them the caller may combine the scores of several devices that each
@@ -792,7 +753,7 @@ extern "C" int mkb_pool_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr,
 // s_tail (mkb_pool_step only): the MFMA forward may leave the scores as split-K partials for the loss rows to reduce
 static int pool_step_fwd(const mkb_tables_t *tb, const int64_t *sample, const int64_t *pool, const uint16_t *cnt, int64_t B,
                          int64_t K, int mode, float *pos_score, float *pool_score, void *ws, void *stream, GemmTail *s_tail) {
-    PoolLaunch L;
+    PoolPlan L;
     if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
     MKB_REQUIRE(pos_score && pool_score, "null pointer");
     const int64_t P = 2 * K;
@@ -800,18 +761,17 @@ static int pool_step_fwd(const mkb_tables_t *tb, const int64_t *sample, const in
     hipStream_t st = (hipStream_t)stream;
     const bool head = mode_is_head(mode);
     RowStepArgs ra{tb->ent, tb->rel, tb->modulus, sample, w.Q, w.dQ, pos_score, w.dpos, nullptr, nullptr, nullptr,
-                   tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, L.q_slices, tb->phase_div, tb->gamma};
+                   tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, L.dq_parts, tb->phase_div, tb->gamma};
     ra.occ = w.occ; ra.pool = pool; ra.P = (int)P;
     if (L.rel_copies > 1) { ra.rel_rep = w.rel_rep; ra.rel_copies = L.rel_copies; ra.n_rel = (int)tb->n_relation; }
-    if (use_mfma(tb)) { ra.cnt = cnt; ra.depth = w.depth; ra.depth_P = (int)P; }  // used pool depth per row (GEMM cuts)
+    if (L.matrix()) { ra.cnt = cnt; ra.depth = w.depth; ra.depth_P = (int)P; }  // used pool depth per row (GEMM cuts)
     // positive pass (mode None: tail-style formula against the true tail, pipeline.py:211) + negative-path queries
     {
         ProfScope ps(MKB_PROF_GENERAL_FWD, st);
-        if (int rc = dispatch_row_fwd(tb, head, ra, B, st)) return rc;
+        if (int rc = launch_row_fwd(tb, head, ra, st)) return rc;
     }
     // negative pass over the shared pool (pipeline.py:230-232)
-    return pooled_fwd(tb, head, sample, pool, cnt, B, P, pool_score, w, L, st, /*build_queries=*/false,
-                      (s_tail && P <= 64 * 16) ? s_tail : nullptr, ra.occ);
+    return pooled_fwd(tb, head, sample, pool, cnt, B, P, pool_score, w, L, st, (s_tail && P <= 64 * 16) ? s_tail : nullptr, ra.occ);
 }
 
 // s_tail: scores still in split-K partials (from pool_step_fwd); fold: the scattered product's tail rides the row backward
@@ -819,7 +779,7 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
                          const int64_t *pool, const uint16_t *cnt, int64_t B, int64_t K, int mode, float alpha,
                          const float *weight_sum, const float *pos_score, float *pool_score, float *loss, void *ws,
                          void *stream, const GemmTail *s_tail) {
-    PoolLaunch L;
+    PoolPlan L;
     if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
     MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && weight && pos_score && pool_score && loss, "null pointer");
     MKB_REQUIRE(tb->model != MKB_PROTATE || gr->g_modulus, "pRotatE needs g_modulus");
@@ -828,7 +788,7 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
     hipStream_t st = (hipStream_t)stream;
     const bool head = mode_is_head(mode);
     RowStepArgs ra{tb->ent, tb->rel, tb->modulus, sample, w.Q, w.dQ, nullptr, w.dpos, gr->g_ent, gr->g_rel, gr->g_modulus,
-                   tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, L.q_slices, tb->phase_div, tb->gamma};
+                   tb->entity_dim, tb->relation_dim, tb->hidden_dim, (int)B, L.dq_parts, tb->phase_div, tb->gamma};
     // Adversarial forward + gradient seeds (pipeline.py:234 and the head of :236)
     ra.occ = w.occ; ra.pool = pool; ra.P = (int)P;
     if (L.rel_copies > 1) {  // (zeroed by the row forward kernel of this step)
@@ -836,19 +796,18 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
     }
     // (the occurrence counts: the VALU forward kernel counted them; the MFMA path has no such kernel, the loss rows do it)
     if (int rc = adversarial_launch(pos_score, pool_score, weight, cnt, B, P, alpha, weight_sum, loss, w.dpos, w.G, w.scratch, st,
-                                    /*defer_finish=*/true, seed_layout(L), s_tail, use_mfma(tb) ? ra.occ : nullptr,
+                                    /*defer_finish=*/true, L.seeds(), s_tail, L.matrix() ? ra.occ : nullptr,
                                     sample, pool)) return rc;
     ra.loss_rowpart = w.scratch + 1;
     ra.loss_scal = weight_sum ? weight_sum : w.scratch;
     ra.loss_out = loss;
     // backward (pipeline.py:236): pooled negatives, then the positive pair and both query chains in one row kernel
-    if (int rc = pooled_bwd(tb, head, gr, sample, pool, cnt, B, P, w, L, st, /*chain_queries=*/false, L.bwd1 ? &ra.dx : nullptr,
-                            &ra.sc, &ra.nslices)) return rc;
+    if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, L.single_pass() ? &ra.dx : nullptr, &ra.sc, &ra.nslices)) return rc;
     ra.dx.occ = ra.occ;  // (the dx reduction riding this launch writes pool rows: exclusive ones without atomics)
     ra.grads_clear = gr->rows_clear ? 1 : 0;
     ra.dx.clear = ra.grads_clear;
     ProfScope ps(MKB_PROF_GENERAL_BWD, st);
-    if (int rc = dispatch_row_bwd(tb, head, ra, B, st)) return rc;
+    if (int rc = launch_row_bwd(tb, head, ra, st)) return rc;
     if (ra.rel_rep) {
         hipLaunchKernelGGL(rel_fold_kernel, dim3((unsigned)((L.rel_elems + 255) / 256)), dim3(256), 0, st, ra.rel_rep, gr->g_rel,
                            L.rel_copies, L.rel_elems);

@@ -1801,166 +1801,4 @@ __device__ __forceinline__ void pool_dx_reduce_block(const DxReduce &R, int bloc
 template <int UNUSED = 0>  // (a template so that the header can be included by several translation units)
 __global__ __launch_bounds__(256) void pool_dx_reduce_kernel(DxReduce R) { pool_dx_reduce_block(R, (int)blockIdx.x); }
 
-inline DxReduce make_dx_reduce(const PoolArgs &A, int kpt, bool cplx, int row_groups) {
-    DxReduce R{};
-    R.dXp = A.dXp; R.xused = A.xused; R.pool = A.pool; R.g_ent = A.g_ent; R.De = A.De; R.P = A.P; R.d = A.d;
-    R.npb = A.q_slices; R.halves = A.pb_halves; R.dim_slices = A.dim_slices; R.row_groups = row_groups; R.kpt = kpt;
-    R.cplx = cplx ? 1 : 0; R.blocks = A.q_slices * A.pb_halves * 64;
-    return R;
-}
-
-// ------------------------------------------------------------------------------------------------ launch helpers
-struct PoolLaunch {
-    int kpt, nw;          // units per lane, waves per workgroup (backward kernels)
-    int fkpt, fnw;        // the same for the forward kernel (it amortises its wave reduction over more units per lane)
-    int fwd_slices, q_slices, x_slices;
-    int mfma;             // bilinear models: dense fp32 MFMA GEMMs instead of the tile kernels
-    int bwd1;             // single-pass backward (pool_bwd1_kernel): q_slices = position blocks, plus the five below
-    int bkpt;             // its units per lane (1, 2, or 4 for real-valued models with long rows)
-    int dim_slices, pb_halves, tiles_per_wave, row_groups, cplx;
-    int dense_lanes;      // lanes of every half that hold dense-prefix positions (pool_bwd1_kernel's dense pass; 0 = none)
-    int tile, tile_kd, tile_ks, tile_fringe_slices;  // forward: dense prefix [0, tile_kd) on the register tile (score_pool_tile.h)
-    int small, skpt, schunks;  // backward of a small problem: pool_bwd_wave_kernel (q_slices position slices, skpt units per lane, schunks dim chunks)
-    int rel_copies;       // > 1: copies of the relation gradient the row backward spreads its atomics over (few relations)
-    int64_t rel_elems;    // n_relation * relation_dim
-    int64_t n_entity;
-};
-
-// The kernels a pool_launch_fn launches (its `which` argument)
-constexpr int kPoolFwd = 0;       // forward (pool_fwd_kernel)
-constexpr int kPoolBwd = 1;       // two-pass backward: dq and dx passes in one grid (pool_bwd_kernel)
-constexpr int kPoolBwd1 = 2;      // single-pass backward (pool_bwd1_kernel)
-constexpr int kPoolFwdTile = 3;   // forward: dense prefix on the register tile + sparse fringe (pool_fwd_tile_kernel)
-constexpr int kPoolBwdSmall = 4;  // backward of a small problem, one wave per piece (pool_bwd_wave_kernel)
-
-// The two-pass backward runs only when a pool needs more position blocks than the single-pass kernel has (pick_config),
-// which takes 4 floats per lane and position: RotatE at >= 2 units per lane, or a real-valued model at 4 (pRotatE has no
-// 4-unit form).  It is compiled for these (model, units per lane) pairs alone.
-constexpr bool pool_two_pass_compiled(int model, int kpt) { return model != MKB_PROTATE && kpt >= 2; }
-
-// Per-model entry points (defined in score_pool_<model>.hip): launch one of the kernels above for (head, config).
-typedef int (*pool_launch_fn)(int which, bool head, const PoolLaunch &L, const PoolArgs &A, hipStream_t st);
-int pool_launch_transe(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
-int pool_launch_rotate(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
-int pool_launch_complex(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
-int pool_launch_distmult(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
-int pool_launch_protate(int, bool, const PoolLaunch &, const PoolArgs &, hipStream_t);
-
-template <int MODEL, bool HEAD, int KPT, int NW>
-static int launch_cfg(int which, const PoolLaunch &L, const PoolArgs &A, hipStream_t st) {
-    const dim3 block(NW * 64);
-    if (which == kPoolFwd) {
-        dim3 grid((unsigned)((A.B + TI - 1) / TI), (unsigned)L.fwd_slices);
-        hipLaunchKernelGGL((pool_fwd_kernel<MODEL, HEAD, KPT, NW>), grid, block, (size_t)3 * ((A.P + L.fwd_slices - 1) / L.fwd_slices) * 4, st, A);
-    } else if constexpr (pool_two_pass_compiled(MODEL, KPT)) {
-        const size_t rows_per = (size_t)((A.B + L.x_slices - 1) / L.x_slices);
-        const size_t lds_x = ((TI + 2) * rows_per + 16) * 4;
-        const size_t lds_q = ((size_t)(TI + 2) * ((A.P + L.q_slices - 1) / L.q_slices) + 32) * 4;
-        const unsigned xb = (unsigned)(((A.P + TI - 1) / TI) * L.x_slices);
-        const unsigned qb = (unsigned)(((A.B + TI - 1) / TI) * L.q_slices);
-        PoolArgs A2 = A;
-        A2.x_blocks = (int)xb;
-        // dq workgroups ahead of the dx pass: a little under one per CU measured best (headline: 0 -> 169 us, 96..224 ->
-        // 160-165 us, 256 -> 170 us; the other shapes are flat within 2 %)
-        A2.q_first = (int)(qb < 160u ? qb : 160u);
-        hipLaunchKernelGGL((pool_bwd_kernel<MODEL, HEAD, KPT, NW>), dim3(xb + qb), block, lds_x > lds_q ? lds_x : lds_q, st, A2);
-    } else {
-        return set_error(MKB_ERR_UNSUPPORTED, "two-pass pooled backward not compiled for this model at %d units per lane", KPT);
-    }
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-template <int MODEL, bool HEAD, int KPT>
-static int launch_bwd1(const PoolLaunch &L, const PoolArgs &A, hipStream_t st) {
-    constexpr int NC = KPT * (ModelTraits<MODEL>::cplx_pair ? 2 : 1);
-    const bool dense_cfg = A.g_blocked && L.dense_lanes > 0;
-    const size_t lds_pass = (size_t)2 * L.pb_halves * L.dense_lanes * NC * 64 * 4;  // accumulator + row images of the dense slots
-    const size_t lds_rows = L.tiles_per_wave == 1 ? (size_t)kBwd1Waves * TI * NC * 64 * 4 : 0;  // ... then the workgroup's query rows
-    const size_t lds_main = lds_pass > lds_rows ? lds_pass : lds_rows;
-    const size_t lds = dense_cfg ? lds_main + 128 + (size_t)L.pb_halves * 64 * 8  // + the block's pool-id table
-                                 : (size_t)L.pb_halves * 64 * NC * 64 * 4 + 128;
-    PoolArgs A2 = A;
-    A2.q_slices = L.q_slices; A2.dim_slices = L.dim_slices; A2.pb_halves = L.pb_halves; A2.tiles_per_wave = L.tiles_per_wave;
-    A2.dense_lanes = A.g_blocked ? L.dense_lanes : 0;  // (the dense pass reads the blocked seed layout)
-    A2.lds_ids_off = (int)(lds_main / 4);
-    // the dense form is compiled for the complex-modulus pair function and for TransE (pick_config never asks for it elsewhere:
-    // DistMult / ComplEx take the matrix route, pRotatE's term is two transcendental chains; every instantiation is ~60 KB)
-    constexpr bool kHasDense = ModelTraits<MODEL>::cplx_pair || MODEL == MKB_TRANSE;
-    const bool dense = kHasDense && A2.dense_lanes > 0;
-    if (!kHasDense && A2.dense_lanes > 0) return set_error(MKB_ERR_INVALID, "the dense pass is built for the complex-modulus models and TransE only");
-    static LdsOptIn lds_ok[2];  // per instantiation: opt in to more than 64 KB of dynamic LDS once per device
-    if (lds > 64 * 1024) {
-        const void *fn = reinterpret_cast<const void *>(&pool_bwd1_kernel<MODEL, HEAD, KPT, false>);
-        if constexpr (kHasDense)
-            if (dense) fn = reinterpret_cast<const void *>(&pool_bwd1_kernel<MODEL, HEAD, KPT, true>);
-        if (int rc = lds_ok[dense].ensure(fn, 160 * 1024)) return rc;
-    }
-    const int row_tiles = (A.B + TI - 1) / TI, per_group = kBwd1Waves * L.tiles_per_wave;
-    const unsigned groups = (unsigned)((row_tiles + per_group - 1) / per_group);
-    bool launched = false;
-    if constexpr (kHasDense)
-        if (dense) {
-            hipLaunchKernelGGL((pool_bwd1_kernel<MODEL, HEAD, KPT, true>), dim3(groups * L.q_slices * L.dim_slices),
-                               dim3(kBwd1Waves * 64), lds, st, A2);
-            launched = true;
-        }
-    if (!launched)
-        hipLaunchKernelGGL((pool_bwd1_kernel<MODEL, HEAD, KPT, false>), dim3(groups * L.q_slices * L.dim_slices),
-                           dim3(kBwd1Waves * 64), lds, st, A2);
-    const DxReduce R = make_dx_reduce(A2, KPT, ModelTraits<MODEL>::cplx_pair, (int)groups);
-    if (A.dx_reduce_out) *A.dx_reduce_out = R;  // the caller's next launch (row backward) carries the reduction
-    else hipLaunchKernelGGL(pool_dx_reduce_kernel<0>, dim3((unsigned)R.blocks), dim3(256), 0, st, R);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-template <int MODEL, bool HEAD>
-static int launch_fwd_tile(const PoolLaunch &L, const PoolArgs &A, hipStream_t st, float *part, GemmTail *tail);  // score_pool_tile.h
-
-template <int MODEL, bool HEAD, int KPT>
-static int launch_wave(const PoolLaunch &L, const PoolArgs &A, hipStream_t st) {
-    PoolArgs A2 = A;
-    A2.q_slices = L.q_slices;
-    const dim3 grid((unsigned)((A.B + TI - 1) / TI), (unsigned)L.q_slices, (unsigned)L.schunks);
-    hipLaunchKernelGGL((pool_bwd_wave_kernel<MODEL, HEAD, KPT>), grid, dim3(64), 0, st, A2);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-template <int MODEL, bool HEAD>
-static int launch_head(int which, const PoolLaunch &L0, const PoolArgs &A, hipStream_t st) {
-    if (which == kPoolFwdTile) return launch_fwd_tile<MODEL, HEAD>(L0, A, st, A.tile_part, A.tile_tail);
-    if (which == kPoolBwdSmall) return L0.skpt == 2 ? launch_wave<MODEL, HEAD, 2>(L0, A, st) : launch_wave<MODEL, HEAD, 1>(L0, A, st);
-    if (which == kPoolBwd1) {
-        if constexpr (!ModelTraits<MODEL>::cplx_pair && MODEL != MKB_PROTATE)
-            if (L0.bkpt == 4) return launch_bwd1<MODEL, HEAD, 4>(L0, A, st);
-        return L0.bkpt >= 2 ? launch_bwd1<MODEL, HEAD, 2>(L0, A, st) : launch_bwd1<MODEL, HEAD, 1>(L0, A, st);
-    }
-    if (which != kPoolFwd && which != kPoolBwd) return set_error(MKB_ERR_INVALID, "unknown pooled kernel %d", which);
-    PoolLaunch L = L0;
-    if (which == kPoolFwd) { L.kpt = L0.fkpt; L.nw = L0.fnw; }
-    if (L.kpt == 1 && L.nw == 1) return launch_cfg<MODEL, HEAD, 1, 1>(which, L, A, st);
-    if (L.kpt == 2 && L.nw == 1) return launch_cfg<MODEL, HEAD, 2, 1>(which, L, A, st);
-    if (L.kpt == 1 && L.nw == 2) return launch_cfg<MODEL, HEAD, 1, 2>(which, L, A, st);
-    if (L.kpt == 1 && L.nw == 4) return launch_cfg<MODEL, HEAD, 1, 4>(which, L, A, st);
-    if (L.kpt == 1 && L.nw == 16) return launch_cfg<MODEL, HEAD, 1, 16>(which, L, A, st);
-    if (L.kpt == 2 && L.nw == 2) return launch_cfg<MODEL, HEAD, 2, 2>(which, L, A, st);
-    if (L.kpt == 2 && L.nw == 4) return launch_cfg<MODEL, HEAD, 2, 4>(which, L, A, st);
-    if (L.kpt == 2 && L.nw == 8) return launch_cfg<MODEL, HEAD, 2, 8>(which, L, A, st);
-    if (L.kpt == 2 && L.nw == 16) return launch_cfg<MODEL, HEAD, 2, 16>(which, L, A, st);
-    // (pRotatE's pair term carries a sin / cos and two divisions: its 4-units-per-lane bodies are 230 KB of code each and
-    // were a seventh of the library; pick_config keeps that model at <= 2 units per lane)
-    if constexpr (MODEL != MKB_PROTATE) {
-        if (L.kpt == 4 && L.nw == 4) return launch_cfg<MODEL, HEAD, 4, 4>(which, L, A, st);
-        if (L.kpt == 4 && L.nw == 16) return launch_cfg<MODEL, HEAD, 4, 16>(which, L, A, st);
-    }
-    return set_error(MKB_ERR_UNSUPPORTED, "no pooled kernel configuration (kpt=%d, nw=%d)", L.kpt, L.nw);
-}
-
-#define MKB_DEFINE_POOL_LAUNCH(fn, MODEL)                                                                       \
-    int fn(int which, bool head, const PoolLaunch &L, const PoolArgs &A, hipStream_t st) {                      \
-        return head ? launch_head<MODEL, true>(which, L, A, st) : launch_head<MODEL, false>(which, L, A, st); \
-    }
-
 }  // namespace mkb

@@ -18,7 +18,7 @@
 // 51.5 us for the 1024 x 256 x 1000 block against 35.7 us of pure issue time at the measured instruction rates; the old
 // kernel took 69.5 us for prefix + fringe.
 #pragma once
-#include "score_pool_kernels.h"
+#include "score_pool_plan.h"
 
 namespace mkb {
 
@@ -247,21 +247,21 @@ __global__ __launch_bounds__(256) void tile_scores_reduce_kernel(const float *__
 
 // tail: non-null = the consumer adds the partial sums up itself (described in *tail, kind 3); null = S is finished here
 template <int MODEL, bool HEAD>
-static int launch_fwd_tile(const PoolLaunch &L, const PoolArgs &A0, hipStream_t st, float *part, GemmTail *tail) {
+static int launch_fwd_tile(const PoolPlan &L, const PoolArgs &A0, hipStream_t st, float *part, GemmTail *tail) {
     if constexpr (!ModelTraits<MODEL>::cplx_pair && MODEL != MKB_TRANSE) {
         return set_error(MKB_ERR_UNSUPPORTED, "pool_fwd_tile: complex-modulus pair function and TransE only");
     } else {
         PoolArgs A = A0;
         TileArgs T{};
-        T.part = part; T.Kd = L.tile_kd; T.ks = L.tile_ks;
+        T.part = part; T.Kd = L.tile.kd; T.ks = L.tile.ks;
         T.row_tiles = (A.B + kTileRows - 1) / kTileRows; T.pos_tiles = T.Kd / kTilePos;
         A.p_lo = T.Kd;
         const bool fringe = A.P > T.Kd;
         T.fringe_tiles = fringe ? (A.B + TI - 1) / TI : 0;
-        T.fringe_slices = fringe ? L.tile_fringe_slices : 0;
+        T.fringe_slices = fringe ? L.tile.fringe_slices : 0;
         const size_t lds = (T.fringe_tiles > 0) ? (size_t)3 * ((A.P - T.Kd + T.fringe_slices - 1) / T.fringe_slices) * 4 : 0;
         const unsigned blocks = (unsigned)(T.fringe_tiles * T.fringe_slices + T.row_tiles * T.pos_tiles * T.ks);
-        if (L.fkpt == 4) hipLaunchKernelGGL((pool_fwd_tile_kernel<MODEL, HEAD, 4>), dim3(blocks), dim3(256), lds, st, A, T);
+        if (L.tile.kpt == 4) hipLaunchKernelGGL((pool_fwd_tile_kernel<MODEL, HEAD, 4>), dim3(blocks), dim3(256), lds, st, A, T);
         else hipLaunchKernelGGL((pool_fwd_tile_kernel<MODEL, HEAD, 2>), dim3(blocks), dim3(256), lds, st, A, T);
         if (tail) {
             *tail = GemmTail{3, part, A.S, nullptr, A.B, T.Kd, T.ks, A.P, (int64_t)A.B * T.Kd, A.c0, A.c1, nullptr, 0};
