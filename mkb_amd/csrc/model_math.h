@@ -259,4 +259,13 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Sum over a 256-lane workgroup, wave totals added left to right; every lane gets it.  red: 4 floats of LDS, free again
+// only after the caller's next barrier.
+__device__ __forceinline__ float block_sum_4waves(float v, float *red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
 }  // namespace mkb

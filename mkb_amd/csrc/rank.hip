@@ -14,7 +14,7 @@
 // Kernel 2  rank    : one wave per query: count scores above the target's, then walk the query's true set
 //           (a contiguous range of the sorted key array) and take back the ones that were counted.
 #include "common.h"
-#include "model_math.h"
+#include "query_side.h"
 #include "score_pool_tile.h"  // the pooled forward's outer-product register tile, for the all-entity block of RotatE / TransE
 #include "gemm_mfma.h"        // ... and the matrix-core product for ComplEx / DistMult, whose score is a dot product
 
@@ -32,31 +32,6 @@ struct AllArgs {
     int64_t N, De;
     float kd, c0, c1;
 };
-
-__device__ __forceinline__ void reduce8_wave_r(const float (&v)[8], float &t0, float &t1) {
-    float w[4], u[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[j]), __float_as_uint(v[j + 4]), false, false);
-        w[j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[j]), __float_as_uint(w[j + 2]), false, false);
-        u[j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        float t = u[j];
-        t += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(t), 0x128, 0xf, 0xf, false));
-        t += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(t), 0x141, 0xf, 0xf, false));
-        t += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(t), 0xB1, 0xf, 0xf, false));
-        t += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(t), 0x4E, 0xf, 0xf, false));
-        u[j] = t;
-    }
-    t0 = u[0];
-    t1 = u[1];
-}
 
 // NW waves per workgroup: 16 x KPT units per lane cover rows of up to 1024 KPT units; rows of <= 1024 units take 8 waves x 2 units
 // per lane instead of 16 x 1 (round 5: the per-candidate wave reduction -- ~30 cross-lane operations -- is then paid once per 128
@@ -116,7 +91,7 @@ __global__ __launch_bounds__(NW * 64) void all_fwd_kernel(AllArgs A) {
             }
         }
         float t0, t1;
-        reduce8_wave_r(part, t0, t1);
+        reduce8_wave(part, t0, t1);
         const int jj = j % kSlabR, buf = (j / kSlabR) & 1;
         if ((lane & 15) == 0) {
             const int R = lane >> 4, r = 4 * (R >> 1) + 2 * (R & 1);
@@ -200,34 +175,6 @@ __global__ __launch_bounds__(256) void export_scores_kernel(const float *__restr
                                                             float c0, float c1) {
     const int64_t i = blockIdx.y;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < N; e += (int64_t)gridDim.x * 256) out[i * N + e] = c0 + c1 * S[i * ld + e];
-}
-
-struct RowArgsR {
-    const float *ent, *rel;
-    const int64_t *sample;
-    float *Q;
-    int64_t De, Dr;
-    int d;
-    float kd;
-};
-
-template <int MODEL, bool HEAD>
-__global__ __launch_bounds__(256) void query_build_kernel_r(RowArgsR A) {
-    const int64_t i = blockIdx.x;
-    const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
-    const float *eh = A.ent + h * A.De, *er = A.rel + r * A.Dr, *et = A.ent + t * A.De;
-    float *q = A.Q + i * A.De;
-    if constexpr (ModelTraits<MODEL>::cplx_query) {
-        const float *e = HEAD ? et : eh;
-        for (int u = threadIdx.x; u < A.d; u += 256) {
-            Cplx qq = build_q_cplx<MODEL, HEAD>(Cplx{e[u], e[A.d + u]}, Cplx{er[u], MODEL == MKB_COMPLEX ? er[A.d + u] : 0.f}, A.kd);
-            q[u] = qq.re;
-            q[A.d + u] = qq.im;
-        }
-    } else {
-        for (int u = threadIdx.x; u < (int)A.De; u += 256)
-            q[u] = build_q_real<MODEL, HEAD>(HEAD ? er[u] : eh[u], HEAD ? et[u] : er[u], A.kd);
-    }
 }
 
 // ids[i] = min(i, n_real - 1) for i < n (n >= n_real: the padded tail repeats the last row)
@@ -528,8 +475,8 @@ __global__ __launch_bounds__(256) void l2_block_kernel(const float *__restrict__
 template <int MODEL, bool HEAD, class Finish>
 static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, float *Q, float *S, int64_t *ids, hipStream_t st,
                     const Finish &finish) {
-    RowArgsR ra{tb->ent, tb->rel, sample, Q, tb->entity_dim, tb->relation_dim, tb->hidden_dim, tb->phase_div};
-    hipLaunchKernelGGL((query_build_kernel_r<MODEL, HEAD>), dim3((unsigned)B), dim3(256), 0, st, ra);
+    const RowArgs ra = query_build_args(tb->ent, tb->rel, sample, Q, tb->entity_dim, tb->relation_dim, tb->hidden_dim, B, tb->phase_div);
+    hipLaunchKernelGGL((query_build_kernel<MODEL, HEAD>), dim3((unsigned)B), dim3(256), 0, st, ra);
     const float c0 = ModelTraits<MODEL>::uses_gamma ? tb->gamma : 0.f, c1 = ModelTraits<MODEL>::uses_gamma ? -1.f : 1.f;
     // RotatE / TransE: the all-entity block on the pooled forward's register tile (score_pool_tile.h: 64 queries x 64 entities per
     // workgroup, 4 x 4 pairs per lane, operands staged through LDS -- no per-candidate wave reduction at all), the "pool" being

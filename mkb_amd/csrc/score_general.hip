@@ -10,18 +10,19 @@
 // Backward : candidates given (K > 1 slots per row): two passes over the B*K pairs, lanes OWN units k in both (no cross-lane
 //            reduction), neither writes a gradient per pair:
 //              dq pass   one workgroup per batch row; dq accumulates in registers over the row's K candidates and is chained
-//                        into the fixed operands' rows (one atomic per element and row);
+//                        into the fixed operands' rows (one atomic per element and row): score_bwd_kernel<.., DX = false>;
 //              dx pass   the pairs are SORTED BY CANDIDATE (hipCUB radix sort of B*K int32 keys); a workgroup walks 64
 //                        consecutive sorted pairs, keeps the candidate row and its running gradient in registers and adds
 //                        them to the table gradient only when the candidate changes: B*K/64 ... #distinct flushes instead
 //                        of one fp32 atomic per (pair, dim) -- 524 M at the headline shape, which was ~2/3 of the step.
 //            The pair term is evaluated in both passes (cheaper than the atomics it replaces).  Positive triples
-//            (no candidates, K = 1) keep the one-pass kernel.
+//            (no candidates, K = 1) keep the one-pass kernel: the dq pass with its per-pair gradient writes (DX = true).
+//            The dx pass reads the rows' queries from Q [B, De], written by query_side.h's query_build_kernel.
 // The [B,K,D] intermediates of the reference are never materialised.
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
-#include "model_math.h"
+#include "query_side.h"
 
 #include <stdlib.h>
 
@@ -48,36 +49,16 @@ static TablesDev to_dev(const mkb_tables_t *tb) {
     return t;
 }
 
-// Build q for unit u of row (h, r, t).  Real models: one float.  Complex-query models: (re, im).
-template <int MODEL, bool HEAD>
-__device__ __forceinline__ void build_unit(const TablesDev &T, const float *eh, const float *er, const float *et,
-                                           int u, float &q0, float &q1) {
-    if constexpr (ModelTraits<MODEL>::cplx_query) {
-        const float *e = HEAD ? et : eh;
-        Cplx ec{e[u], e[T.d + u]};
-        Cplx rc{er[u], MODEL == MKB_COMPLEX ? er[T.d + u] : 0.f};
-        Cplx q = build_q_cplx<MODEL, HEAD>(ec, rc, T.kd);
-        q0 = q.re; q1 = q.im;
-    } else {
-        const float a = HEAD ? er[u] : eh[u];
-        const float b = HEAD ? et[u] : er[u];
-        q0 = build_q_real<MODEL, HEAD>(a, b, T.kd);
-        q1 = 0.f;
-    }
-}
-
 template <int MODEL, bool HEAD>
 __global__ __launch_bounds__(kBlock) void score_fwd_kernel(TablesDev T, const int64_t *__restrict__ sample,
                                                            const int64_t *__restrict__ cand, int K,
                                                            float *__restrict__ score) {
     extern __shared__ __attribute__((aligned(16))) float q_lds[];
     const int i = blockIdx.x;
-    const int64_t h = sample[3 * (int64_t)i], r = sample[3 * (int64_t)i + 1], t = sample[3 * (int64_t)i + 2];
-    const float *eh = T.ent + h * T.De, *er = T.rel + r * T.Dr, *et = T.ent + t * T.De;
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
-    for (int u = threadIdx.x; u < U; u += kBlock) {
+    const QueryRow R = query_row<MODEL>(T, sample, i);
+    for (int u = threadIdx.x; u < R.U; u += kBlock) {
         float q0, q1;
-        build_unit<MODEL, HEAD>(T, eh, er, et, u, q0, q1);
+        query_unit<MODEL, HEAD>(R, u, q0, q1);
         q_lds[u] = q0;
         if constexpr (ModelTraits<MODEL>::cplx_query) q_lds[T.d + u] = q1;
     }
@@ -86,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void score_fwd_kernel(TablesDev T, const in
     const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
     const bool vec4 = T.vec4 != 0;
     for (int j = wave; j < K; j += kWaves) {
-        const int64_t c = cand ? cand[(int64_t)i * K + j] : t;
+        const int64_t c = cand ? cand[(int64_t)i * K + j] : R.t;
         const float *x = T.ent + c * T.De;
         float acc = 0.f;
         if constexpr (ModelTraits<MODEL>::cplx_pair) {
@@ -118,163 +99,64 @@ __global__ __launch_bounds__(kBlock) void score_fwd_kernel(TablesDev T, const in
     }
 }
 
-template <int MODEL, bool HEAD>
+// Backward over the K candidates of a batch row: one workgroup per row, lanes own units; dq accumulates in registers and is
+// chained into the fixed operands' rows (one atomic per element and row).
+//   DX   the one-pass backward: also one atomic per (pair, element) into the candidate's row.  Positive triples (cand ==
+//        nullptr, K = 1) score against the row's own tail.
+//   !DX  the dq pass of the two-pass backward: no gradient is written per pair.
+template <int MODEL, bool HEAD, bool DX>
 __global__ __launch_bounds__(kBlock) void score_bwd_kernel(TablesDev T, mkb_grads_t G,
                                                            const int64_t *__restrict__ sample,
                                                            const int64_t *__restrict__ cand, int K,
                                                            const float *__restrict__ dscore) {
     __shared__ float red[kWaves];
     const int i = blockIdx.x;
-    const int64_t h = sample[3 * (int64_t)i], r = sample[3 * (int64_t)i + 1], t = sample[3 * (int64_t)i + 2];
-    const float *eh = T.ent + h * T.De, *er = T.rel + r * T.Dr, *et = T.ent + t * T.De;
-    float *g_e = G.g_ent + (HEAD ? t : h) * T.De;  // fixed entity operand of the query
-    float *g_r = G.g_rel + r * T.Dr;
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
+    const QueryRow R = query_row<MODEL>(T, sample, i);
+    float *g_e = G.g_ent + R.ent_id<HEAD>() * T.De;  // fixed entity operand of the query
+    float *g_r = G.g_rel + R.r * T.Dr;
     const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
     float extra = 0.f;
-    for (int u = threadIdx.x; u < U; u += kBlock) {
+    for (int u = threadIdx.x; u < R.U; u += kBlock) {
         float q0, q1;
-        build_unit<MODEL, HEAD>(T, eh, er, et, u, q0, q1);
+        query_unit<MODEL, HEAD>(R, u, q0, q1);
         float dq0 = 0.f, dq1 = 0.f;
         for (int j = 0; j < K; ++j) {
             const float g = dscore[(int64_t)i * K + j];
-            const int64_t c = cand ? cand[(int64_t)i * K + j] : t;
+            const int64_t c = (DX && !cand) ? R.t : cand[(int64_t)i * K + j];
             const float *x = T.ent + c * T.De;
-            float *gx = G.g_ent + c * T.De;
+            auto add_x = [&](int k, float v) {  // the per-pair gradient write, where the parent pass has one
+                if constexpr (DX) atomicAdd(G.g_ent + c * T.De + k, v);
+            };
             if constexpr (ModelTraits<MODEL>::cplx_pair) {
                 Cplx dq, dx;
                 pair_bwd_cmod(Cplx{q0, q1}, Cplx{x[u], x[T.d + u]}, g, dq, dx);
                 dq0 += dq.re; dq1 += dq.im;
-                atomicAdd(gx + u, dx.re);
-                atomicAdd(gx + T.d + u, dx.im);
+                add_x(u, dx.re);
+                add_x(T.d + u, dx.im);
             } else if constexpr (ModelTraits<MODEL>::cplx_query) {  // ComplEx: dot over both halves
                 float a, b, e0 = 0.f;
                 pair_bwd_real<MODEL, HEAD>(q0, x[u], g, T.kd, modulus, a, b, e0);
-                dq0 += a; atomicAdd(gx + u, b);
+                dq0 += a; add_x(u, b);
                 pair_bwd_real<MODEL, HEAD>(q1, x[T.d + u], g, T.kd, modulus, a, b, e0);
-                dq1 += a; atomicAdd(gx + T.d + u, b);
+                dq1 += a; add_x(T.d + u, b);
             } else {
                 float a, b, e0 = 0.f;
                 pair_bwd_real<MODEL, HEAD>(q0, x[u], g, T.kd, modulus, a, b, e0);
-                dq0 += a; atomicAdd(gx + u, b);
+                dq0 += a; add_x(u, b);
                 extra += g * e0;
             }
         }
-        // chain dq into the fixed operands (duplicates across rows add: atomics)
-        if constexpr (ModelTraits<MODEL>::cplx_query) {
-            const float *e = HEAD ? et : eh;
-            Cplx de, dr;
-            query_bwd_cplx<MODEL, HEAD>(Cplx{e[u], e[T.d + u]}, Cplx{er[u], MODEL == MKB_COMPLEX ? er[T.d + u] : 0.f},
-                                        Cplx{dq0, dq1}, T.kd, de, dr);
-            atomicAdd(g_e + u, de.re);
-            atomicAdd(g_e + T.d + u, de.im);
-            atomicAdd(g_r + u, dr.re);
-            if constexpr (MODEL == MKB_COMPLEX) atomicAdd(g_r + T.d + u, dr.im);
-        } else {
-            const float a = HEAD ? er[u] : eh[u], b = HEAD ? et[u] : er[u];
-            float da, db;
-            query_bwd_real<MODEL, HEAD>(a, b, dq0, T.kd, da, db);
-            // tail-style: a = h, b = r ; head-style: a = r, b = t
-            atomicAdd((HEAD ? g_r : g_e) + u, da);
-            atomicAdd((HEAD ? g_e : g_r) + u, db);
-        }
+        Cplx de, dr;
+        query_unit_bwd<MODEL, HEAD>(R, u, dq0, dq1, de, dr);
+        query_grad_atomic<MODEL, HEAD>(g_e, g_r, T.d, u, de, dr);
     }
     if constexpr (MODEL == MKB_PROTATE) {  // d score / d modulus = - sum_k |sin z|   (protate.py:91)
-        extra = wave_sum(extra);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = extra;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float s = 0.f;
-            for (int w = 0; w < kWaves; ++w) s += red[w];
-            atomicAdd(G.g_modulus, -s);
-        }
+        extra = block_sum_4waves(extra, red);
+        if (threadIdx.x == 0) atomicAdd(G.g_modulus, -extra);
     }
 }
 
-// ---- two-pass backward for explicit candidates ---------------------------------------------------------------------
-// Q[i] = query of row i (units as build_unit gives them; complex-query models: re at u, im at d + u)
-template <int MODEL, bool HEAD>
-__global__ __launch_bounds__(kBlock) void general_query_kernel(TablesDev T, const int64_t *__restrict__ sample, float *__restrict__ Q) {
-    const int64_t i = blockIdx.x;
-    const int64_t h = sample[3 * i], r = sample[3 * i + 1], t = sample[3 * i + 2];
-    const float *eh = T.ent + h * T.De, *er = T.rel + r * T.Dr, *et = T.ent + t * T.De;
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
-    for (int u = threadIdx.x; u < U; u += kBlock) {
-        float q0, q1;
-        build_unit<MODEL, HEAD>(T, eh, er, et, u, q0, q1);
-        Q[i * T.De + u] = q0;
-        if constexpr (ModelTraits<MODEL>::cplx_query) Q[i * T.De + T.d + u] = q1;
-    }
-}
-
-// dq pass: the one-pass kernel without its per-pair gradient writes
-template <int MODEL, bool HEAD>
-__global__ __launch_bounds__(kBlock) void score_bwd_q_kernel(TablesDev T, mkb_grads_t G, const int64_t *__restrict__ sample,
-                                                             const int64_t *__restrict__ cand, int K,
-                                                             const float *__restrict__ dscore) {
-    __shared__ float red[kWaves];
-    const int i = blockIdx.x;
-    const int64_t h = sample[3 * (int64_t)i], r = sample[3 * (int64_t)i + 1], t = sample[3 * (int64_t)i + 2];
-    const float *eh = T.ent + h * T.De, *er = T.rel + r * T.Dr, *et = T.ent + t * T.De;
-    float *g_e = G.g_ent + (HEAD ? t : h) * T.De;
-    float *g_r = G.g_rel + r * T.Dr;
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
-    const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
-    float extra = 0.f;
-    for (int u = threadIdx.x; u < U; u += kBlock) {
-        float q0, q1;
-        build_unit<MODEL, HEAD>(T, eh, er, et, u, q0, q1);
-        float dq0 = 0.f, dq1 = 0.f;
-        for (int j = 0; j < K; ++j) {
-            const float g = dscore[(int64_t)i * K + j];
-            const float *x = T.ent + cand[(int64_t)i * K + j] * T.De;
-            if constexpr (ModelTraits<MODEL>::cplx_pair) {
-                Cplx dq, dx;
-                pair_bwd_cmod(Cplx{q0, q1}, Cplx{x[u], x[T.d + u]}, g, dq, dx);
-                dq0 += dq.re; dq1 += dq.im;
-            } else if constexpr (ModelTraits<MODEL>::cplx_query) {
-                float a, b, e0 = 0.f;
-                pair_bwd_real<MODEL, HEAD>(q0, x[u], g, T.kd, modulus, a, b, e0);
-                dq0 += a;
-                pair_bwd_real<MODEL, HEAD>(q1, x[T.d + u], g, T.kd, modulus, a, b, e0);
-                dq1 += a;
-            } else {
-                float a, b, e0 = 0.f;
-                pair_bwd_real<MODEL, HEAD>(q0, x[u], g, T.kd, modulus, a, b, e0);
-                dq0 += a;
-                extra += g * e0;
-            }
-        }
-        if constexpr (ModelTraits<MODEL>::cplx_query) {
-            const float *e = HEAD ? et : eh;
-            Cplx de, dr;
-            query_bwd_cplx<MODEL, HEAD>(Cplx{e[u], e[T.d + u]}, Cplx{er[u], MODEL == MKB_COMPLEX ? er[T.d + u] : 0.f},
-                                        Cplx{dq0, dq1}, T.kd, de, dr);
-            atomicAdd(g_e + u, de.re);
-            atomicAdd(g_e + T.d + u, de.im);
-            atomicAdd(g_r + u, dr.re);
-            if constexpr (MODEL == MKB_COMPLEX) atomicAdd(g_r + T.d + u, dr.im);
-        } else {
-            const float a = HEAD ? er[u] : eh[u], b = HEAD ? et[u] : er[u];
-            float da, db;
-            query_bwd_real<MODEL, HEAD>(a, b, dq0, T.kd, da, db);
-            atomicAdd((HEAD ? g_r : g_e) + u, da);
-            atomicAdd((HEAD ? g_e : g_r) + u, db);
-        }
-    }
-    if constexpr (MODEL == MKB_PROTATE) {
-        extra = wave_sum(extra);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = extra;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float s = 0.f;
-            for (int w = 0; w < kWaves; ++w) s += red[w];
-            atomicAdd(G.g_modulus, -s);
-        }
-    }
-}
-
-// dx pass: workgroup = kChunkPairs consecutive pairs of the candidate-sorted pair list
+// dx pass of the two-pass backward: workgroup = kChunkPairs consecutive pairs of the candidate-sorted pair list
 constexpr int kChunkPairs = 64;
 template <int MODEL, bool HEAD>
 __global__ __launch_bounds__(kBlock) void score_bwd_x_kernel(TablesDev T, mkb_grads_t G, const int *__restrict__ sorted_cand,
@@ -369,13 +251,15 @@ static int launch_bwd2(const TablesDev &T, const mkb_tables_t *tb, const mkb_gra
     hipLaunchKernelGGL(pair_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand, (int)n, k_in, v_in);
     MKB_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, k_in, k_out, v_in, v_out, (int)n, 0, bits, st));
     const unsigned chunks = (unsigned)((n + kChunkPairs - 1) / kChunkPairs);
+    static_assert(kBlock == 256, "query_build_kernel strides its row by 256 lanes");
+    const RowArgs qa = query_build_args(T.ent, T.rel, sample, Q, T.De, T.Dr, T.d, B, T.kd);
     if (head) {
-        hipLaunchKernelGGL((general_query_kernel<MODEL, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, sample, Q);
-        hipLaunchKernelGGL((score_bwd_q_kernel<MODEL, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
+        hipLaunchKernelGGL((query_build_kernel<MODEL, true>), dim3((unsigned)B), dim3(kBlock), 0, st, qa);
+        hipLaunchKernelGGL((score_bwd_kernel<MODEL, true, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
         hipLaunchKernelGGL((score_bwd_x_kernel<MODEL, true>), dim3(chunks), dim3(kBlock), 0, st, T, G, k_out, v_out, (int)n, K, Q, dscore);
     } else {
-        hipLaunchKernelGGL((general_query_kernel<MODEL, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, sample, Q);
-        hipLaunchKernelGGL((score_bwd_q_kernel<MODEL, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
+        hipLaunchKernelGGL((query_build_kernel<MODEL, false>), dim3((unsigned)B), dim3(kBlock), 0, st, qa);
+        hipLaunchKernelGGL((score_bwd_kernel<MODEL, false, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
         hipLaunchKernelGGL((score_bwd_x_kernel<MODEL, false>), dim3(chunks), dim3(kBlock), 0, st, T, G, k_out, v_out, (int)n, K, Q, dscore);
     }
     MKB_LAUNCH_CHECK();
@@ -400,9 +284,9 @@ static int launch_bwd(const TablesDev &T, const mkb_grads_t &G, const int64_t *s
                       int K, bool head, const float *dscore, hipStream_t st) {
     ProfScope ps(MKB_PROF_GENERAL_BWD, st);
     if (head)
-        hipLaunchKernelGGL((score_bwd_kernel<MODEL, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
+        hipLaunchKernelGGL((score_bwd_kernel<MODEL, true, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
     else
-        hipLaunchKernelGGL((score_bwd_kernel<MODEL, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
+        hipLaunchKernelGGL((score_bwd_kernel<MODEL, false, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }

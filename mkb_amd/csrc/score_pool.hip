@@ -2,6 +2,7 @@
 // mkb_pool_score_bwd).  The three tile kernels live in score_pool_kernels.h and are instantiated per model in
 // score_pool_<model>.hip (parallel compilation); see the header for the design.
 #include "score_pool_plan.h"
+#include "query_side.h"
 #include "gemm_mfma.h"
 
 #include <stdlib.h>
@@ -10,53 +11,9 @@
 namespace mkb {
 
 // ------------------------------------------------------------------------------------------------ row kernels
-struct RowArgs {
-    const float *ent, *rel;
-    const int64_t *sample;
-    float *Q;          // [B, De] out (build) / [nslices, B, De] dQ partials in (backward)
-    float *g_ent, *g_rel;
-    int64_t De, Dr;
-    int d, B, nslices;
-    float kd;
-    // GEMM route: depth[i] = one past the last pool position row i uses (cnt [B, P]); null = not wanted
-    const uint16_t *cnt;
-    int *depth;
-    int P;
-};
-
-// depth[i] for the GEMM route's "used pool depth" cuts (gemm_mfma.h): one workgroup per row scans the row's multiplicities
-__device__ __forceinline__ void row_depth_256(const uint16_t *__restrict__ cnt, int P, int64_t i, int *__restrict__ depth) {
-    __shared__ int s_dep[4];
-    int m = 0;
-    for (int p = threadIdx.x; p < P; p += 256)
-        if (cnt[i * P + p]) m = p + 1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) s_dep[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) depth[i] = max(max(s_dep[0], s_dep[1]), max(s_dep[2], s_dep[3]));
-}
-
-// Q[i] = query of row i (same math as the LDS staging of the general forward kernel, written to global)
-template <int MODEL, bool HEAD>
-__global__ __launch_bounds__(256) void query_build_kernel(RowArgs A) {
-    const int64_t i = blockIdx.x;
-    if (A.depth) row_depth_256(A.cnt, A.P, i, A.depth);
-    const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
-    const float *eh = A.ent + h * A.De, *er = A.rel + r * A.Dr, *et = A.ent + t * A.De;
-    float *q = A.Q + i * A.De;
-    if constexpr (ModelTraits<MODEL>::cplx_query) {
-        const float *e = HEAD ? et : eh;
-        for (int u = threadIdx.x; u < A.d; u += 256) {
-            Cplx qq = build_q_cplx<MODEL, HEAD>(Cplx{e[u], e[A.d + u]}, Cplx{er[u], MODEL == MKB_COMPLEX ? er[A.d + u] : 0.f}, A.kd);
-            q[u] = qq.re;
-            q[A.d + u] = qq.im;
-        }
-    } else {
-        for (int u = threadIdx.x; u < (int)A.De; u += 256)
-            q[u] = build_q_real<MODEL, HEAD>(HEAD ? er[u] : eh[u], HEAD ? et[u] : er[u], A.kd);
-    }
-}
+// One workgroup of 256 lanes per batch row.  What they know about a row's query -- operand rows, unit layout, build and chain --
+// is query_side.h's; the query build itself (query_build_kernel, RowArgs) is that header's kernel, the very code the general
+// path and the evaluation launch.
 
 // sum of the slice partials of dQ for N elements of one row: the loads of four slices x N elements are requested together
 // and added in slice order.  (A plain loop over a run-time slice count waits for every load before it issues the next: the
@@ -84,33 +41,19 @@ __device__ __forceinline__ void dq_slices_sum(const float *__restrict__ dq, int6
 template <int MODEL, bool HEAD>
 __global__ __launch_bounds__(256) void query_bwd_kernel(RowArgs A) {
     const int64_t i = blockIdx.x;
-    const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
-    const float *eh = A.ent + h * A.De, *er = A.rel + r * A.Dr, *et = A.ent + t * A.De;
+    const QueryRow R = query_row<MODEL>(A, A.sample, i);
     const float *dq = A.Q + i * A.De;
     const int64_t sstride = (int64_t)A.B * A.De;
-    float *g_e = A.g_ent + (HEAD ? t : h) * A.De;
-    float *g_r = A.g_rel + r * A.Dr;
-    if constexpr (ModelTraits<MODEL>::cplx_query) {
-        const float *e = HEAD ? et : eh;
-        for (int u = threadIdx.x; u < A.d; u += 256) {
-            Cplx de, dr;
-            float dqn[2];
-            dq_slices_sum<2>(dq, sstride, A.nslices, {u, A.d + u}, dqn);
-            query_bwd_cplx<MODEL, HEAD>(Cplx{e[u], e[A.d + u]}, Cplx{er[u], MODEL == MKB_COMPLEX ? er[A.d + u] : 0.f},
-                                        Cplx{dqn[0], dqn[1]}, A.kd, de, dr);
-            atomicAdd(g_e + u, de.re);
-            atomicAdd(g_e + A.d + u, de.im);
-            atomicAdd(g_r + u, dr.re);
-            if constexpr (MODEL == MKB_COMPLEX) atomicAdd(g_r + A.d + u, dr.im);
-        }
-    } else {
-        for (int u = threadIdx.x; u < (int)A.De; u += 256) {
-            float da, db, dqn[1];
-            dq_slices_sum<1>(dq, sstride, A.nslices, {u}, dqn);
-            query_bwd_real<MODEL, HEAD>(HEAD ? er[u] : eh[u], HEAD ? et[u] : er[u], dqn[0], A.kd, da, db);
-            atomicAdd((HEAD ? g_r : g_e) + u, da);
-            atomicAdd((HEAD ? g_e : g_r) + u, db);
-        }
+    float *g_e = A.g_ent + R.ent_id<HEAD>() * A.De;
+    float *g_r = A.g_rel + R.r * A.Dr;
+    for (int u = threadIdx.x; u < R.U; u += 256) {
+        constexpr int N = ModelTraits<MODEL>::cplx_query ? 2 : 1;  // floats per unit
+        Cplx de, dr;
+        float dqn[N];
+        if constexpr (N == 2) dq_slices_sum<2>(dq, sstride, A.nslices, {u, R.d + u}, dqn);
+        else dq_slices_sum<1>(dq, sstride, A.nslices, {u}, dqn);
+        query_unit_bwd<MODEL, HEAD>(R, u, dqn[0], dqn[N - 1], de, dr);  // (real models: dq1 is not read)
+        query_grad_atomic<MODEL, HEAD>(g_e, g_r, R.d, u, de, dr);
     }
 }
 
@@ -162,48 +105,39 @@ struct RowStepArgs {
     int grads_clear;
 };
 
-__device__ __forceinline__ float block_sum_256_row(float v, float *red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // positive score (mode None == tail-style formula against the true tail, pipeline.py:211) + Q for the negatives
 template <int MODEL, bool HEAD>
 __global__ __launch_bounds__(256) void row_fwd_kernel(RowStepArgs A) {
     __shared__ float red[4];
     const int64_t i = blockIdx.x;
-    const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
-
-    const float *eh = A.ent + h * A.De, *er = A.rel + r * A.Dr, *et = A.ent + t * A.De;
+    const QueryRow R = query_row<MODEL>(A, A.sample, i);
     float *q = A.Q + i * A.De;
     float acc = 0.f;
     if constexpr (ModelTraits<MODEL>::cplx_query) {
-        for (int u = threadIdx.x; u < A.d; u += 256) {
-            const Cplx ch{eh[u], eh[A.d + u]}, ct{et[u], et[A.d + u]};
-            const Cplx cr{er[u], MODEL == MKB_COMPLEX ? er[A.d + u] : 0.f};
-            const Cplx qp = build_q_cplx<MODEL, false>(ch, cr, A.kd);
-            const Cplx qn = HEAD ? build_q_cplx<MODEL, true>(ct, cr, A.kd) : qp;
+        for (int u = threadIdx.x; u < R.U; u += 256) {
+            const Cplx ch = ent_unit(R.eh, R.d, u), ct = ent_unit(R.et, R.d, u);
+            const Cplx cr = rel_unit<MODEL>(R.er, R.d, u);
+            const Cplx qp = query_of<MODEL, false>(ch, cr, A.kd);
+            const Cplx qn = HEAD ? query_of<MODEL, true>(ct, cr, A.kd) : qp;
             q[u] = qn.re;
             q[A.d + u] = qn.im;
             if constexpr (ModelTraits<MODEL>::cplx_pair) acc += pair_term_cmod(qp, ct);
             else acc += pair_term_real<MODEL, false>(qp.re, ct.re, A.kd) + pair_term_real<MODEL, false>(qp.im, ct.im, A.kd);
         }
     } else {
-        for (int u = threadIdx.x; u < (int)A.De; u += 256) {
-            const float vh = eh[u], vr = er[u], vt = et[u];
-            const float qp = build_q_real<MODEL, false>(vh, vr, A.kd);
-            q[u] = HEAD ? build_q_real<MODEL, true>(vr, vt, A.kd) : qp;
+        for (int u = threadIdx.x; u < R.U; u += 256) {
+            const float vh = R.eh[u], vr = R.er[u], vt = R.et[u];
+            const float qp = query_of<MODEL, false>(vh, vr, A.kd);
+            q[u] = HEAD ? query_of<MODEL, true>(vt, vr, A.kd) : qp;
             acc += pair_term_real<MODEL, false>(qp, vt, A.kd);
         }
     }
-    acc = block_sum_256_row(acc, red);
+    acc = block_sum_4waves(acc, red);
     if (threadIdx.x == 0) A.pos_score[i] = finish_score<MODEL>(acc, A.gamma, MODEL == MKB_PROTATE ? A.modulus[0] : 0.f);
     if (A.depth) row_depth_256(A.cnt, A.depth_P, i, A.depth);
     // housekeeping for the later kernels of the step, behind the row's own work (fire-and-forget stores)
     if (A.occ && threadIdx.x == 64) {  // (counted by the pooled forward / the loss kernel, read by the row backward)
-        A.occ[h] = 0; A.occ[t] = 0;
+        A.occ[R.h] = 0; A.occ[R.t] = 0;
         for (int64_t p = i; p < A.P; p += A.B) A.occ[A.pool[p]] = 0;
     }
     if (A.rel_copies > 1)  // the row backward's relation-gradient copies start from zero
@@ -228,14 +162,13 @@ __global__ __launch_bounds__(256) void row_bwd_kernel(RowStepArgs A) {
         return;
     }
     const int64_t i = (int64_t)blockIdx.x - A.dx.blocks - sc_blocks;
-    const int64_t h = A.sample[3 * i], r = A.sample[3 * i + 1], t = A.sample[3 * i + 2];
-    const float *eh = A.ent + h * A.De, *er = A.rel + r * A.Dr, *et = A.ent + t * A.De;
-    float *g_h = A.g_ent + h * A.De, *g_t = A.g_ent + t * A.De;
-    float *g_r = A.rel_copies > 1 ? A.rel_rep + ((int64_t)(i % A.rel_copies) * A.n_rel + r) * A.Dr : A.g_rel + r * A.Dr;
+    const QueryRow R = query_row<MODEL>(A, A.sample, i);
+    float *g_h = A.g_ent + R.h * A.De, *g_t = A.g_ent + R.t * A.De;
+    float *g_r = A.rel_copies > 1 ? A.rel_rep + ((int64_t)(i % A.rel_copies) * A.n_rel + R.r) * A.Dr : A.g_rel + R.r * A.Dr;
     const float *dq = A.dQ + i * A.De;
     const int64_t sstride = (int64_t)A.B * A.De;
     const float gp = A.dpos[i];
-    const bool own_h = A.occ && A.occ[h] == 1, own_t = A.occ && A.occ[t] == 1;  // workgroup-uniform
+    const bool own_h = A.occ && A.occ[R.h] == 1, own_t = A.occ && A.occ[R.t] == 1;  // workgroup-uniform
     // rows one workgroup alone writes: a plain store when the row is known to be all-zero (grads_clear), else read-modify-
     // write; shared rows: one fp32 atomic per element
     const bool st_h = own_h && A.grads_clear, st_t = own_t && A.grads_clear;  // workgroup-uniform
@@ -244,11 +177,11 @@ __global__ __launch_bounds__(256) void row_bwd_kernel(RowStepArgs A) {
     const float modulus = (MODEL == MKB_PROTATE) ? A.modulus[0] : 0.f;
     float extra = 0.f;
     if constexpr (ModelTraits<MODEL>::cplx_query) {
-        for (int u = threadIdx.x; u < A.d; u += 256) {
-            const Cplx ch{eh[u], eh[A.d + u]}, ct{et[u], et[A.d + u]};
-            const Cplx cr{er[u], MODEL == MKB_COMPLEX ? er[A.d + u] : 0.f};
+        for (int u = threadIdx.x; u < R.U; u += 256) {
+            const Cplx ch = ent_unit(R.eh, R.d, u), ct = ent_unit(R.et, R.d, u);
+            const Cplx cr = rel_unit<MODEL>(R.er, R.d, u);
             // positive pair: q = h (x) rot, candidate = t
-            const Cplx qp = build_q_cplx<MODEL, false>(ch, cr, A.kd);
+            const Cplx qp = query_of<MODEL, false>(ch, cr, A.kd);
             Cplx dqp, dxp;
             if constexpr (ModelTraits<MODEL>::cplx_pair) {
                 pair_bwd_cmod(qp, ct, gp, dqp, dxp);
@@ -258,12 +191,12 @@ __global__ __launch_bounds__(256) void row_bwd_kernel(RowStepArgs A) {
                 pair_bwd_real<MODEL, false>(qp.im, ct.im, gp, A.kd, modulus, dqp.im, dxp.im, e0);
             }
             Cplx dh, dr, dt = dxp, de, dr2;
-            query_bwd_cplx<MODEL, false>(ch, cr, dqp, A.kd, dh, dr);
+            query_chain<MODEL, false>(ch, cr, dqp, A.kd, dh, dr);
             // negative path: q = conj(rot) (x) t (head-batch) or h (x) rot (tail-batch)
             float dqs[2];
             dq_slices_sum<2>(dq, sstride, A.nslices, {u, A.d + u}, dqs);
             const Cplx dqn{dqs[0], dqs[1]};
-            query_bwd_cplx<MODEL, HEAD>(HEAD ? ct : ch, cr, dqn, A.kd, de, dr2);
+            query_chain<MODEL, HEAD>(HEAD ? ct : ch, cr, dqn, A.kd, de, dr2);
             if constexpr (HEAD) { dt.re += de.re; dt.im += de.im; } else { dh.re += de.re; dh.im += de.im; }
             dr.re += dr2.re; dr.im += dr2.im;
             add_h(u, dh.re); add_h(A.d + u, dh.im);
@@ -272,25 +205,26 @@ __global__ __launch_bounds__(256) void row_bwd_kernel(RowStepArgs A) {
             if constexpr (MODEL == MKB_COMPLEX) atomicAdd(g_r + A.d + u, dr.im);
         }
     } else {
-        for (int u = threadIdx.x; u < (int)A.De; u += 256) {
-            const float vh = eh[u], vr = er[u], vt = et[u];
-            const float qp = build_q_real<MODEL, false>(vh, vr, A.kd);
+        for (int u = threadIdx.x; u < R.U; u += 256) {
+            const float vh = R.eh[u], vr = R.er[u], vt = R.et[u];
+            const float qp = query_of<MODEL, false>(vh, vr, A.kd);
             float dqp, dxp, e0 = 0.f;
             pair_bwd_real<MODEL, false>(qp, vt, gp, A.kd, modulus, dqp, dxp, e0);
             extra += gp * e0;
             float dh, dr, dt = dxp;
-            query_bwd_real<MODEL, false>(vh, vr, dqp, A.kd, dh, dr);  // tail-style: a = h, b = r
-            float da, db, dqs[1];
+            query_chain<MODEL, false>(vh, vr, dqp, A.kd, dh, dr);
+            float de, dr2, dqs[1];
             dq_slices_sum<1>(dq, sstride, A.nslices, {u}, dqs);
-            query_bwd_real<MODEL, HEAD>(HEAD ? vr : vh, HEAD ? vt : vr, dqs[0], A.kd, da, db);
-            if constexpr (HEAD) { dr += da; dt += db; } else { dh += da; dr += db; }
+            query_chain<MODEL, HEAD>(HEAD ? vt : vh, vr, dqs[0], A.kd, de, dr2);
+            if constexpr (HEAD) dt += de; else dh += de;
+            dr += dr2;
             add_h(u, dh);
             atomicAdd(g_r + u, dr);
             add_t(u, dt);
         }
     }
     if constexpr (MODEL == MKB_PROTATE) {  // d score / d modulus = - sum_k |sin z| for the positive pair
-        extra = block_sum_256_row(extra, red);
+        extra = block_sum_4waves(extra, red);
         if (threadIdx.x == 0) atomicAdd(A.g_modulus, -extra);
     }
     if (A.loss_out && i == A.B - 1)  // the per-row loss terms were written by an earlier kernel

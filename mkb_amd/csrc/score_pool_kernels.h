@@ -839,17 +839,12 @@ constexpr int kBwd1Waves = 16;
 constexpr int kChunkStride = 1;                         // chunks (= phases) between a wave and the next wave of the chain
 constexpr int kChunks = kBwd1Waves * kChunkStride;      // chunks per block = phases per tile
 
-template <int NC> struct AccVec;
-template <> struct AccVec<1> { typedef float type; };
-template <> struct AccVec<2> { typedef float2 type; };
-template <> struct AccVec<4> { typedef float4 type; };
-
 template <int MODEL, bool HEAD, int KPT, bool DENSE>  // DENSE: dense pass + chain-free fringe (A.dense_lanes > 0); else the general pass
 __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) {
     constexpr bool CP = ModelTraits<MODEL>::cplx_pair;
     constexpr int NC = KPT * (CP ? 2 : 1);  // floats per lane and position
     constexpr int NW = kBwd1Waves, WG = NW * 64;
-    typedef typename AccVec<NC>::type acc_t;
+    typedef typename AccVecOf<NC>::type acc_t;
     extern __shared__ __attribute__((aligned(16))) int lds1[];
     const int halves = A.pb_halves, cap = halves * 64;  // halves in {1, 2, 4, 8}
     // accumulator slots: all of the block's (general pass), or the dense lanes of every half only -- the fringe's dx never
