@@ -23,10 +23,21 @@
 //               instead of exchanging [B,P,D] products through memory or per-pair atomics: VALU is cheaper.
 // KPT = 2 / 4 lanes load float2 / float4 and give the compiler pairs of units to pack into v_pk_* ops.
 // VALU-bound by design (RotatE: one v_sqrt / v_rsq per (row, slot, complex dim)).
+//
+// Two more backward kernels follow them: pool_bwd_wave (small problems: one wave per tile, no LDS) and pool_bwd1 (the
+// single-pass backward: every pair term evaluated once for both gradients; its own header comment has the phases).
+// What the backward kernels share is written once:
+//   the pair step   "given q, x and the seed g, add into dq and / or dx" for a lane's KPT units, unit by unit: pair_step.h.
+//                   RotatE's packed forms (pair_bwd_cmod2 in the two-pass bodies, pair_bwd_cmod2_both / _both_x2 in pool_bwd1)
+//                   stay written out where they are used: moved into a helper they compile to different code, and
+//                   pool_bwd1_kernel<RotatE, ., 2, .> has no register to spare (profiles/r09_pair_step_disassembly.txt);
+//   the lane packet a lane's units of one row as one 4 / 8 / 16-byte access: packet_pack / packet_unpack / packet_add
+//                   below, next to AccVecOf.
 #pragma once
 #include <type_traits>
 #include "common.h"
 #include "model_math.h"
+#include "pair_step.h"
 
 namespace mkb {
 
@@ -148,6 +159,45 @@ template <int N> struct AccVecOf;
 template <> struct AccVecOf<1> { typedef float type; };
 template <> struct AccVecOf<2> { typedef float2 type; };
 template <> struct AccVecOf<4> { typedef float4 type; };
+
+// The lane packet of the single-pass backward: a lane's KPT units of one row as ONE LDS / global access of NC = KPT (real
+// models) or 2 * KPT (RotatE) floats, component order [re/real KPT][im KPT].  In registers the same units are the pair
+// (a0[KPT], a1[KPT]) = (re / real parts, im parts; a1 is all zeros for the real models).  Row images, parked query rows, the
+// LDS accumulator and the dx partial buffer all hold packets: the layout is written here and nowhere else.
+template <bool CP, int KPT>
+__device__ __forceinline__ typename AccVecOf<KPT * (CP ? 2 : 1)>::type packet_pack(const float (&a0)[KPT], const float (&a1)[KPT]) {
+    constexpr int NC = KPT * (CP ? 2 : 1);
+    typename AccVecOf<NC>::type v;
+    if constexpr (NC == 1) v = a0[0];
+    else if constexpr (NC == 2 && !CP) { v.x = a0[0]; v.y = a0[1]; }
+    else if constexpr (NC == 2) { v.x = a0[0]; v.y = a1[0]; }
+    else if constexpr (NC == 4 && !CP) { v.x = a0[0]; v.y = a0[1]; v.z = a0[KPT - 2]; v.w = a0[KPT - 1]; }
+    else { v.x = a0[0]; v.y = a0[1]; v.z = a1[0]; v.w = a1[1]; }
+    return v;
+}
+
+template <bool CP, int KPT>
+__device__ __forceinline__ void packet_unpack(const typename AccVecOf<KPT * (CP ? 2 : 1)>::type v, float (&a0)[KPT], float (&a1)[KPT]) {
+    constexpr int NC = KPT * (CP ? 2 : 1);
+    if constexpr (NC == 1) { a0[0] = v; a1[0] = 0.f; }
+    else if constexpr (NC == 2 && !CP) { a0[0] = v.x; a0[1] = v.y; a1[0] = 0.f; a1[1] = 0.f; }
+    else if constexpr (NC == 2) { a0[0] = v.x; a1[0] = v.y; }
+    else if constexpr (NC == 4 && !CP) {
+        a0[0] = v.x; a0[1] = v.y; a0[KPT - 2] = v.z; a0[KPT - 1] = v.w;
+#pragma unroll
+        for (int k = 0; k < KPT; ++k) a1[k] = 0.f;
+    } else { a0[0] = v.x; a0[1] = v.y; a1[0] = v.z; a1[1] = v.w; }
+}
+
+template <bool CP, int KPT>
+__device__ __forceinline__ void packet_add(typename AccVecOf<KPT * (CP ? 2 : 1)>::type &v, const float (&a0)[KPT], const float (&a1)[KPT]) {
+    constexpr int NC = KPT * (CP ? 2 : 1);
+    if constexpr (NC == 1) v += a0[0];
+    else if constexpr (NC == 2 && !CP) { v.x += a0[0]; v.y += a0[1]; }
+    else if constexpr (NC == 2) { v.x += a0[0]; v.y += a1[0]; }
+    else if constexpr (NC == 4 && !CP) { v.x += a0[0]; v.y += a0[1]; v.z += a0[KPT - 2]; v.w += a0[KPT - 1]; }
+    else { v.x += a0[0]; v.y += a0[1]; v.z += a1[0]; v.w += a1[1]; }
+}
 
 // Load this lane's KPT consecutive units of a row: UNCONDITIONAL vector load from a clamped offset, then a select.
 // (A predicated load becomes a branch whose join makes the compiler wait for the data immediately, which
@@ -488,20 +538,8 @@ __device__ __forceinline__ void pool_bwd_q_body(const PoolArgs &A, const int blo
                                 dq0[r][v] = ar.x; dq0[r][v + 1] = ar.y;
                                 dq1[r][v] = ai.x; dq1[r][v + 1] = ai.y;
                             }
-                        } else
-#pragma unroll
-                        for (int v = 0; v < KPT; ++v) {
-                            if constexpr (CP) {
-                                Cplx dq, dx;
-                                pair_bwd_cmod(Cplx{q0[r][v], q1[r][v]}, Cplx{x0[v], x1[v]}, g[r], dq, dx);
-                                dq0[r][v] += dq.re;
-                                dq1[r][v] += dq.im;
-                            } else {
-                                float dq, dx, e0 = 0.f;
-                                pair_bwd_real<MODEL, HEAD>(q0[r][v], x0[v], g[r], A.kd, modulus, dq, dx, e0);
-                                dq0[r][v] += dq;
-                                extra += g[r] * e0;
-                            }
+                        } else {
+                            pair_step_one<MODEL, HEAD, KPT, false>(q0[r], q1[r], x0, x1, g[r], A.kd, modulus, dq0[r], dq1[r], extra);
                         }
                     }
                 }
@@ -602,6 +640,7 @@ __device__ __forceinline__ void pool_bwd_x_body(const PoolArgs &A, const int blo
 
     MKB_TRACE_T(tr_t1);
     const float modulus = (MODEL == MKB_PROTATE) ? A.modulus[0] : 0.f;
+    float extra_unused = 0.f;  // (pRotatE's modulus gradient is the dq pass's: what the pair step adds here is never read)
 
     float qr0[kRing][KPT], qr1[kRing][KPT];
     auto load_q = [&](int j, float (&d0)[KPT], float (&d1)[KPT]) {
@@ -641,19 +680,8 @@ __device__ __forceinline__ void pool_bwd_x_body(const PoolArgs &A, const int blo
                                 dx0[t][v] = ar.x; dx0[t][v + 1] = ar.y;
                                 dx1[t][v] = ai.x; dx1[t][v + 1] = ai.y;
                             }
-                        } else
-#pragma unroll
-                        for (int v = 0; v < KPT; ++v) {
-                            if constexpr (CP) {
-                                Cplx dq, dx;
-                                pair_bwd_cmod(Cplx{q0[v], q1[v]}, Cplx{x0[t][v], x1[t][v]}, g[t], dq, dx);
-                                dx0[t][v] += dx.re;
-                                dx1[t][v] += dx.im;
-                            } else {
-                                float dq, dx, e0 = 0.f;
-                                pair_bwd_real<MODEL, HEAD>(q0[v], x0[t][v], g[t], A.kd, modulus, dq, dx, e0);
-                                dx0[t][v] += dx;
-                            }
+                        } else {
+                            pair_step_one<MODEL, HEAD, KPT, true>(q0, q1, x0[t], x1[t], g[t], A.kd, modulus, dx0[t], dx1[t], extra_unused);
                         }
                     }
                 }
@@ -777,21 +805,7 @@ __global__ __launch_bounds__(64) void pool_bwd_wave_kernel(PoolArgs A) {
             for (int r = 0; r < TI; ++r) {
                 const float g = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(gv[r]), j));
                 if ((__float_as_uint(g) << 1) == 0u) continue;  // (wave-uniform)
-#pragma unroll
-                for (int v = 0; v < KPT; ++v) {
-                    if constexpr (CP) {
-                        Cplx dq, dx;
-                        pair_bwd_cmod(Cplx{q0[r][v], q1[r][v]}, Cplx{x0[v], x1[v]}, g, dq, dx);
-                        dq0[r][v] += dq.re; dq1[r][v] += dq.im;
-                        dx0[v] += dx.re; dx1[v] += dx.im;
-                    } else {
-                        float dq, dx, e0 = 0.f;
-                        pair_bwd_real<MODEL, HEAD>(q0[r][v], x0[v], g, A.kd, modulus, dq, dx, e0);
-                        dq0[r][v] += dq;
-                        dx0[v] += dx;
-                        extra += g * e0;
-                    }
-                }
+                pair_step<MODEL, HEAD, KPT>(q0[r], q1[r], x0, x1, g, A.kd, modulus, dq0[r], dq1[r], dx0, dx1, extra);
             }
             if (u0 < NU) {
                 float *grow = A.g_ent + xoff;
@@ -829,15 +843,8 @@ __global__ __launch_bounds__(64) void pool_bwd_wave_kernel(PoolArgs A) {
 //   flush     = after the last phase the LDS array goes to the table gradient rows (one fp32 atomic per element and row
 //               group: 8 per element at the headline shape, as before); dq partial stored once per wave and block.
 // Nothing is recomputed: RotatE 9 packed ops + 2 v_rsq per two complex dims (the two-pass kernels: 14 + 4).
-#ifndef MKB_HANDON_PRIO
-#define MKB_HANDON_PRIO 0
-#endif
-#ifndef MKB_BWD1_Q_EARLY
-#define MKB_BWD1_Q_EARLY 1
-#endif
 constexpr int kBwd1Waves = 16;
-constexpr int kChunkStride = 1;                         // chunks (= phases) between a wave and the next wave of the chain
-constexpr int kChunks = kBwd1Waves * kChunkStride;      // chunks per block = phases per tile
+constexpr int kChunks = kBwd1Waves;  // chunks per block = phases per tile: one chunk per wave and phase
 
 template <int MODEL, bool HEAD, int KPT, bool DENSE>  // DENSE: dense pass + chain-free fringe (A.dense_lanes > 0); else the general pass
 __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) {
@@ -876,10 +883,10 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
 
     // The wave's first row tile: its 8 query-row slices are requested at ENTRY, ahead of the pool ids and the candidate-row images
     // below (two dependent round trips) and the barrier behind them -- round 6: they used to be requested behind that barrier, a
-    // third round trip in series in a workgroup that owns its CU alone (nothing else hides it).  MKB_BWD1_Q_EARLY=0: A/B builds.
+    // third round trip in series in a workgroup that owns its CU alone (nothing else hides it).
     const int row_tiles = (A.B + TI - 1) / TI;
     float q0[TI][KPT], q1[TI][KPT];
-    if constexpr (MKB_BWD1_Q_EARLY != 0) {
+    {
         const int i00 = ((rg * A.tiles_per_wave) * NW + wave) * TI;
         if (i00 < A.B) {
 #pragma unroll
@@ -923,13 +930,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
 #pragma unroll
                     for (int v = 0; v < KPT; ++v) { xa[c][v] = 0.f; xb[c][v] = 0.f; }
                 }
-                acc_t v;
-                if constexpr (NC == 1) v = xa[c][0];
-                else if constexpr (NC == 2 && !CP) { v.x = xa[c][0]; v.y = xa[c][1]; }
-                else if constexpr (NC == 2) { v.x = xa[c][0]; v.y = xb[c][0]; }
-                else if constexpr (NC == 4 && !CP) { v.x = xa[c][0]; v.y = xa[c][1]; v.z = xa[c][KPT - 2]; v.w = xa[c][KPT - 1]; }
-                else { v.x = xa[c][0]; v.y = xa[c][1]; v.z = xb[c][0]; v.w = xb[c][1]; }
-                s_x[(size_t)(h0 * A.dense_lanes + j0) * 64 + lane] = v;
+                s_x[(size_t)(h0 * A.dense_lanes + j0) * 64 + lane] = packet_pack<CP, KPT>(xa[c], xb[c]);
             }
         }
     }
@@ -942,7 +943,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
         const bool have = tile < row_tiles;  // (wave-uniform; a wave without a tile only keeps the barriers)
         const int i0 = tile * TI;
         float dq0[TI][KPT], dq1[TI][KPT];
-        if (MKB_BWD1_Q_EARLY == 0 || t > 0) {  // (tile 0's rows were requested at entry)
+        if (t > 0) {  // (tile 0's rows were requested at entry)
 #pragma unroll
             for (int r = 0; r < TI; ++r) {
                 // (all eight rows' loads first, the selects behind them: a select next to its load makes the wave wait there, and the
@@ -985,7 +986,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
             // successor -- the phase in which the two own the same chunk.)
             if (lane == 0) __hip_atomic_store(&s_done[wave], finished, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             MKB_TRACE_ONLY(const unsigned long long th0 = __builtin_readcyclecounter();)
-            while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_done[pred], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < finished - (kChunkStride - 1))
+            while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_done[pred], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < finished)
                 __builtin_amdgcn_s_sleep(1);
             asm volatile("" ::: "memory");
             MKB_TRACE_ONLY(tr_hand += __builtin_readcyclecounter() - th0;)
@@ -994,7 +995,8 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
             // time (per-wave trace: half of every wave's loop time was hand-off wait) and a lone wave cannot fill the VALU.
             // A wave that is ahead of a SIMD mate (waves w, w+4, w+8, w+12 share a SIMD) drops to priority 0, the others
             // run at 3: the four stay within a phase of each other and interleave instruction by instruction.
-#if MKB_HANDON_PRIO == 0  // (A/B builds, tools/kbench.py: 1 = no priority changes at all, 2 = a static priority by wave age, set once)
+            // (Measured against no priority changes at all and against a static priority by wave age, set once: this dynamic
+            // rule won -- profiles/r06_ab_experiments.txt.)
             int behind = 0x3fffffff;
 #pragma unroll
             for (int k = 1; k < 4; ++k)
@@ -1002,13 +1004,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                                                                                        __HIP_MEMORY_SCOPE_WORKGROUP)));
             if (finished > behind) __builtin_amdgcn_s_setprio(0);
             else __builtin_amdgcn_s_setprio(3);
-#endif
         };
-#if MKB_HANDON_PRIO == 2
-        if (wave >= 12) __builtin_amdgcn_s_setprio(3);
-        else if (wave >= 8) __builtin_amdgcn_s_setprio(2);
-        else if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
         if constexpr (DENSE) {
             // Dense pass.  In phase ph the wave owns chunk (wave + ph) mod 16 = lanes l0, l0 + cph, ... of half h; the first
             // nd = dense_lanes / cph of them are dense positions.  All eight rows take the pair body unconditionally (a row that
@@ -1026,7 +1022,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
             const float *Gt = A.G + (((int64_t)tile * npb + pb) * halves) * 512;
             v8f gL = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             auto slot_of = [&](int ph_, int k_, int &p_, int &ds_) {
-                const int c = (kChunkStride * wave + ph_) & (kChunks - 1);
+                const int c = (wave + ph_) & (kChunks - 1);
                 const int h_ = c >> lcph, j_ = (c & (cph - 1)) + (k_ << lcph);
                 p_ = pb + npb * (j_ * halves + h_);
                 ds_ = h_ * A.dense_lanes + j_;  // slot of the (dense-only) LDS accumulator
@@ -1067,17 +1063,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
             for (int ph = 0; ph < kChunks; ++ph) {
                 for (int k = 0; k < nd; ++k) {
                     float x0[KPT], x1[KPT], g[TI];
-                    {
-                        const acc_t xv = xv_n;  // (read from LDS a position ago; lanes past the row's end hold 0)
-                        if constexpr (NC == 1) { x0[0] = xv; x1[0] = 0.f; }
-                        else if constexpr (NC == 2 && !CP) { x0[0] = xv.x; x0[1] = xv.y; x1[0] = 0.f; x1[1] = 0.f; }
-                        else if constexpr (NC == 2) { x0[0] = xv.x; x1[0] = xv.y; }
-                        else if constexpr (NC == 4 && !CP) {
-                            x0[0] = xv.x; x0[1] = xv.y; x0[KPT - 2] = xv.z; x0[KPT - 1] = xv.w;
-#pragma unroll
-                            for (int v = 0; v < KPT; ++v) x1[v] = 0.f;
-                        } else { x0[0] = xv.x; x0[1] = xv.y; x1[0] = xv.z; x1[1] = xv.w; }
-                    }
+                    packet_unpack<CP, KPT>(xv_n, x0, x1);  // (read from LDS a position ago; lanes past the row's end hold 0)
 #pragma unroll
                     for (int r = 0; r < TI; ++r) g[r] = gL[r];  // (rows past B: their seeds are written as 0 by the producers of G)
                     acc_t *slot = s_dx + (size_t)dslot_n * 64 + lane;
@@ -1109,28 +1095,10 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                     } else {
 #pragma unroll
                         for (int r = 0; r < TI; ++r)
-#pragma unroll
-                            for (int v = 0; v < KPT; ++v) {
-                                if constexpr (CP) {
-                                    Cplx dq, dx;
-                                    pair_bwd_cmod(Cplx{q0[r][v], q1[r][v]}, Cplx{x0[v], x1[v]}, g[r], dq, dx);
-                                    dq0[r][v] += dq.re; dq1[r][v] += dq.im;
-                                    dx0[v] += dx.re; dx1[v] += dx.im;
-                                } else {
-                                    float dq, dx, e0 = 0.f;
-                                    pair_bwd_real<MODEL, HEAD>(q0[r][v], x0[v], g[r], A.kd, modulus, dq, dx, e0);
-                                    dq0[r][v] += dq;
-                                    dx0[v] += dx;
-                                    extra += g[r] * e0;
-                                }
-                            }
+                            pair_step<MODEL, HEAD, KPT>(q0[r], q1[r], x0, x1, g[r], A.kd, modulus, dq0[r], dq1[r], dx0, dx1, extra);
                     }
                     acc_t upd = *slot;
-                    if constexpr (NC == 1) upd += dx0[0];
-                    else if constexpr (NC == 2 && !CP) { upd.x += dx0[0]; upd.y += dx0[1]; }
-                    else if constexpr (NC == 2) { upd.x += dx0[0]; upd.y += dx1[0]; }
-                    else if constexpr (NC == 4 && !CP) { upd.x += dx0[0]; upd.y += dx0[1]; upd.z += dx0[2]; upd.w += dx0[3]; }
-                    else { upd.x += dx0[0]; upd.y += dx0[1]; upd.z += dx1[0]; upd.w += dx1[1]; }
+                    packet_add<CP, KPT>(upd, dx0, dx1);
                     *slot = upd;
                     swait();
                 }
@@ -1229,23 +1197,8 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                                 dq0[r][0] = arA.x; dq0[r][1] = arA.y; dq1[r][0] = aiA.x; dq1[r][1] = aiA.y;
                                 dq0[r + 1][0] = arB.x; dq0[r + 1][1] = arB.y; dq1[r + 1][0] = aiB.x; dq1[r + 1][1] = aiB.y;
                             } else {
-#pragma unroll
-                                for (int rr = r; rr < r + 2; ++rr) {
-                                    const float gr = rr == r ? gA : gB;
-#pragma unroll
-                                    for (int v = 0; v < KPT; ++v) {
-                                        if constexpr (CP) {
-                                            Cplx dq, dx;
-                                            pair_bwd_cmod(Cplx{q0[rr][v], q1[rr][v]}, Cplx{x0[v], x1[v]}, gr, dq, dx);
-                                            dq0[rr][v] += dq.re; dq1[rr][v] += dq.im;
-                                        } else {
-                                            float dq, dx, e0 = 0.f;
-                                            pair_bwd_real<MODEL, HEAD>(q0[rr][v], x0[v], gr, A.kd, modulus, dq, dx, e0);
-                                            dq0[rr][v] += dq;
-                                            extra += gr * e0;
-                                        }
-                                    }
-                                }
+                                pair_step<MODEL, HEAD, KPT>(q0[r], q1[r], x0, x1, gA, A.kd, modulus, dq0[r], dq1[r], dx0, dx1, extra);
+                                pair_step<MODEL, HEAD, KPT>(q0[r + 1], q1[r + 1], x0, x1, gB, A.kd, modulus, dq0[r + 1], dq1[r + 1], dx0, dx1, extra);
                             }
                         }
                     }
@@ -1266,7 +1219,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
         // not matter.)  Candidate rows are requested kRing1 positions ahead, across phase boundaries: x is read-only, only
         // the LDS update has to wait for its phase.
         for (int ph0 = 0; ph0 < kChunks;) {
-            const int c0 = (kChunkStride * wave + ph0) & (kChunks - 1);
+            const int c0 = (wave + ph0) & (kChunks - 1);
             const int h = c0 / cph, l00 = c0 - h * cph;
             const int len = min(kChunks - ph0, cph - l00), ph1 = ph0 + len;  // phases [ph0, ph1): chunk lane offsets l00, l00 + 1, ...
             MKB_TRACE_ONLY(const unsigned long long ts0 = __builtin_readcyclecounter();)
@@ -1363,21 +1316,8 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                                 dx0[v] = br.x; dx0[v + 1] = br.y;
                                 dx1[v] = bi.x; dx1[v + 1] = bi.y;
                             }
-                        } else
-#pragma unroll
-                        for (int v = 0; v < KPT; ++v) {
-                            if constexpr (CP) {
-                                Cplx dq, dx;
-                                pair_bwd_cmod(Cplx{q0[r][v], q1[r][v]}, Cplx{x0[v], x1[v]}, g[r], dq, dx);
-                                dq0[r][v] += dq.re; dq1[r][v] += dq.im;
-                                dx0[v] += dx.re; dx1[v] += dx.im;
-                            } else {
-                                float dq, dx, e0 = 0.f;
-                                pair_bwd_real<MODEL, HEAD>(q0[r][v], x0[v], g[r], A.kd, modulus, dq, dx, e0);
-                                dq0[r][v] += dq;
-                                dx0[v] += dx;
-                                extra += g[r] * e0;
-                            }
+                        } else {
+                            pair_step<MODEL, HEAD, KPT>(q0[r], q1[r], x0, x1, g[r], A.kd, modulus, dq0[r], dq1[r], dx0, dx1, extra);
                         }
                     };
 #pragma unroll
@@ -1403,13 +1343,9 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                         if ((__float_as_uint(g[r + 1]) << 1) != 0u) one_row(r + 1);
                     }
                     // this wave owns the chunk during the phase: plain read-modify-write (read late: 4 VGPRs less across the
-                    // rows).  Component order: [re/real KPT][im KPT]
+                    // rows)
                     acc_t upd = *slot;
-                    if constexpr (NC == 1) upd += dx0[0];
-                    else if constexpr (NC == 2 && !CP) { upd.x += dx0[0]; upd.y += dx0[1]; }
-                    else if constexpr (NC == 2) { upd.x += dx0[0]; upd.y += dx1[0]; }
-                    else if constexpr (NC == 4 && !CP) { upd.x += dx0[0]; upd.y += dx0[1]; upd.z += dx0[2]; upd.w += dx0[3]; }
-                    else { upd.x += dx0[0]; upd.y += dx0[1]; upd.z += dx1[0]; upd.w += dx1[1]; }
+                    packet_add<CP, KPT>(upd, dx0, dx1);
                     *slot = upd;
                 }
             }
@@ -1444,13 +1380,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                 __syncthreads();  // the accumulator has been read out
 #pragma unroll
                 for (int r = 0; r < TI; ++r) {
-                    acc_t v;
-                    if constexpr (NC == 1) v = q0[r][0];
-                    else if constexpr (NC == 2 && !CP) { v.x = q0[r][0]; v.y = q0[r][1]; }
-                    else if constexpr (NC == 2) { v.x = q0[r][0]; v.y = q1[r][0]; }
-                    else if constexpr (NC == 4 && !CP) { v.x = q0[r][0]; v.y = q0[r][1]; v.z = q0[r][KPT - 2]; v.w = q0[r][KPT - 1]; }
-                    else { v.x = q0[r][0]; v.y = q0[r][1]; v.z = q1[r][0]; v.w = q1[r][1]; }
-                    s_q[(size_t)(wave * TI + r) * 64 + lane] = v;  // (a wave without a tile parks zeros)
+                    s_q[(size_t)(wave * TI + r) * 64 + lane] = packet_pack<CP, KPT>(q0[r], q1[r]);  // (a wave without a tile parks zeros)
                 }
             }
         }
@@ -1466,7 +1396,6 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
         __syncthreads();
         MKB_TRACE_ONLY(const unsigned long long tf0 = __builtin_readcyclecounter();)
         constexpr int NB = 4;  // rows per batch: SMALL on purpose -- this code runs once per launch, and every 64 bytes of it are an instruction-cache miss the first time (a 16-row batch, unrolled, cost more in cold code than it saved in round trips)
-        const int row_tiles2 = (A.B + TI - 1) / TI;
         const unsigned long long fmask = A.dense_lanes >= 64 ? 0ull : ~0ull << A.dense_lanes;
         int n_used = 0;
         for (int h = 0; h < halves; ++h) n_used += __popcll(s_used[h] & fmask);
@@ -1496,7 +1425,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
             n_id = s_ids[n_h * 64 + n_j];
             load_units_raw<CP, KPT>(A.ent + n_id * A.De, A.d, NU, u0, nx0, nx1);  // (lanes past the row's end: never read back)
             n_gsx = 0.f; n_gsy = 0.f;
-            if (tile_l0 < row_tiles2) {
+            if (tile_l0 < row_tiles) {
                 const float2 gs = *reinterpret_cast<const float2 *>(A.G + ((((int64_t)tile_l0 * npb + pb) * halves + n_h) * 64 + n_j) * 8 + (lane & 3) * 2);
                 n_gsx = gs.x; n_gsy = gs.y;
             }
@@ -1533,7 +1462,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                 float vx = gsx, vy = gsy;
                 if (t2 > 0) {
                     vx = 0.f; vy = 0.f;
-                    if (tile_l < row_tiles2) {
+                    if (tile_l < row_tiles) {
                         const float2 gs = *reinterpret_cast<const float2 *>(A.G + ((((int64_t)tile_l * npb + pb) * halves + h) * 64 + j) * 8 + (lane & 3) * 2);
                         vx = gs.x; vy = gs.y;
                     }
@@ -1563,17 +1492,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                         }
                         if (A.tiles_per_wave == 1) {  // parked in LDS by the rows' owners: sixteen reads in flight
 #pragma unroll
-                            for (int c = 0; c < NB; ++c) {
-                                const acc_t qv = s_q[(size_t)li[c] * 64 + lane];
-                                if constexpr (NC == 1) { qa0[c][0] = qv; qa1[c][0] = 0.f; }
-                                else if constexpr (NC == 2 && !CP) { qa0[c][0] = qv.x; qa0[c][1] = qv.y; qa1[c][0] = 0.f; qa1[c][1] = 0.f; }
-                                else if constexpr (NC == 2) { qa0[c][0] = qv.x; qa1[c][0] = qv.y; }
-                                else if constexpr (NC == 4 && !CP) {
-                                    qa0[c][0] = qv.x; qa0[c][1] = qv.y; qa0[c][KPT - 2] = qv.z; qa0[c][KPT - 1] = qv.w;
-#pragma unroll
-                                    for (int v = 0; v < KPT; ++v) qa1[c][v] = 0.f;
-                                } else { qa0[c][0] = qv.x; qa0[c][1] = qv.y; qa1[c][0] = qv.z; qa1[c][1] = qv.w; }
-                            }
+                            for (int c = 0; c < NB; ++c) packet_unpack<CP, KPT>(s_q[(size_t)li[c] * 64 + lane], qa0[c], qa1[c]);
                         } else {
 #pragma unroll
                             for (int c = 0; c < NB; ++c)
@@ -1591,20 +1510,11 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                                                        gr[c], gr[c + 1], arA, aiA, arB, aiB, br, bi);
                                 ax0[a4][0] = br.x; ax0[a4][1] = br.y; ax1[a4][0] = bi.x; ax1[a4][1] = bi.y;
                             } else {
+                                float nq0[KPT], nq1[KPT], ne = 0.f;  // (never read: the dq products are dead code here)
 #pragma unroll
-                                for (int cc = c; cc < c + 2; ++cc)
-#pragma unroll
-                                    for (int v = 0; v < KPT; ++v) {
-                                        if constexpr (CP) {
-                                            Cplx dq, dx;
-                                            pair_bwd_cmod(Cplx{qa0[cc][v], qa1[cc][v]}, Cplx{x0[v], x1[v]}, gr[cc], dq, dx);
-                                            ax0[a4][v] += dx.re; ax1[a4][v] += dx.im;
-                                        } else {
-                                            float dq, dx, e0 = 0.f;
-                                            pair_bwd_real<MODEL, HEAD>(qa0[cc][v], x0[v], gr[cc], A.kd, modulus, dq, dx, e0);
-                                            ax0[a4][v] += dx;
-                                        }
-                                    }
+                                for (int v = 0; v < KPT; ++v) { nq0[v] = 0.f; nq1[v] = 0.f; }
+                                pair_step<MODEL, HEAD, KPT>(qa0[c], qa1[c], x0, x1, gr[c], A.kd, modulus, nq0, nq1, ax0[a4], ax1[a4], ne);
+                                pair_step<MODEL, HEAD, KPT>(qa0[c + 1], qa1[c + 1], x0, x1, gr[c + 1], A.kd, modulus, nq0, nq1, ax0[a4], ax1[a4], ne);
                             }
                         }
                     }
@@ -1616,13 +1526,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
                 dx0[v] = (ax0[0][v] + ax0[1][v]) + (ax0[2][v] + ax0[3][v]);
                 dx1[v] = (ax1[0][v] + ax1[1][v]) + (ax1[2][v] + ax1[3][v]);
             }
-            acc_t upd;
-            if constexpr (NC == 1) upd = dx0[0];
-            else if constexpr (NC == 2 && !CP) { upd.x = dx0[0]; upd.y = dx0[1]; }
-            else if constexpr (NC == 2) { upd.x = dx0[0]; upd.y = dx1[0]; }
-            else if constexpr (NC == 4 && !CP) { upd.x = dx0[0]; upd.y = dx0[1]; upd.z = dx0[2]; upd.w = dx0[3]; }
-            else { upd.x = dx0[0]; upd.y = dx0[1]; upd.z = dx1[0]; upd.w = dx1[1]; }
-            reinterpret_cast<acc_t *>(A.dXp)[((((size_t)rg * npb + pb) * cap + (h * 64 + j)) * A.dim_slices + s) * 64 + lane] = upd;
+            reinterpret_cast<acc_t *>(A.dXp)[((((size_t)rg * npb + pb) * cap + (h * 64 + j)) * A.dim_slices + s) * 64 + lane] = packet_pack<CP, KPT>(dx0, dx1);
         }
         MKB_TRACE_ONLY(tr_p2 += __builtin_readcyclecounter() - tf0;)
     }
@@ -1634,7 +1538,7 @@ __global__ __launch_bounds__(kBwd1Waves * 64) void pool_bwd1_kernel(PoolArgs A) 
     }
 #endif
     __syncthreads();  // every wave's last phase is done
-    // LDS accumulator -> this row group's partial buffer (16 B per lane, 1 KB per slot and store: plain coalesced stores).
+    // LDS accumulator -> this row group's partial buffer, with the used-slot masks that say which of its slots were written.
     // pool_dx_reduce_kernel sums the row groups and adds the result to the table gradient rows: one fp32 atomic per element
     // instead of one per element AND row group (8.4 M atomics at the headline shape, all issued when the workgroups finish
     // together: 26-37 us of the launch).

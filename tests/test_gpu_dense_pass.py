@@ -63,6 +63,14 @@ def test_dense_pass_edge_shapes_with_wrapping_rows(name, B, K, hidden):
     T.test_fused_step_edge_shapes_with_wrapping_rows(name, B, K, hidden)
 
 
+@pytest.mark.parametrize("flag", ["1", "0"])
+def test_two_tiles_per_wave_with_and_without_the_dense_pass(flag, monkeypatch):
+    """Two row tiles per wave: with the dense pass the fringe's dx half takes its query rows from the Q buffer; without it the
+    general pass walks the chunk ring twice per workgroup."""
+    monkeypatch.setenv("MKB_POOL_DENSE", flag)
+    T.test_every_launch_configuration_agrees_with_general_kernels(*T.TWO_TILES_PER_WAVE, monkeypatch)
+
+
 def test_dense_pass_equals_general_pass_on_the_headline_shape():
     """The two forms of the kernel, same inputs: the dense positions are summed in the same chunk rotation as before, the
     fringe in row order by its slot's owner -- float addition order differs, so the comparison is to 1e-6, not bitwise."""

@@ -715,18 +715,24 @@ def test_full_size_pooled_path_agrees_with_general_kernels_and_oracle_rows(name,
     ns.check()
 
 
-@pytest.mark.parametrize("name,hidden", [("RotatE", 1500), ("RotatE", 3000), ("pRotatE", 1500), ("pRotatE", 3000),
-                                          ("TransE", 3000), ("TransE", 301), ("DistMult", 2600), ("RotatE", 257),
-                                          ("ComplEx", 700)])
-def test_every_launch_configuration_agrees_with_general_kernels(name, hidden, monkeypatch):
+LAUNCH_CONFIGS = [("RotatE", 1500), ("RotatE", 3000), ("pRotatE", 1500), ("pRotatE", 3000), ("TransE", 3000), ("TransE", 301),
+                  ("DistMult", 2600), ("RotatE", 257), ("ComplEx", 700)]
+# Four times the headline batch: 512 row tiles x 8 dim slices x 4 position blocks = 16384 waves, so every wave of the single-pass
+# backward takes TWO row tiles (plan_backward) and the fringe's dx half reads its query rows from the Q buffer, not from LDS.
+TWO_TILES_PER_WAVE = ("RotatE", 1000, "Fb15k237", 4096, 256)
+
+
+@pytest.mark.parametrize("name,hidden,cls,B,K", [(n, h, "Umls", 40, 16) for n, h in LAUNCH_CONFIGS] + [TWO_TILES_PER_WAVE],
+                         ids=[f"{n}-{h}" for n, h in LAUNCH_CONFIGS] + ["RotatE-1000-two-tiles-per-wave"])
+def test_every_launch_configuration_agrees_with_general_kernels(name, hidden, cls, B, K, monkeypatch):
     """The pooled kernels are instantiated per (units per lane, waves per workgroup); wide rows use 16-wave
     workgroups whose register budget is tight (some instantiations spill to scratch).  Every configuration of the
     launch table must give the general kernels' scores and gradients (MFMA route off so the tile kernels run)."""
     from mkb_amd import losses
     monkeypatch.setenv("MKB_POOL_NO_MFMA", "1")
-    ds, m, tb, ns, train = _setup("Umls", name, hidden, 40, 16)
-    idx = torch.as_tensor(np.random.RandomState(3).randint(len(train), size=40))
-    s, w = train[idx].cuda(), (torch.rand(40) + 0.1).cuda()
+    ds, m, tb, ns, train = _setup(cls, name, hidden, B, K)
+    idx = torch.as_tensor(np.random.RandomState(3).randint(len(train), size=B))
+    s, w = train[idx].cuda(), (torch.rand(B) + 0.1).cuda()
     for mode in ("head-batch", "tail-batch"):
         neg = ns.generate(s, mode)
         plain = neg.clone()
