@@ -204,6 +204,19 @@ def aligned_bytes(n, device):
     return raw[off: off + n]
 
 
+class Workspace:
+    """The scratch of a call made in chunks: ``ptr(need)`` -> a 256-byte aligned pointer to at least ``need`` bytes of one device
+    buffer (torch's caching allocator: stream-ordered), which is allocated anew only when a chunk needs more than it holds."""
+
+    def __init__(self, device):
+        self.device, self.raw = device, None
+
+    def ptr(self, need):
+        if self.raw is None or self.raw.numel() < need + 256:
+            self.raw = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        return c_void_p(self.raw.data_ptr() + (-self.raw.data_ptr()) % 256)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _exchange = getattr(torch._C, "_cuda_exchangeDevice", None)
 

@@ -3,13 +3,16 @@ for every positive triple, the k entities / relations the teacher scores highest
 ``FastTopKSampling`` precomputes those lists over the teacher's training triples once and looks them up.  Unsupervised: the
 ground truth is not put into the lists, so ``Distillation`` distils each part of a triple whose other two parts are shared.
 
-The reference loops over the triples on the host with three ``argsort``s per triple.  Here the entity sides are one
-``mkb_topk_masked`` launch per side and batch (the all-entity score block, restricted to the shared entities by a bitmask), the
-relation side one general forward of the ``[b, shared relations, 3]`` block (as ``Evaluation.relation_ranks`` scores it) and one
-``mkb_topk_block``; the ids are mapped with device tables.  ``TopKSamplingTransE`` is the reference's sampler for a TransE teacher:
-the shared entities / relations nearest in L2 to the teacher's translated queries, with the device's exact squared-L2 k nearest
-rows (``mkb_topk_nearest``) in place of the reference's faiss ``IndexFlatL2``; ``FastTopKSampling(..., transe_sampler=
-TopKSamplingTransE)`` precomputes it for a TransE teacher."""
+The reference loops over the triples on the host with three ``argsort``s per triple.  Here one base class holds what every
+sampler shares (the mappings, sizes, checks, device tables, the random columns and the one ``get``), and each live sampler
+answers one question, ``side(part, sample, teacher)``: the k candidates of one part ("head", "relation" or "tail") of these
+triples, in teacher and in student ids.  ``TopKSampling.side`` is one ``mkb_topk_masked`` launch per entity side and batch (the
+all-entity score block, restricted to the shared entities by a bitmask), and for the relation side one general forward of the
+``[b, shared relations, 3]`` block (as ``Evaluation.relation_ranks`` scores it) and one ``mkb_topk_block``.
+``TopKSamplingTransE.side`` is the reference's sampler for a TransE teacher: the shared entities / relations nearest in L2 to
+the teacher's translated queries, with the device's exact squared-L2 k nearest rows (``mkb_topk_nearest``) in place of the
+reference's faiss ``IndexFlatL2``.  ``FastTopKSampling`` runs one loop over the distinct keys of the three parts and asks the
+``side`` of ``TopKSampling`` -- or, for a TransE teacher, of ``transe_sampler=TopKSamplingTransE`` -- ``chunk`` keys at a time."""
 import collections
 
 import numpy as np
@@ -19,6 +22,8 @@ from .. import _hip
 from ..utils.predict_top_k import _launch, candidate_bits, topk_block, topk_nearest
 
 __all__ = ["FastTopKSampling", "TopKSampling", "TopKSamplingTransE"]
+
+PARTS = ("head", "relation", "tail")
 
 
 def _shared(teacher, student):
@@ -33,49 +38,9 @@ def _check_k(k, n_shared, what):
         raise ValueError(f"batch_size_{what} = {k} is larger than the {n_shared} {what} teacher and student share")
 
 
-class _Random:
-    """The random columns of the reference's ``_randomize_distribution`` (top_k_sampling.py:877-960): one draw of entities, then
-    one of relations, per call, from the sampler's ``RandomState``; the same draw goes to every row."""
-
-    def _random_columns(self, b, dev, outs):
-        head_t, rel_t, tail_t, head_s, rel_s, tail_s = outs
-        if self.n_random_entities > 0:
-            t = self._rng.choice(list(self.mapping_entities.keys()), size=self.n_random_entities, replace=False)
-            s = [self.mapping_entities[i] for i in t]
-            t, s = (torch.as_tensor(np.asarray(x, dtype=np.int64)).to(dev).view(1, -1).expand(b, -1) for x in (t, s))
-            head_t, tail_t = torch.cat([head_t, t], dim=1), torch.cat([tail_t, t], dim=1)
-            head_s, tail_s = torch.cat([head_s, s], dim=1), torch.cat([tail_s, s], dim=1)
-        if self.n_random_relations > 0:
-            t = self._rng.choice(list(self.mapping_relations.keys()), size=self.n_random_relations, replace=False)
-            s = [self.mapping_relations[i] for i in t]
-            t, s = (torch.as_tensor(np.asarray(x, dtype=np.int64)).to(dev).view(1, -1).expand(b, -1) for x in (t, s))
-            rel_t, rel_s = torch.cat([rel_t, t], dim=1), torch.cat([rel_s, s], dim=1)
-        return head_t, rel_t, tail_t, head_s, rel_s, tail_s
-
-    @property
-    def batch_size_entity(self):
-        return self.batch_size_entity_top_k + self.n_random_entities
-
-    @property
-    def batch_size_relation(self):
-        return self.batch_size_relation_top_k + self.n_random_relations
-
-
-class TopKSampling(_Random):
-    """The teacher's top ``batch_size_entity`` heads and tails and top ``batch_size_relation`` relations of every triple of
-    ``sample``, among the entities / relations teacher and student share, followed by ``n_random_entities`` /
-    ``n_random_relations`` random shared ones (reference top_k_sampling.py:267-662).
-
-    ``get(sample, teacher)`` -> six int64 tensors on ``sample``'s device: head, relation and tail candidates in teacher ids,
-    then the same in student ids, ``[b, batch_size_entity]`` / ``[b, batch_size_relation]``.
-
-    Two differences from the reference, both where it is ill-defined:
-      - equal teacher scores are ordered by lower teacher id (the reference's ``argsort`` leaves their order unspecified);
-      - the teacher relation list holds teacher relation ids.  The reference returns student ids there
-        (``relations_student[rank_relations]``): the same list whenever both graphs number their shared relations alike;
-        where they do not, it scores the teacher on the wrong relations or indexes out of its table.
-    A top k larger than the number of shared entities / relations raises ``ValueError`` (the reference would return fewer
-    columns and fail later)."""
+class _Sampler:
+    """What the three samplers share: the teacher id -> student id mappings of the shared entities / relations, the top-k and
+    random sizes with their checks, the device tables, the random columns, and ``get``.  A live sampler adds ``side``."""
 
     supervised = False  # the ground truth is not part of the distributions
     depends_on_teacher = True  # KdmkbModel.learn rebuilds it as the teacher trains
@@ -91,8 +56,8 @@ class TopKSampling(_Random):
         self.n_teacher_entities, self.n_teacher_relations = len(teacher_entities), len(teacher_relations)
         _check_k(batch_size_entity, len(self.mapping_entities), "entity")
         _check_k(batch_size_relation, len(self.mapping_relations), "relation")
-        for what, n, shared in (("entity", n_random_entities, self.mapping_entities),
-                                ("relation", n_random_relations, self.mapping_relations)):
+        for what, n, shared in (("entities", n_random_entities, self.mapping_entities),
+                                ("relations", n_random_relations, self.mapping_relations)):
             if n < 0 or n > len(shared):
                 raise ValueError(f"n_random_{what} = {n} must lie in [0, {len(shared)}]")
         self._tables = {}
@@ -123,30 +88,39 @@ class TopKSampling(_Random):
             raise ValueError(f"the teacher's tables ({teacher.n_entity} entities, {teacher.n_relation} relations) do not match "
                              f"teacher_entities / teacher_relations ({self.n_teacher_entities}, {self.n_teacher_relations})")
 
-    def top_k(self, sample, teacher, chunk=1024):
-        """-> (heads, relations, tails) in teacher ids, then the same in student ids: the top-k columns only, on the teacher's
-        device, for ``sample`` [b, 3] int64 on that device.  No random columns, no synchronisation."""
-        dev = teacher.entity_embedding.device
-        tb = self.tables(dev)
-        b = sample.shape[0]
-        ke, kr = self.batch_size_entity_top_k, self.batch_size_relation_top_k
-        none = torch.empty(0, dtype=torch.int64, device=dev)
-        out = []
-        for mode in ("head-batch", "tail-batch"):  # the shared entities only, nothing filtered
-            ids = torch.empty((b, ke), dtype=torch.int64, device=dev)
-            _launch(teacher, sample, mode, ke, none, 0, tb["ent_bits"], chunk, ids, torch.empty((b, ke), dtype=torch.float32, device=dev))
-            out.append(ids)
-        heads_t, tails_t = out
-        rel_pos = torch.empty((b, kr), dtype=torch.int64, device=dev)
-        rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
-        for lo in range(0, b, chunk):  # the relation side: the general forward of [b, R_shared, 3], then the block selection
-            s = sample[lo: lo + chunk]
-            block = torch.stack([s[:, 0:1].expand(-1, n_rel), rel_t.view(1, -1).expand(s.shape[0], -1),
-                                 s[:, 2:3].expand(-1, n_rel)], dim=-1)
-            score = teacher(block.contiguous()).reshape(s.shape[0], n_rel).float().contiguous()
-            topk_block(score, kr, ids=rel_pos[lo: lo + chunk])
-        rels_t = rel_t[rel_pos]
-        return heads_t, rels_t, tails_t, tb["ent_map"][heads_t], tb["rel_s"][rel_pos], tb["ent_map"][tails_t]
+    def _sync(self, teacher):
+        """What ``get`` does to the teacher before it is scored: rows a row-lazy Adam has not brought current yet."""
+        teacher.sync_parameters()
+
+    def _k(self, part):
+        return self.batch_size_relation_top_k if part == "relation" else self.batch_size_entity_top_k
+
+    def _random_columns(self, b, dev, outs):
+        """The random columns of the reference's ``_randomize_distribution`` (top_k_sampling.py:877-960): one draw of entities,
+        then one of relations, per call, from the sampler's ``RandomState``; the same draw goes to every row."""
+        head_t, rel_t, tail_t, head_s, rel_s, tail_s = outs
+
+        def draw(mapping, n):
+            t = self._rng.choice(list(mapping.keys()), size=n, replace=False)
+            s = [mapping[i] for i in t]
+            return (torch.as_tensor(np.asarray(x, dtype=np.int64)).to(dev).view(1, -1).expand(b, -1) for x in (t, s))
+
+        if self.n_random_entities > 0:
+            t, s = draw(self.mapping_entities, self.n_random_entities)
+            head_t, tail_t = torch.cat([head_t, t], dim=1), torch.cat([tail_t, t], dim=1)
+            head_s, tail_s = torch.cat([head_s, s], dim=1), torch.cat([tail_s, s], dim=1)
+        if self.n_random_relations > 0:
+            t, s = draw(self.mapping_relations, self.n_random_relations)
+            rel_t, rel_s = torch.cat([rel_t, t], dim=1), torch.cat([rel_s, s], dim=1)
+        return head_t, rel_t, tail_t, head_s, rel_s, tail_s
+
+    @property
+    def batch_size_entity(self):
+        return self.batch_size_entity_top_k + self.n_random_entities
+
+    @property
+    def batch_size_relation(self):
+        return self.batch_size_relation_top_k + self.n_random_relations
 
     def get(self, sample, teacher, **kwargs):
         """-> (head, relation, tail distributions of the teacher, then of the student): int64 on ``sample``'s device."""
@@ -154,20 +128,64 @@ class TopKSampling(_Random):
         self._check_teacher(teacher)
         out_dev = sample.device
         dev = teacher.entity_embedding.device
-        teacher.sync_parameters()  # (rows a row-lazy Adam has not brought current yet)
+        self._sync(teacher)
         with torch.no_grad():
             s = sample.to(device=dev, dtype=torch.int64).reshape(-1, 3).contiguous()
             b = s.shape[0]
             if b:
-                outs = self.top_k(s, teacher)
+                t_ids, s_ids = zip(*(self.side(part, s, teacher) for part in PARTS))
+                outs = t_ids + s_ids
             else:
-                ke, kr = self.batch_size_entity_top_k, self.batch_size_relation_top_k
-                outs = tuple(torch.empty((0, k), dtype=torch.int64, device=dev) for k in (ke, kr, ke, ke, kr, ke))
+                outs = tuple(torch.empty((0, self._k(part)), dtype=torch.int64, device=dev) for part in PARTS + PARTS)
             outs = self._random_columns(b, dev, outs)
         return tuple(x.contiguous().to(out_dev) for x in outs)
 
 
-class TopKSamplingTransE(_Random):
+class TopKSampling(_Sampler):
+    """The teacher's top ``batch_size_entity`` heads and tails and top ``batch_size_relation`` relations of every triple of
+    ``sample``, among the entities / relations teacher and student share, followed by ``n_random_entities`` /
+    ``n_random_relations`` random shared ones (reference top_k_sampling.py:267-662).
+
+    ``get(sample, teacher)`` -> six int64 tensors on ``sample``'s device: head, relation and tail candidates in teacher ids,
+    then the same in student ids, ``[b, batch_size_entity]`` / ``[b, batch_size_relation]``.
+
+    Two differences from the reference, both where it is ill-defined:
+      - equal teacher scores are ordered by lower teacher id (the reference's ``argsort`` leaves their order unspecified);
+      - the teacher relation list holds teacher relation ids.  The reference returns student ids there
+        (``relations_student[rank_relations]``): the same list whenever both graphs number their shared relations alike;
+        where they do not, it scores the teacher on the wrong relations or indexes out of its table.
+    A top k larger than the number of shared entities / relations raises ``ValueError`` (the reference would return fewer
+    columns and fail later)."""
+
+    def side(self, part, sample, teacher, chunk=1024):
+        """-> (teacher ids, student ids) [b, k] of one part ("head", "relation" or "tail") for ``sample`` [b, 3] int64 on the
+        teacher's device, ``chunk`` rows per launch: the teacher's k best shared entities / relations in that place.  No random
+        columns, no synchronisation."""
+        dev = teacher.entity_embedding.device
+        tb = self.tables(dev)
+        b, k = sample.shape[0], self._k(part)
+        ids = torch.empty((b, k), dtype=torch.int64, device=dev)
+        if part != "relation":  # the shared entities only, nothing filtered
+            _launch(teacher, sample, f"{part}-batch", k, torch.empty(0, dtype=torch.int64, device=dev), 0, tb["ent_bits"], chunk, ids,
+                    torch.empty((b, k), dtype=torch.float32, device=dev))
+            return ids, tb["ent_map"][ids]
+        rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
+        for lo in range(0, b, chunk):  # the general forward of [b, R_shared, 3], then the block selection
+            s = sample[lo: lo + chunk]
+            block = torch.stack([s[:, 0:1].expand(-1, n_rel), rel_t.view(1, -1).expand(s.shape[0], -1),
+                                 s[:, 2:3].expand(-1, n_rel)], dim=-1)
+            score = teacher(block.contiguous()).reshape(s.shape[0], n_rel).float().contiguous()
+            topk_block(score, k, ids=ids[lo: lo + chunk])
+        return rel_t[ids], tb["rel_s"][ids]
+
+    def top_k(self, sample, teacher, chunk=1024):
+        """-> (heads, relations, tails) in teacher ids, then the same in student ids: the top-k columns only, on the teacher's
+        device, for ``sample`` [b, 3] int64 on that device.  No random columns, no synchronisation."""
+        t_ids, s_ids = zip(*(self.side(part, sample, teacher, chunk) for part in PARTS))
+        return t_ids + s_ids
+
+
+class TopKSamplingTransE(_Sampler):
     """The reference's sampler for a TransE teacher (top_k_sampling.py:680-875): for every triple of ``sample`` the
     ``batch_size_entity`` shared entities nearest in L2 to the teacher's translated queries ``t - r`` (heads) and ``h + r``
     (tails), the ``batch_size_relation`` shared relations nearest to ``t - h`` (``TransE._top_k``), then ``n_random_entities`` /
@@ -182,23 +200,11 @@ class TopKSamplingTransE(_Random):
     larger than the number of shared entities / relations raises ``ValueError``, as in ``TopKSampling``; so does a teacher that
     is not a TransE."""
 
-    supervised = False
-    depends_on_teacher = True
-
     def __init__(self, teacher_entities, teacher_relations, student_entities, student_relations, teacher, batch_size_entity,
                  batch_size_relation, n_random_entities, n_random_relations, seed=None, device="cpu", **kwargs):
-        if teacher.name != "TransE":
-            raise ValueError(f"TopKSamplingTransE needs a TransE teacher, got {teacher.name}")
-        self._base = TopKSampling(teacher_entities=teacher_entities, teacher_relations=teacher_relations,
-                                  student_entities=student_entities, student_relations=student_relations,
-                                  batch_size_entity=batch_size_entity, batch_size_relation=batch_size_relation,
-                                  n_random_entities=n_random_entities, n_random_relations=n_random_relations, device=device)
-        self._base._check_teacher(teacher)
-        self.mapping_entities, self.mapping_relations = self._base.mapping_entities, self._base.mapping_relations
-        self.batch_size_entity_top_k, self.batch_size_relation_top_k = batch_size_entity, batch_size_relation
-        self.n_random_entities, self.n_random_relations = n_random_entities, n_random_relations
-        self.device = device
-        self._rng = np.random.RandomState(seed)
+        super().__init__(teacher_entities, teacher_relations, student_entities, student_relations, batch_size_entity,
+                         batch_size_relation, n_random_entities, n_random_relations, device=device, seed=seed)
+        self._check_teacher(teacher)
         teacher.sync_parameters()
         with torch.no_grad():
             dev = teacher.entity_embedding.device
@@ -209,46 +215,26 @@ class TopKSamplingTransE(_Random):
             self._index = {part: (tables[part].detach()[ids].contiguous(), ids, torch.arange(ids.numel(), device=dev))
                            for part, ids in shared.items()}
 
+    def _check_teacher(self, teacher):
+        if teacher.name != "TransE":
+            raise ValueError(f"TopKSamplingTransE needs a TransE teacher, got {teacher.name}")
+        super()._check_teacher(teacher)
+
+    def _sync(self, teacher):
+        """Nothing: the constructor synchronised the teacher when it cut the index; ``get`` reads its tables as they are."""
+
     def side(self, part, sample, teacher):
         """-> (teacher ids, student ids) [b, k] of one part ("head", "relation" or "tail") for ``sample`` [b, 3] int64 on the
         teacher's device: the shared rows nearest to the part's translated query.  No random columns, no synchronisation."""
         index, t_ids, pos = self._index["relation" if part == "relation" else "entity"]
-        k = self.batch_size_relation_top_k if part == "relation" else self.batch_size_entity_top_k
-        q = teacher._top_k(sample)[("head", "relation", "tail").index(part)]
-        near, _ = topk_nearest(q.reshape(sample.shape[0], -1).contiguous(), index, pos, k)
+        q = teacher._top_k(sample)[PARTS.index(part)]
+        near, _ = topk_nearest(q.reshape(sample.shape[0], -1).contiguous(), index, pos, self._k(part))
         t = t_ids[near]
         tb = self.tables(sample.device)
         return t, (tb["rel_map"] if part == "relation" else tb["ent_map"])[t]
 
-    def tables(self, device):
-        """``TopKSampling.tables``: the teacher id -> student id maps."""
-        return self._base.tables(device)
 
-    def _check_teacher(self, teacher):
-        self._base._check_teacher(teacher)
-
-    def get(self, sample, teacher, **kwargs):
-        """-> (head, relation, tail distributions of the teacher, then of the student): int64 on ``sample``'s device."""
-        _hip.require_device(teacher.entity_embedding)
-        if teacher.name != "TransE":
-            raise ValueError(f"TopKSamplingTransE needs a TransE teacher, got {teacher.name}")
-        self._base._check_teacher(teacher)
-        out_dev = sample.device
-        dev = teacher.entity_embedding.device
-        with torch.no_grad():
-            s = sample.to(device=dev, dtype=torch.int64).reshape(-1, 3).contiguous()
-            b = s.shape[0]
-            if b:
-                (ht, hs), (rt, rs), (tt, ts) = (self.side(part, s, teacher) for part in ("head", "relation", "tail"))
-                outs = (ht, rt, tt, hs, rs, ts)
-            else:
-                ke, kr = self.batch_size_entity_top_k, self.batch_size_relation_top_k
-                outs = tuple(torch.empty((0, k), dtype=torch.int64, device=dev) for k in (ke, kr, ke, ke, kr, ke))
-            outs = self._random_columns(b, dev, outs)
-        return tuple(x.contiguous().to(out_dev) for x in outs)
-
-
-class FastTopKSampling(_Random):
+class FastTopKSampling(_Sampler):
     """``TopKSampling`` precomputed over the teacher's training triples when it is built (reference top_k_sampling.py:9-264):
     for every distinct (r, t) of ``dataset_teacher``'s triples the teacher's top heads, for every distinct (h, t) its top
     relations, for every distinct (h, r) its top tails -- on the device, ``chunk`` queries at a time.  ``get`` looks the rows of
@@ -258,9 +244,6 @@ class FastTopKSampling(_Random):
     when their iterators are created), so a seeded run keeps the reference's batch order.  A TransE teacher takes the sampler the
     reference hands it to, ``TopKSamplingTransE``, when ``transe_sampler=distillation.TopKSamplingTransE`` is passed; without
     it a TransE teacher raises ``ImportError``, as the reference does without faiss.  Other teachers ignore ``transe_sampler``."""
-
-    supervised = False
-    depends_on_teacher = True
 
     def __init__(self, teacher_entities, teacher_relations, student_entities, student_relations, batch_size_entity,
                  batch_size_relation, n_random_entities, n_random_relations, dataset_teacher, teacher, device="cpu", seed=None,
@@ -272,16 +255,10 @@ class FastTopKSampling(_Random):
                               "for the device's exact L2 index, or use another teacher or TopKSampling")
         kw = dict(teacher_entities=teacher_entities, teacher_relations=teacher_relations, student_entities=student_entities,
                   student_relations=student_relations, batch_size_entity=batch_size_entity, batch_size_relation=batch_size_relation,
-                  n_random_entities=0, n_random_relations=0, device=device, seed=seed)
-        base = transe_sampler(teacher=teacher, **kw) if transe else TopKSampling(**kw)
-        self.mapping_entities, self.mapping_relations = base.mapping_entities, base.mapping_relations
-        self.batch_size_entity_top_k, self.batch_size_relation_top_k = batch_size_entity, batch_size_relation
-        self.n_random_entities, self.n_random_relations = n_random_entities, n_random_relations
-        if n_random_entities > len(self.mapping_entities) or n_random_relations > len(self.mapping_relations) \
-                or min(n_random_entities, n_random_relations) < 0:
-            raise ValueError("n_random_entities / n_random_relations must lie in [0, the number of shared entities / relations]")
-        self._rng = np.random.RandomState(seed)
-        self.device = device
+                  device=device, seed=seed)
+        super().__init__(n_random_entities=n_random_entities, n_random_relations=n_random_relations, **kw)
+        # whose ``side`` answers "the k candidates of this part for these queries"
+        base = (transe_sampler if transe else TopKSampling)(teacher=teacher, n_random_entities=0, n_random_relations=0, **kw)
         _hip.require_device(teacher.entity_embedding)
         base._check_teacher(teacher)
         # the reference's pass over the teacher's training batches (its dicts are filled from the head-batch ones)
@@ -293,47 +270,17 @@ class FastTopKSampling(_Random):
         teacher.sync_parameters()
         self._keys = {}
         self._N, self._R = N, R
-        if transe:  # the shared rows nearest to each distinct key's translated query (TopKSamplingTransE.side)
-            with torch.no_grad():
-                zero = torch.zeros_like
-                for part, key, row in (("head", r * N + t, lambda u: (zero(u), u // N, u % N)),
-                                       ("relation", h * N + t, lambda u: (u // N, zero(u), u % N)),
-                                       ("tail", h * R + r, lambda u: (u // R, u % R, zero(u)))):
-                    u = torch.unique(key)
-                    q = torch.stack(row(u), 1).contiguous()
-                    k = batch_size_relation if part == "relation" else batch_size_entity
-                    t_ids, s_ids = (torch.empty((u.numel(), k), dtype=torch.int64, device=dev) for _ in range(2))
-                    for lo in range(0, u.numel(), chunk):
-                        t_ids[lo: lo + chunk], s_ids[lo: lo + chunk] = base.side(part, q[lo: lo + chunk], teacher)
-                    self._keys[part] = (u, t_ids, s_ids)
-            return
-        with torch.no_grad():
-            tb = base.tables(dev)
-            ke, kr = batch_size_entity, batch_size_relation
-            none = torch.empty(0, dtype=torch.int64, device=dev)
-            # heads of (?, r, t) and tails of (h, r, ?): one masked top k per distinct key
-            for part, key, mode, cols in (("head", r * N + t, "head-batch", lambda u: (u // N, u % N)),
-                                          ("tail", h * R + r, "tail-batch", lambda u: (u // R, u % R))):
+        zero = torch.zeros_like
+        with torch.no_grad():  # per part: its distinct keys, a query row per key (the part's own column is a placeholder)
+            for part, key, row in (("head", r * N + t, lambda u: (zero(u), u // N, u % N)),
+                                   ("relation", h * N + t, lambda u: (u // N, zero(u), u % N)),
+                                   ("tail", h * R + r, lambda u: (u // R, u % R, zero(u)))):
                 u = torch.unique(key)
-                a, c = cols(u)
-                q = torch.stack([torch.zeros_like(a), a, c], 1) if part == "head" else torch.stack([a, c, torch.zeros_like(a)], 1)
-                ids = torch.empty((u.numel(), ke), dtype=torch.int64, device=dev)
-                if u.numel():
-                    _launch(teacher, q.contiguous(), mode, ke, none, 0, tb["ent_bits"], chunk, ids,
-                            torch.empty((u.numel(), ke), dtype=torch.float32, device=dev))
-                self._keys[part] = (u, ids, tb["ent_map"][ids])
-            # relations of (h, ?, t)
-            u = torch.unique(h * N + t)
-            q = torch.stack([u // N, torch.zeros_like(u), u % N], 1).contiguous()
-            pos = torch.empty((u.numel(), kr), dtype=torch.int64, device=dev)
-            rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
-            for lo in range(0, u.numel(), chunk):
-                s = q[lo: lo + chunk]
-                block = torch.stack([s[:, 0:1].expand(-1, n_rel), rel_t.view(1, -1).expand(s.shape[0], -1),
-                                     s[:, 2:3].expand(-1, n_rel)], dim=-1)
-                score = teacher(block.contiguous()).reshape(s.shape[0], n_rel).float().contiguous()
-                topk_block(score, kr, ids=pos[lo: lo + chunk])
-            self._keys["relation"] = (u, rel_t[pos], tb["rel_s"][pos])
+                q = torch.stack(row(u), 1).contiguous()
+                t_ids, s_ids = (torch.empty((u.numel(), self._k(part)), dtype=torch.int64, device=dev) for _ in range(2))
+                for lo in range(0, u.numel(), chunk):
+                    t_ids[lo: lo + chunk], s_ids[lo: lo + chunk] = base.side(part, q[lo: lo + chunk], teacher)
+                self._keys[part] = (u, t_ids, s_ids)
 
     def _rows(self, part, key):
         keys, t, s = self._keys[part]
@@ -352,8 +299,7 @@ class FastTopKSampling(_Random):
         dev = self._keys["head"][0].device
         s = sample.to(device=dev, dtype=torch.int64).reshape(-1, 3)
         h, r, t = s[:, 0], s[:, 1], s[:, 2]
-        head_t, head_s = self._rows("head", r * self._N + t)
-        rel_t, rel_s = self._rows("relation", h * self._N + t)
-        tail_t, tail_s = self._rows("tail", h * self._R + r)
+        (head_t, head_s), (rel_t, rel_s), (tail_t, tail_s) = (
+            self._rows(part, key) for part, key in zip(PARTS, (r * self._N + t, h * self._N + t, h * self._R + r)))
         outs = self._random_columns(s.shape[0], dev, (head_t, rel_t, tail_t, head_s, rel_s, tail_s))
         return tuple(x.contiguous().to(out_dev) for x in outs)

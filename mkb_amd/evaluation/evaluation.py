@@ -9,7 +9,6 @@ reference's route instead: ``TestDataset`` candidate lists + filter bias, ``mode
 through the general HIP forward, rank read off a descending argsort (evaluation.py:245-262).
 """
 import collections
-import ctypes
 
 import numpy as np
 import torch
@@ -21,6 +20,24 @@ from ..models.base import BaseModel
 from ..utils import Bar, Mean, predict_top_k, true_keys
 
 __all__ = ["Evaluation"]
+
+
+def _metrics():
+    return collections.OrderedDict({m: Mean() for m in ["MRR", "MR", "HITS@1", "HITS@3", "HITS@10"]})
+
+
+def _update(metrics, ranks):
+    """Add the 1-based ``ranks`` (a list) to the five running means."""
+    for ranking in ranks:
+        metrics["MRR"].update(1.0 / ranking)
+        metrics["MR"].update(ranking)
+        metrics["HITS@1"].update(1.0 if ranking <= 1 else 0.0)
+        metrics["HITS@3"].update(1.0 if ranking <= 3 else 0.0)
+        metrics["HITS@10"].update(1.0 if ranking <= 10 else 0.0)
+
+
+def _report(metrics, suffix=""):
+    return {f"{name}{suffix}": round(metric.get(), 4) for name, metric in metrics.items()}
 
 
 class Evaluation:
@@ -48,10 +65,6 @@ class Evaluation:
                                collate_fn=base.TestDatasetRelation.collate_fn)
 
     # ------------------------------------------------------------------ device ranking (mkb_rank)
-    def _true_keys(self, device, n_entity, n_relation):
-        """Sorted keys of all true triples, one ordering per mode (cached on the device: utils.true_keys)."""
-        return true_keys(self.true_triples, device, n_entity, n_relation)
-
     def ranks(self, model, dataset, mode, chunk=1024, with_scores=False):
         """Filtered rank (1-based) of every triple of ``dataset`` in ``mode``, computed on the device: int64 tensor.
         ``with_scores=True`` -> ``(ranks, scores [n, n_entity])``: the scores of every triple against all entities the ranks
@@ -60,29 +73,20 @@ class Evaluation:
         dev = model.entity_embedding.device
         _hip.require_device(model.entity_embedding)
         model.sync_parameters()
-        keys = self._true_keys(dev, model.n_entity, model.n_relation)[mode]
+        keys = true_keys(self.true_triples, dev, model.n_entity, model.n_relation)[mode]
         triples = torch.as_tensor(np.asarray(dataset, dtype=np.int64).reshape(-1, 3), device=dev)
         out = torch.empty(len(triples), dtype=torch.int64, device=dev)
         scores = torch.empty((len(triples), model.n_entity), dtype=torch.float32, device=dev) if with_scores else None
-        lib, tb = _hip.lib(), model._tables()
-        ws = None
+        lib, tb, ws = _hip.lib(), model._tables(), _hip.Workspace(dev)
+        name = "mkb_rank_scores" if with_scores else "mkb_rank"
+        fn = getattr(lib, name)
         with _hip.on_device(dev):
             for lo in range(0, len(triples), chunk):
                 s = triples[lo: lo + chunk].contiguous()
                 need = lib.mkb_rank_workspace_bytes(tb, s.shape[0])
-                if ws is None or ws.numel() < need + 256:
-                    ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-                off = (-ws.data_ptr()) % 256
-                if with_scores:
-                    _hip.check(lib.mkb_rank_scores(tb, _hip.ptr(s), s.shape[0], _hip.mode_id(mode), _hip.ptr(keys), keys.numel(),
-                                                   _hip.ptr(out[lo: lo + chunk]), _hip.ptr(scores[lo: lo + chunk]),
-                                                   ctypes.c_void_p(ws.data_ptr() + off), need, _hip.stream_ptr()),
-                               "mkb_rank_scores")
-                    continue
-                _hip.check(lib.mkb_rank(tb, _hip.ptr(s), s.shape[0], _hip.mode_id(mode), _hip.ptr(keys), keys.numel(),
-                                        _hip.ptr(out[lo: lo + chunk]), ctypes.c_void_p(ws.data_ptr() + off), need,
-                                        _hip.stream_ptr()),
-                           "mkb_rank")
+                block = (_hip.ptr(scores[lo: lo + chunk]),) if with_scores else ()  # (the score rows follow the ranks)
+                _hip.check(fn(tb, _hip.ptr(s), s.shape[0], _hip.mode_id(mode), _hip.ptr(keys), keys.numel(),
+                              _hip.ptr(out[lo: lo + chunk]), *block, ws.ptr(need), need, _hip.stream_ptr()), name)
         return (out, scores) if with_scores else out
 
     def top_k(self, model, dataset, mode, k, keep_target=True, chunk=1024):
@@ -97,7 +101,7 @@ class Evaluation:
                 and units <= 4096 and len(self.true_triples) > 0)
 
     def eval(self, model, dataset):
-        metrics = collections.OrderedDict({m: Mean() for m in ["MRR", "MR", "HITS@1", "HITS@3", "HITS@10"]})
+        metrics = _metrics()
         if self._device_ok(model) and not getattr(self, "force_reference_path", False):
             with torch.no_grad():
                 for mode in ("head-batch", "tail-batch"):  # same order as get_entity_stream
@@ -105,17 +109,12 @@ class Evaluation:
                     # from torch's global CPU generator (the workers' base seed).  Draw it too, so that a training
                     # run interleaved with evaluations keeps shuffling its batches exactly like the reference.
                     torch.empty((), dtype=torch.int64).random_()
-                    for ranking in self.ranks(model, dataset, mode).tolist():
-                        metrics["MRR"].update(1.0 / ranking)
-                        metrics["MR"].update(ranking)
-                        metrics["HITS@1"].update(1.0 if ranking <= 1 else 0.0)
-                        metrics["HITS@3"].update(1.0 if ranking <= 3 else 0.0)
-                        metrics["HITS@10"].update(1.0 if ranking <= 10 else 0.0)
-            return {name: round(metric.get(), 4) for name, metric in metrics.items()}
+                    _update(metrics, self.ranks(model, dataset, mode).tolist())
+            return _report(metrics)
         with torch.no_grad():
             for test_set in self.get_entity_stream(dataset):
                 metrics = self.compute_score(model=model, test_set=test_set, metrics=metrics, device=self.device)
-        return {name: round(metric.get(), 4) for name, metric in metrics.items()}
+        return _report(metrics)
 
     def relation_ranks(self, model, dataset, chunk=4096):
         """Filtered rank (1-based) of the true relation of every triple among all relations, on the device: what
@@ -123,7 +122,7 @@ class Evaluation:
         (h, ., t) are replaced by the target relation and biased by -1), without the per-item host loop."""
         dev = model.entity_embedding.device
         n_ent, n_rel = model.n_entity, model.n_relation
-        keys = self._true_keys(dev, n_ent, n_rel)["tail-batch"]  # sorted (h * R + r) * N + t
+        keys = true_keys(self.true_triples, dev, n_ent, n_rel)["tail-batch"]  # sorted (h * R + r) * N + t
         triples = torch.as_tensor(np.asarray(dataset, dtype=np.int64).reshape(-1, 3), device=dev)
         cand = torch.arange(n_rel, device=dev)
         out = []
@@ -146,21 +145,16 @@ class Evaluation:
         return torch.cat(out) if out else torch.empty(0, dtype=torch.int64, device=dev)
 
     def eval_relations(self, model, dataset):
-        metrics = collections.OrderedDict({m: Mean() for m in ["MRR", "MR", "HITS@1", "HITS@3", "HITS@10"]})
+        metrics = _metrics()
         if self._device_ok(model) and not getattr(self, "force_reference_path", False) and len(dataset) > 0:
             with torch.no_grad():
                 torch.empty((), dtype=torch.int64).random_()  # the reference's DataLoader iterator draws its base seed
-                for ranking in self.relation_ranks(model, dataset).tolist():
-                    metrics["MRR"].update(1.0 / ranking)
-                    metrics["MR"].update(ranking)
-                    metrics["HITS@1"].update(1.0 if ranking <= 1 else 0.0)
-                    metrics["HITS@3"].update(1.0 if ranking <= 3 else 0.0)
-                    metrics["HITS@10"].update(1.0 if ranking <= 10 else 0.0)
-            return {f"{name}_relations": round(metric.get(), 4) for name, metric in metrics.items()}
+                _update(metrics, self.relation_ranks(model, dataset).tolist())
+            return _report(metrics, "_relations")
         with torch.no_grad():
             metrics = self.compute_score(model=model, test_set=self.get_relation_stream(dataset), metrics=metrics,
                                          device=self.device)
-        return {f"{name}_relations": round(metric.get(), 4) for name, metric in metrics.items()}
+        return _report(metrics, "_relations")
 
     @classmethod
     def compute_score(cls, model, test_set, metrics, device):
@@ -184,13 +178,7 @@ class Evaluation:
             argsort = torch.argsort(score, dim=1, descending=True)
             hit = argsort == positive_arg.unsqueeze(1)
             assert bool((hit.sum(dim=1) == 1).all())
-            ranks = (hit.float().argmax(dim=1) + 1).tolist()  # one D2H copy per batch
-            for ranking in ranks:
-                metrics["MRR"].update(1.0 / ranking)
-                metrics["MR"].update(ranking)
-                metrics["HITS@1"].update(1.0 if ranking <= 1 else 0.0)
-                metrics["HITS@3"].update(1.0 if ranking <= 3 else 0.0)
-                metrics["HITS@10"].update(1.0 if ranking <= 10 else 0.0)
+            _update(metrics, (hit.float().argmax(dim=1) + 1).tolist())  # one D2H copy per batch
         if training:
             model = model.train()
         return metrics

@@ -29,12 +29,10 @@ def _workspace(model, B, K, slot=0):
     if ws is None:
         n = _hip.lib().mkb_pool_step_workspace_bytes(model._tables(), B, K)
         guard = _GUARD_BYTES if _guard_on() else 0
-        buf = torch.empty(n + 256 + guard, dtype=torch.uint8, device=dev)
-        off = (-buf.data_ptr()) % 256
-        ws = buf[off: off + n]
+        buf = _hip.aligned_bytes(n + guard, dev)
+        ws = buf[:n]
         if guard:  # (debug: a pattern behind the workspace that no kernel may touch; check_workspace_guards() looks at it)
-            buf[off + n:].fill_(_GUARD_VALUE)
-            _guards[key] = buf[off + n:]
+            _guards[key] = buf[n:].fill_(_GUARD_VALUE)
         _workspaces[key] = ws
     return ws
 

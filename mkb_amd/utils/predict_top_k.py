@@ -3,7 +3,6 @@
 are those of the all-entity block ``Evaluation.ranks(..., with_scores=True)`` hands out, the order that of the filtered rank (NaN
 first, then higher score, then lower entity id); no ``[B, n_entity]`` block is ever returned or kept.  ``candidates`` limits the
 predictions to a subset of the entities (``mkb_topk_masked``)."""
-import ctypes
 import operator
 
 import torch
@@ -92,26 +91,16 @@ def predict_top_k(model, sample, mode, k, true_triples=None, keep_target=False, 
 def _launch(model, s_all, mode, k, keys, flags, bits, chunk, ids, scores):
     """mkb_topk (bits None) / mkb_topk_masked over the rows of s_all in chunks; no validation, no synchronisation."""
     dev = model.entity_embedding.device
-    lib, tb = _hip.lib(), model._tables()
-    ws = None
+    lib, tb, ws = _hip.lib(), model._tables(), _hip.Workspace(dev)
+    name, mask = ("mkb_topk", ()) if bits is None else ("mkb_topk_masked", (_hip.ptr(bits),))  # (the mask follows the keys)
+    fn = getattr(lib, name)
     with _hip.on_device(dev):
         for lo in range(0, s_all.shape[0], chunk):
             s = s_all[lo: lo + chunk].contiguous()
             need = lib.mkb_topk_workspace_bytes(tb, s.shape[0], k)
-            if ws is None or ws.numel() < need + 256:
-                ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-            off = (-ws.data_ptr()) % 256
-            if bits is None:
-                _hip.check(lib.mkb_topk(tb, _hip.ptr(s), s.shape[0], _hip.mode_id(mode), _hip.ptr(keys), keys.numel(), k, flags,
-                                        _hip.ptr(ids[lo: lo + chunk]), _hip.ptr(scores[lo: lo + chunk]),
-                                        ctypes.c_void_p(ws.data_ptr() + off), need, _hip.stream_ptr()),
-                           "mkb_topk")
-            else:
-                _hip.check(lib.mkb_topk_masked(tb, _hip.ptr(s), s.shape[0], _hip.mode_id(mode), _hip.ptr(keys), keys.numel(),
-                                               _hip.ptr(bits), k, flags, _hip.ptr(ids[lo: lo + chunk]),
-                                               _hip.ptr(scores[lo: lo + chunk]), ctypes.c_void_p(ws.data_ptr() + off), need,
-                                               _hip.stream_ptr()),
-                           "mkb_topk_masked")
+            _hip.check(fn(tb, _hip.ptr(s), s.shape[0], _hip.mode_id(mode), _hip.ptr(keys), keys.numel(), *mask, k, flags,
+                          _hip.ptr(ids[lo: lo + chunk]), _hip.ptr(scores[lo: lo + chunk]), ws.ptr(need), need, _hip.stream_ptr()),
+                       name)
     return ids, scores
 
 

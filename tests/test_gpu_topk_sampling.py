@@ -361,3 +361,52 @@ def test_fast_topk_sampling_errors_and_lookup():
     h = next(e for e in range(len(ds.entities)) if all((e, 0, t) not in seen for t in range(len(ds.entities))))
     with pytest.raises(KeyError):
         fast.get(sample=torch.tensor([[h, 0, 0]], device="cuda"))
+
+
+@pytest.mark.parametrize("cls", ["RotatE", "TransE"])
+def test_fast_topk_sampling_chunk_seams(cls):
+    """The one precompute loop at its chunk seams: chunk = 7 (it divides none of CountriesS1's 192 / 1110 / 432 head / relation /
+    tail keys, so every part ends on a ragged chunk) against chunk = 1024 (one chunk, but two for the relations) -- the same keys,
+    teacher ids and student ids for all three parts, for a RotatE teacher (TopKSampling.side) and a TransE teacher
+    (TopKSamplingTransE.side)."""
+    from mkb_amd import datasets, distillation, models
+
+    ds = datasets.CountriesS1(batch_size=64, seed=42, shuffle=False, num_workers=0)
+    torch.manual_seed(5)
+    teacher = getattr(models, cls)(hidden_dim=6, entities=ds.entities, relations=ds.relations, gamma=3).cuda()
+    kw = dict(teacher_entities=ds.entities, teacher_relations=ds.relations, student_entities=ds.entities,
+              student_relations=ds.relations, dataset_teacher=ds, teacher=teacher, batch_size_entity=3, batch_size_relation=2,
+              n_random_entities=1, n_random_relations=1, seed=3, device="cuda", transe_sampler=distillation.TopKSamplingTransE)
+    small, whole = (distillation.FastTopKSampling(chunk=chunk, **kw) for chunk in (7, 1024))
+    for part in ("head", "relation", "tail"):
+        n = whole._keys[part][0].numel()
+        assert n > 7 and n % 7 != 0, (part, n)
+        assert whole._keys[part][1].shape == (n, 2 if part == "relation" else 3)
+        for a, b in zip(small._keys[part], whole._keys[part]):
+            assert torch.equal(a, b), part
+
+
+def test_samplers_share_one_constructor():
+    """FastTopKSampling and TopKSamplingTransE refuse the sizes TopKSampling refuses (tests/test_host_topk_sampling.py), and a
+    FastTopKSampling over no triples holds empty [0, k] lists."""
+    from mkb_amd import datasets, distillation, models
+
+    ds = datasets.CountriesS1(batch_size=64, seed=42, shuffle=False, num_workers=0)
+    n_e, n_r = len(ds.entities), len(ds.relations)
+    kw = dict(teacher_entities=ds.entities, teacher_relations=ds.relations, student_entities=ds.entities,
+              student_relations=ds.relations, dataset_teacher=[], seed=3, device="cuda")
+    ok = dict(batch_size_entity=3, batch_size_relation=1, n_random_entities=1, n_random_relations=1)
+    teachers = {distillation.FastTopKSampling: models.RotatE(hidden_dim=4, entities=ds.entities, relations=ds.relations, gamma=3).cuda(),
+                distillation.TopKSamplingTransE: models.TransE(hidden_dim=4, entities=ds.entities, relations=ds.relations, gamma=3).cuda()}
+    for sampler, teacher in teachers.items():
+        for bad in (dict(batch_size_entity=0), dict(batch_size_entity=n_e + 1), dict(batch_size_relation=0),
+                    dict(batch_size_relation=n_r + 1), dict(n_random_entities=-1), dict(n_random_entities=n_e + 1),
+                    dict(n_random_relations=-1), dict(n_random_relations=n_r + 1)):
+            with pytest.raises(ValueError):
+                sampler(teacher=teacher, **kw, **{**ok, **bad})
+    empty = distillation.FastTopKSampling(teacher=teachers[distillation.FastTopKSampling], **kw, **ok)
+    assert (empty.batch_size_entity, empty.batch_size_relation) == (4, 2)
+    for part, k in (("head", 3), ("relation", 1), ("tail", 3)):
+        assert [tuple(x.shape) for x in empty._keys[part]] == [(0,), (0, k), (0, k)]
+    with pytest.raises(KeyError):
+        empty.get(sample=torch.tensor([[0, 0, 1]], device="cuda"))

@@ -141,3 +141,23 @@ def test_kdmkb_with_transe_teacher_vs_reference(golden):
     for key, m in (("m1", m1), ("m2", m2)):
         np.testing.assert_allclose(m.entity_embedding.detach().cpu().numpy(), g[f"kd/{key}_ent_after"], rtol=0, atol=1e-2)
         np.testing.assert_allclose(m.relation_embedding.detach().cpu().numpy(), g[f"kd/{key}_rel_after"], rtol=0, atol=3e-5)
+
+
+def test_fast_equals_slow_for_a_transe_teacher():
+    """FastTopKSampling(transe_sampler=TopKSamplingTransE).get equals TopKSamplingTransE.get on the first 50 CountriesS1
+    training triples, all six tensors, with one seed on both: the two score the same query rows against the same index rows with
+    the same kernel, so the lists are equal exactly."""
+    from mkb_amd import datasets, distillation, models
+
+    ds = datasets.CountriesS1(batch_size=64, seed=42, shuffle=False, num_workers=0)
+    torch.manual_seed(0)
+    teacher = models.TransE(hidden_dim=8, entities=ds.entities, relations=ds.relations, gamma=3).cuda()
+    kw = dict(teacher_entities=ds.entities, teacher_relations=ds.relations, student_entities=ds.entities,
+              student_relations=ds.relations, teacher=teacher, batch_size_entity=3, batch_size_relation=1, n_random_entities=2,
+              n_random_relations=1, seed=3, device="cuda")
+    fast = distillation.FastTopKSampling(dataset_teacher=ds, transe_sampler=distillation.TopKSamplingTransE, **kw)
+    slow = distillation.TopKSamplingTransE(**kw)
+    train = torch.as_tensor(np.asarray(ds.train, dtype=np.int64)[:50]).cuda()
+    for name, x, y in zip(NAMES, fast.get(sample=train), slow.get(sample=train, teacher=teacher)):
+        assert x.shape == y.shape == (50, 2 if name.startswith("rel") else 5)
+        assert torch.equal(x, y), name

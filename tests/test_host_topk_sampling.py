@@ -109,3 +109,26 @@ def test_topk_sampling_mappings_and_sizes():
         distillation.FastTopKSampling(teacher_entities=t_ents, teacher_relations=t_rels, student_entities=s_ents,
                                       student_relations=s_rels, batch_size_entity=2, batch_size_relation=1, n_random_entities=0,
                                       n_random_relations=0, dataset_teacher=[], teacher=transe)
+
+
+@pytest.mark.parametrize("what", ["entity", "relation"])
+def test_one_constructor_checks_both_sizes(what):
+    """The samplers' one constructor: a top k of 0, past the shared set or past TOPK_MAX_K, and a random size below 0 or past the
+    shared set, raise ValueError -- for entities and for relations."""
+    from mkb_amd import _hip, distillation
+
+    big = _hip.TOPK_MAX_K + 6  # shared labels: more than the largest k, so that only the k bound can refuse it
+    dicts = {f"teacher_{w}": {f"x{i}": i for i in range(big)} for w in ("entities", "relations")}
+    dicts.update({f"student_{w}": {f"x{i}": i for i in range(5, big + 5)} for w in ("entities", "relations")})  # big - 5 shared
+    shared = big - 5
+    ok = dict(batch_size_entity=2, batch_size_relation=2, n_random_entities=1, n_random_relations=1)
+    ts = distillation.TopKSampling(**dicts, **ok)
+    assert len(ts.mapping_entities) == len(ts.mapping_relations) == shared > _hip.TOPK_MAX_K
+    plural = "entities" if what == "entity" else "relations"
+    for bad in ({f"batch_size_{what}": 0}, {f"batch_size_{what}": shared + 1}, {f"batch_size_{what}": _hip.TOPK_MAX_K + 1},
+                {f"n_random_{plural}": -1}, {f"n_random_{plural}": shared + 1}):
+        with pytest.raises(ValueError):
+            distillation.TopKSampling(**dicts, **{**ok, **bad})
+    small = {k: ({f"x{i}": i for i in range(4)} if k.endswith(plural) else v) for k, v in dicts.items()}
+    with pytest.raises(ValueError):  # within TOPK_MAX_K, past the 4 shared
+        distillation.TopKSampling(**small, **{**ok, f"batch_size_{what}": 5})
