@@ -32,15 +32,12 @@ def direct(param, tensor, ids_fn):
     exactly what the fused step does.  Nothing dense is allocated, filled, added or stepped: the README loop
     (``model(sample)`` / ``model(sample, negatives, mode)`` / ``loss.backward()`` / ``optimizer.step()``) keeps the row-lazy
     route, where a dense buffer handed to autograd made the optimizer fall back to the dense kernel for good."""
-    if param is None or _links.owner(param) is None or not _links.owner(param).direct_grads:
+    opt = None if param is None else _links.owner(param)
+    if opt is None or not opt.direct_grads:
         return None
     g = param.grad
     if (g is None or tensor.data_ptr() != param.data_ptr() or g.shape != param.shape or not g.is_contiguous()
             or g.dtype != torch.float32 or g.device != param.device):
         return None
-    # (rows a forward pass of THIS optimizer step count made current -- models/base.py:_make_current -- need no second visit
-    # in front of the step launch)
-    st = _links.owner(param)._state(param)
-    _links.mark_touched(param, ids_fn(), current=st.get("fwd_n") == st["n"])
-    _links.rebase(param)
+    opt.rows_written(param, ids_fn(), after_forward=True)
     return g

@@ -1,9 +1,9 @@
-"""Side tables that tie a parameter to the ``mkb_amd.optim.Adam`` stepping it row-lazily and to the rows its pending step
-has to visit.
+"""The side table that ties a parameter to the ``mkb_amd.optim.Adam`` stepping it row-lazily and to the rows its pending step
+has to visit: one ``Link`` record per parameter.
 
 They used to be attributes on the ``nn.Parameter``; torch pickles a Parameter's ``__dict__`` with it, so ``model.save()``
 (models/base.py, the reference's mkb/models/base.py:41-46) serialised the whole optimizer -- moments, replay constants, a
-ctypes sampler handle (which cannot be pickled at all) -- into the model file.  Identity-keyed weak tables keep the links
+ctypes sampler handle (which cannot be pickled at all) -- into the model file.  An identity-keyed weak table keeps the links
 out of the model: nothing here survives or travels with a parameter.
 """
 import weakref
@@ -60,16 +60,7 @@ class WeakIdTable:
     def __len__(self):
         return len(self._d)
 
-__all__ = ["all_marks_current", "attach", "autograd_wrote", "clear_autograd_wrote", "detach", "mark_touched", "owner", "rebase", "take_touched", "touched"]
-
-_owner = WeakIdTable()    # parameter -> optimizer that defers its zero-gradient row steps
-_touched = WeakIdTable()  # parameter -> int64 ids of the rows written since the optimizer last stepped
-_hooks = WeakIdTable()    # parameter -> handle of the post-accumulate hook below
-_wrote = WeakIdTable()    # parameter -> True once AUTOGRAD has accumulated into .grad since the optimizer last stepped
-
-
-_marks = WeakIdTable()    # parameter -> [mark_touched calls, those of them whose rows a forward pass had made current] since the last step
-_base = WeakIdTable()     # parameter -> (data_ptr, version) of .grad when our own backward functions last looked at it
+__all__ = ["Link", "attach", "autograd_wrote", "detach", "mark_touched", "owner", "record", "touched"]
 
 
 def _sig(p):
@@ -77,77 +68,89 @@ def _sig(p):
     return None if g is None else (g.data_ptr(), g._version)
 
 
-def rebase(p):
-    """Called by a backward function that adds its rows straight into ``p.grad`` (``_gradshare.direct``): whatever autograd
-    accumulates into ``.grad`` behind it changes the tensor's version counter (or replaces the tensor)."""
-    _base[p] = _sig(p)
+class Link:
+    """One parameter's record: ``owner`` (the optimizer that defers its zero-gradient row steps), ``hook`` (the post-accumulate
+    hook's handle), ``base`` (``_sig`` of ``.grad`` when our own backward functions last looked at it) and, since ``owner`` last
+    stepped: ``touched`` (int64 ids of the rows written), ``marks`` / ``marks_current`` (``mark`` calls / those whose rows a forward
+    pass had made current), ``wrote`` (``autograd_wrote``).  Plain slots: the optimizer looks it up once and reads attributes."""
+
+    __slots__ = ("owner", "hook", "touched", "marks", "marks_current", "wrote", "base")
+
+    def __init__(self):
+        self.owner = self.hook = self.touched = self.base = None
+        self.marks, self.marks_current, self.wrote = 0, 0, False
+
+    def mark(self, ids, replace=False, current=False):
+        """Record the rows a backward pass wrote.  Several passes before one ``optimizer.step()`` accumulate: the lists are concatenated.
+        ``replace=True``: ``ids`` already covers everything pending (e.g. the all-gathered union of a data-parallel step)."""
+        prev = None if replace else self.touched
+        self.touched = ids if prev is None or prev is ids else torch.cat([prev, ids])
+        if replace:
+            self.marks = self.marks_current = 0
+        self.marks += 1
+        self.marks_current += 1 if current else 0
+
+    def all_marks_current(self):
+        """True if every ``mark`` since the last step said ``current=True``: the step need not visit the rows again first."""
+        return self.marks > 0 and self.marks == self.marks_current
+
+    def take_touched(self):  # the rows of the step that is being taken; the marks and the autograd-wrote flag start over
+        ids, self.touched, self.marks, self.marks_current, self.wrote = self.touched, None, 0, 0, False
+        return ids
+
+    def rebase(self, p):  # a backward function adds rows straight into p.grad: what AUTOGRAD adds behind it changes the version (or the tensor)
+        self.base = _sig(p)
+
+
+_table = WeakIdTable()  # parameter -> Link
+record = _table.get     # record(p): p's Link, or None when nothing was ever attached to or marked on it
+
+
+def _record(p):
+    rec = record(p)
+    if rec is None:
+        rec = _table[p] = Link()
+    return rec
 
 
 def _note_autograd_write(p):
     # torch calls the hook at the end of every backward pass that reaches the parameter -- also when every backward function
     # handed autograd ``None`` for it; only a pass that really changed .grad counts
-    if p not in _base or _base[p] != _sig(p):
-        _wrote[p] = True
+    rec = record(p)
+    if rec is not None and rec.base != _sig(p):
+        rec.wrote = True
 
 
 def autograd_wrote(p):
-    """True if torch's autograd has accumulated into ``p.grad`` since the optimizer last stepped / cleared it (any route:
-    ``model(sample, negatives, mode)`` + ``loss.backward()``, a regulariser on the table, ...).  The fused step bypasses autograd
-    and does not count.  A gradient row written that way is NOT all-zero, so the fused step's row kernels must accumulate into
-    it (``mkb_grads_t.rows_clear`` stays 0)."""
-    return bool(_wrote.get(p, False))
-
-
-def clear_autograd_wrote(p):
-    _wrote.pop(p, None)
+    """True if torch's autograd has accumulated into ``p.grad`` since the optimizer last stepped / cleared it (``loss.backward()``
+    behind ``model(...)``, a regulariser on the table, ...; the fused step bypasses autograd and does not count).  A gradient row
+    written that way is NOT all-zero, so the fused step's row kernels must accumulate into it (``mkb_grads_t.rows_clear`` stays 0)."""
+    rec = record(p)
+    return rec is not None and rec.wrote
 
 
 def owner(p):
-    return _owner.get(p)
+    rec = record(p)
+    return None if rec is None else rec.owner
 
 
 def attach(p, optimizer):
-    _owner[p] = optimizer
-    if p not in _hooks and hasattr(p, "register_post_accumulate_grad_hook"):
-        _hooks[p] = p.register_post_accumulate_grad_hook(_note_autograd_write)
+    rec = _record(p)
+    rec.owner = optimizer
+    if rec.hook is None and hasattr(p, "register_post_accumulate_grad_hook"):
+        rec.hook = p.register_post_accumulate_grad_hook(_note_autograd_write)
 
 
 def detach(p):
-    _owner.pop(p, None)
-    _touched.pop(p, None)
-    _wrote.pop(p, None)
-    _base.pop(p, None)
-    _marks.pop(p, None)
-    h = _hooks.pop(p, None)
-    if h is not None:
-        h.remove()
+    rec = _table.pop(p)  # owner, hook and every pending fact go with the record
+    if rec is not None and rec.hook is not None:
+        rec.hook.remove()
 
 
 def touched(p):
-    return _touched.get(p)
+    rec = record(p)
+    return None if rec is None else rec.touched
 
 
-def mark_touched(p, ids, replace=False, current=False):
-    """Record the rows a backward pass wrote.  Several backward passes before one ``optimizer.step()`` accumulate
-    (gradient accumulation): the lists are concatenated, so every written row takes the step and is cleared.
-    ``replace=True``: ``ids`` already covers everything pending (e.g. the all-gathered union of a data-parallel step)."""
-    prev = None if replace else _touched.get(p)
-    _touched[p] = ids if prev is None or prev is ids else torch.cat([prev, ids])
-    m = _marks.get(p)
-    if m is None or replace:
-        m = _marks[p] = [0, 0]
-    m[0] += 1
-    m[1] += 1 if current else 0
-
-
-def all_marks_current(p):
-    """True if every ``mark_touched`` since the last step said its rows had been made current through the optimizer's step
-    count in front of the forward pass that read them (``current=True``): the step need not visit them again first."""
-    m = _marks.get(p)
-    return m is not None and m[0] > 0 and m[0] == m[1]
-
-
-def take_touched(p):
-    _wrote.pop(p, None)
-    _marks.pop(p, None)
-    return _touched.pop(p, None)
+def mark_touched(p, ids, replace=False, current=False):  # Link.mark for callers outside the optimizer (tests, hand-written steps)
+    _record(p).mark(ids, replace, current)

@@ -84,8 +84,7 @@ class _PoolScoreFn(torch.autograd.Function):
         G = torch.zeros((B, 2 * K), dtype=torch.float32, device=ent.device)
         G.scatter_add_(1, info.pos.long(), _hip.contiguous(dneg, torch.float32))
         # (a row-lazy optimizer's table takes its rows straight into .grad: _gradshare.direct)
-        g_ent = _gradshare.direct(model.entity_embedding, ent, lambda: info.touched if info.touched is not None
-                                  else torch.cat([info.pool, sample[:, 0::2].reshape(-1)]))
+        g_ent = _gradshare.direct(model.entity_embedding, ent, lambda: info.rows(sample))
         fresh_e = False
         if g_ent is None:
             g_ent, fresh_e = _gradshare.take(model.entity_embedding, ent)  # (shared with the positive scores' backward of this pass)
@@ -110,6 +109,30 @@ def pooled_forward(model, sample, info, mode_id):
 PoolInfo.enabled = True
 
 
+def grad_buffers(model):
+    """``_hip.Grads`` of ``model``'s dense ``.grad`` tensors (allocated when missing: first step, ``zero_grad(set_to_none=True)``)."""
+    params = [model.entity_embedding, model.relation_embedding] + ([model.modulus] if model.name == "pRotatE" else [])
+    for p in params:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+    return _hip.Grads(*[p.grad.data_ptr() for p in params])  # (g_modulus stays NULL without a trained modulus)
+
+
+def sampled_step(step, sample, weight, sampler, mode, **kwargs):
+    """``step.sampled(...)``: ``step(sample, weight, sampler.generate(sample, mode), mode, **kwargs)`` with the sampler folded
+    into the optimizer's catch-up launch when the entity table of ``step.model`` steps row-lazily (``mkb_amd.optim.Adam(lazy_rows=
+    True)``): no sampler launch, identical negatives.  The negatives of the call stay available as ``step.negative_sample``."""
+    ent = step.model.entity_embedding
+    lazy = _links.owner(ent)
+    sample = _hip.contiguous(sample, torch.int64)
+    if lazy is not None and sampler.size <= 512 and sample.is_cuda:
+        neg = sampler.generate_with_catch_up(sample, mode, lazy, ent)
+    else:
+        neg = sampler.generate(sample=sample, mode=mode)
+    step.negative_sample = neg
+    return step(sample, weight, neg, mode, **kwargs)
+
+
 class FusedTrainStep:
     """``loss = step(sample, weight, negative_sample, mode)``: fills ``param.grad`` (dense, accumulated) and returns
     the loss as a 0-dim device tensor.  ``positive_score`` [B,1] and ``negative_score`` [B,size] of the last call
@@ -117,30 +140,9 @@ class FusedTrainStep:
 
     def __init__(self, model, alpha):
         self.model, self.alpha = model, float(alpha)
-        self._grads = None
-
-    def _grad_buffers(self):
-        m = self.model
-        params = [m.entity_embedding, m.relation_embedding] + ([m.modulus] if m.name == "pRotatE" else [])
-        for p in params:
-            if p.grad is None:  # first step, or the optimizer's zero_grad(set_to_none=True)
-                p.grad = torch.zeros_like(p)
-        return _hip.Grads(m.entity_embedding.grad.data_ptr(), m.relation_embedding.grad.data_ptr(),
-                          m.modulus.grad.data_ptr() if m.name == "pRotatE" else None)
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
-        """``step(sample, weight, sampler.generate(sample, mode), mode)`` with the sampler folded into the optimizer's
-        catch-up launch when the entity table steps row-lazily (``mkb_amd.optim.Adam(lazy_rows=True)``): no sampler
-        launch, identical negatives.  The negatives of the call stay available as ``self.negative_sample``."""
-        ent = self.model.entity_embedding
-        lazy = _links.owner(ent)
-        sample = _hip.contiguous(sample, torch.int64)
-        if lazy is not None and sampler.size <= 512 and sample.is_cuda:
-            neg = sampler.generate_with_catch_up(sample, mode, lazy, ent)
-        else:
-            neg = sampler.generate(sample=sample, mode=mode)
-        self.negative_sample = neg
-        return self(sample, weight, neg, mode, weight_sum=weight_sum)
+        return sampled_step(self, sample, weight, sampler, mode, weight_sum=weight_sum)
 
     def __call__(self, sample, weight, negative_sample, mode, weight_sum=None):
         """``weight_sum``: optional device scalar = sum of weights of the WHOLE batch when these rows are one
@@ -159,23 +161,11 @@ class FusedTrainStep:
         S = torch.empty((B, 2 * K), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         ws = _workspace(m, B, K)
-        gr = self._grad_buffers()
+        gr = grad_buffers(m)
         ent = m.entity_embedding
         lazy = _links.owner(ent)
-        if lazy is not None:  # row-lazy Adam: the rows this step reads must be current before the forward pass
-            ids = info.touched if info.touched is not None else torch.cat([info.pool, sample[:, 0], sample[:, 2]])
-            st = lazy._state(ent)
-            done = st.get("caught_up")
-            if done is None or done[0] is not ids or done[1] != st["n"]:  # (sampled() already did it)
-                lazy.catch_up(ent, ids)
-            # Deferred real step: that launch consumed AND cleared the gradient row of every row it visited (= every entity row
-            # this step writes), so unless an earlier backward of this same optimizer step has written since, those rows are
-            # all-zero: the row kernels may store instead of read-modify-write (mkb_grads_t.rows_clear)
-            # (autograd_wrote: an autograd backward of this same optimizer step has accumulated into .grad without marking rows)
-            if (st.get("defer") and st["n"] >= 1 and _links.touched(ent) is None and not _links.autograd_wrote(ent)
-                    and st.get("g") is not None and st["g"].data_ptr() == ent.grad.data_ptr()):
-                gr.rows_clear = 1
-            _links.mark_touched(ent, ids)  # accumulates when several steps share one optimizer.step()
+        if lazy is not None and lazy.begin_step_on(ent, info.rows(sample)):  # row-lazy Adam: the rows read become current first
+            gr.rows_clear = 1
         with _hip.on_device(dev):
             _hip.check(_hip.lib().mkb_pool_step(m._tables(), gr, _hip.ptr(sample), _hip.ptr(weight), _hip.ptr(info.pool),
                                                 _hip.ptr(info.cnt), B, K, mode_id, self.alpha, _hip.ptr(weight_sum),

@@ -179,24 +179,11 @@ class BaseModel(Base):
                 opt.flush(p)
 
     def _make_current(self, sample, entity_ids):
-        """In front of a forward pass: the rows it reads are brought up to date when a row-lazy optimizer steps the tables
-        (``entity_ids``: int64 ids, duplicates allowed; ``None`` = too many to list: the whole table is flushed).  One small
-        launch per table with something pending -- the whole-table flush this replaces was 150 us per ``model(...)`` call at
-        the headline shape."""
+        """``optim.Adam.before_forward`` for the tables a row-lazy optimizer steps (the flush this replaces was 150 us per call)."""
         for p, ids in ((self.entity_embedding, entity_ids), (self.relation_embedding, False)):
             opt = _links.owner(p)
-            if opt is None:
-                continue
-            st = opt._state(p)
-            st["fwd_n"] = st["n"]  # (the rows read at this step count are current from here on: _gradshare.direct)
-            if st["n"] <= 0 or st.get("flushed") == st["n"]:
-                continue  # nothing pending
-            if ids is False:
-                ids = sample[:, 1]
-            if ids is None:
-                opt.flush(p)
-            else:
-                opt.catch_up(p, ids)
+            if opt is not None:
+                opt.before_forward(p, sample[:, 1] if ids is False else ids)
 
     # ------------------------------------------------------------------ reference API
     @property
@@ -253,8 +240,7 @@ class BaseModel(Base):
             if pooled is not None and pooled.usable_for(self, sample, mode_id):
                 from ..fused import pooled_forward
                 if lazy:
-                    self._make_current(sample, pooled.touched if pooled.touched is not None
-                                       else torch.cat([pooled.pool, _read_entity_ids(sample)]))
+                    self._make_current(sample, pooled.rows(sample))
                 return pooled_forward(self, sample, pooled, mode_id).view(shape)
             cand = _hip.contiguous(negative_sample, torch.int64)
         if lazy:

@@ -22,8 +22,8 @@ the second pass over p / m / v of every touched row (``mkb_adam_rows_step``) dis
 order: still bit-identical to dense Adam after ``flush()``.  The small dense parameters that rode the step launch (the
 relation table) ride the next catch-up launch instead, so with ``defer_step`` they too are only current after
 ``flush()``.  Contract: clear gradients through ``optimizer.zero_grad()`` only (``model.zero_grad()`` /
-``p.grad.zero_()`` would erase a step that has not been applied yet), and let every backward pass that writes the
-table's gradient be preceded by ``catch_up`` of its rows (``FusedTrainStep`` / ``parallel.DimShardedStep`` do).
+``p.grad.zero_()`` would erase a step that has not been applied yet), and let every step that reads a row-lazy table keep to
+"the protocol" below (the step classes and ``model(...)`` do): rows current before the forward pass, then their gradient, then the report.
 """
 import torch
 
@@ -115,35 +115,71 @@ class Adam:
         n_loc = 0 if local_ids is None else local_ids.numel()
         return world, rank, _hip.ptr(local_ids) if n_loc else None, n_loc
 
-    def catch_up_sharded(self, p, global_ids, world, rank, local_ids):
+    def catch_up_sharded(self, p, global_ids, world, rank, local_ids, listed_as=None):
         """``catch_up`` for a ROW SHARD of a table (``mkb_amd.table_rows``): the rows to make current are the entries of
         ``global_ids`` this rank owns (``e % world == rank``, shard index ``e // world``) plus the shard indices
-        ``local_ids``; one launch, no id list is materialised on the way."""
+        ``local_ids``; one launch, no id list.  ``listed_as``: the tensor the caller will report them with, recorded as what
+        was caught up -- also when no step has been taken yet and nothing is launched."""
         st = self._state(p)
         upto = st["n"]
+        st["caught_up"] = (listed_as, upto)
         if upto <= 0:
             return
-        st["caught_up"] = (None, upto)
         self._advance(p, st, upto, (_hip.ptr(global_ids), global_ids.numel(), *self._shard_rows(world, rank, local_ids)),
                       draw_ahead=self._sampler_handle(p.device))
 
-    def catch_up_sharded_generate(self, p, world, rank, local_ids, sampler_handle, sample, B, mode_id, neg, pool, pos, cnt, touched):
-        """``catch_up_sharded(p, the sampler's pool, world, rank, local_ids)`` fused with the sampler's filter of this rank's rows
-        and the draw of the next pool: one launch (``mkb_adam_rows_advance_generate`` at ``world >= 1``)."""
+    def catch_up_with_sampler(self, p, shard, sampler_handle, sample, mode_id, outputs, listed_as=None):
+        """``catch_up(p, rows of this batch)`` (``shard = (world, rank, local_ids)``: ``catch_up_sharded(p, the pool, *shard)``) in ONE
+        launch with the sampler's filter and next draw (``mkb_adam_rows_advance_generate``; ``NegativeSampling.generate_with_catch_up``)."""
         st = self._state(p)
-        st["caught_up"] = (None, st["n"])
-        self._advance(p, st, st["n"], self._shard_rows(world, rank, local_ids),
-                      (sampler_handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg), _hip.ptr(pool), _hip.ptr(pos), _hip.ptr(cnt),
-                       _hip.ptr(touched)))
+        st["caught_up"] = (listed_as, st["n"])
+        self._advance(p, st, st["n"], (0, 0, None, 0) if shard is None else self._shard_rows(*shard),
+                      (sampler_handle, _hip.ptr(sample), sample.shape[0], mode_id, *[_hip.ptr(t) for t in outputs]))
 
-    def catch_up_generate(self, p, sampler_handle, sample, B, mode_id, neg, pool, pos, cnt, touched):
-        """``catch_up(p, rows of this batch)`` fused with the sampler's filter + next-pool draw (one launch; see
-        ``sampling.NegativeSampling.generate_with_catch_up``)."""
+    # --------------------------------------------- the protocol (DESIGN.md); only it touches caught_up, fwd_n, defer, g, lrs, flushed
+    @staticmethod
+    def _caught_up(st, ids, n):  # the last catch-up recorded was of this very tensor (identity: no device sync) through n
+        done = st.get("caught_up")
+        return done is not None and done[0] is ids and done[1] == n
+
+    def ensure_current(self, p, ids):
+        """``catch_up(p, ids)`` unless the last catch-up at this step count did that (e.g. folded into the sampler's launch)."""
         st = self._state(p)
-        self._advance(p, st, st["n"], (0, 0, None, 0),
-                      (sampler_handle, _hip.ptr(sample), B, mode_id, _hip.ptr(neg), _hip.ptr(pool), _hip.ptr(pos), _hip.ptr(cnt),
-                       _hip.ptr(touched)))
-        st["caught_up"] = (touched, st["n"])
+        if not self._caught_up(st, ids, st["n"]):
+            self.catch_up(p, ids)
+
+    def begin_step_on(self, p, ids):
+        """In front of a fused step that reads the rows ``ids`` of ``p`` and adds to their rows of ``p.grad``: they become current
+        and are marked as written.  -> ``mkb_grads_t.rows_clear``: those gradient rows are all-zero, the kernels may store."""
+        st, rec = self._state(p), _links.record(p)
+        if not self._caught_up(st, ids, st["n"]):
+            self.catch_up(p, ids)
+        # Deferred real step: that launch consumed AND cleared the gradient row of every row this step writes, so unless an earlier
+        # backward of this optimizer step has written since (marked rows, or autograd, which marks none) they are all-zero.  Read BEFORE the mark.
+        clear = bool(st.get("defer") and st["n"] >= 1 and rec.touched is None and not rec.wrote
+                     and st.get("g") is not None and st["g"].data_ptr() == p.grad.data_ptr())
+        rec.mark(ids)  # accumulates when several steps share one optimizer.step()
+        return clear
+
+    def before_forward(self, p, ids):
+        """In front of a forward pass that reads the rows ``ids`` of ``p`` (``None`` = too many to list: the whole table is flushed)."""
+        st = self._state(p)
+        st["fwd_n"] = st["n"]  # (the rows read at this step count are current from here on: rows_written(after_forward=True))
+        if st["n"] <= 0 or st.get("flushed") == st["n"]:
+            return  # nothing pending
+        if ids is None:
+            self.flush(p)
+        else:
+            self.catch_up(p, ids)
+
+    def rows_written(self, p, ids, after_forward=False, replace=False):
+        """Report the rows a backward pass wrote into ``p.grad`` (``_links.Link.mark``).  ``after_forward``: behind autograd's back
+        (``_gradshare.direct``); if ``before_forward`` ran at this step count, ``step()`` need not make the rows current first."""
+        rec = _links.record(p)
+        st = self._state(p) if after_forward else None
+        rec.mark(ids, replace, after_forward and st.get("fwd_n") == st["n"])
+        if after_forward:
+            rec.rebase(p)
 
     def flush(self, p=None):
         """Replay everything that is pending: afterwards the tables equal what dense Adam would hold."""
@@ -171,15 +207,20 @@ class Adam:
             st.pop("defer", None)
 
     # ------------------------------------------------------------------ torch.optim-like API
+    def _link(self, p):  # p's _links record when this optimizer steps it row-lazily, else None (one lookup, then attribute reads)
+        rec = _links.record(p)
+        return rec if rec is not None and rec.owner is self else None
+
     def _rider(self):
         """The dense tensor that steps inside the row-lazy launch (one fewer kernel per step): the first dense,
         16-byte aligned float32 parameter with a gradient, when some table steps row-lazily this time."""
-        lazy = [p for p in self.params if p.grad is not None and _links.owner(p) is self and _links.touched(p) is not None
-                and not _links.autograd_wrote(p)]  # (autograd wrote as well: that table takes the dense route this time)
+        links = [self._link(p) for p in self.params]
+        lazy = [p for p, rec in zip(self.params, links) if p.grad is not None and rec is not None and rec.touched is not None
+                and not rec.wrote]  # (autograd wrote as well: that table takes the dense route this time)
         if len(lazy) != 1:
             return None, None
-        for q in self.params:
-            if (q.grad is not None and _links.owner(q) is not self and q.is_cuda and q.device == lazy[0].device
+        for q, rec in zip(self.params, links):
+            if (q.grad is not None and rec is None and q.is_cuda and q.device == lazy[0].device
                     and q.dtype == torch.float32 and q.is_contiguous() and q.grad.is_contiguous() and q.numel() >= 4
                     and "last" not in self._state(q)):
                 st = self._state(q)
@@ -210,11 +251,12 @@ class Adam:
             g = p.grad
             if not g.is_contiguous():
                 g = p.grad = g.contiguous()
-            wrote = _links.autograd_wrote(p)
-            current = _links.all_marks_current(p)  # (every row was made current by the forward pass that read it)
-            touched = _links.take_touched(p) if _links.owner(p) is self else None
-            if wrote:  # autograd accumulated into .grad in this step as well: which rows is unknown -> the dense route below
-                touched = None
+            touched, rec = None, self._link(p)
+            if rec is not None:
+                current = rec.all_marks_current()  # (every row was made current by the forward pass that read it)
+                wrote, touched = rec.wrote, rec.take_touched()
+                if wrote:  # autograd accumulated into .grad in this step as well: which rows is unknown -> the dense route below
+                    touched = None
             with _hip.on_device(p.device):
                 if touched is not None:
                     done = st.get("caught_up")
@@ -237,7 +279,7 @@ class Adam:
                     st["n"] += 1
                     ids = _hip.contiguous(touched, torch.int64)
                     c = self._consts(st, st["n"])
-                    if not current and (done is None or done[0] is not touched or done[1] != st["n"] - 1):
+                    if not current and not self._caught_up(st, touched, st["n"] - 1):
                         self.catch_up(p, ids, upto=st["n"] - 1)  # e.g. rows only OTHER data-parallel ranks touched
                     _hip.check(lib.mkb_adam_rows_step(_hip.ptr(p.data), _hip.ptr(g), _hip.ptr(st["m"]), _hip.ptr(st["v"]),
                                                       _hip.ptr(st["last"]), _hip.ptr(c), p.shape[0], p.shape[1],
@@ -280,7 +322,9 @@ class Adam:
         if any(st.get("defer") for st in self.state.values()):
             self.flush()  # a deferred step lives in the gradient rows: apply it before they are really cleared
         for p in self.params:
-            _links.clear_autograd_wrote(p)
+            rec = _links.record(p)
+            if rec is not None:
+                rec.wrote = False
             if p.grad is not None:
                 if set_to_none:
                     p.grad = None

@@ -116,9 +116,10 @@ class SparseGradExchange:
         extras.extend(extra_scalars)
         self.last_rows_moved = allreduce_touched_rows(m.entity_embedding.grad, ids, extras, self.group,
                                                       equal_counts=self.equal_batches)
-        if _links.owner(m.entity_embedding) is not None:
+        opt = _links.owner(m.entity_embedding)
+        if opt is not None:
             # row-lazy Adam must step every row ANY rank touched: hand it the gathered id list
-            _links.mark_touched(m.entity_embedding, self.last_union, replace=True)
+            opt.rows_written(m.entity_embedding, self.last_union, replace=True)
 
     @property
     def last_union(self):
@@ -221,26 +222,16 @@ class DimShardedStep:
     [fwd 0][fwd 1 | all-reduce 0][bwd 0 | all-reduce 1][bwd 1].  The loss normaliser W is the whole batch's."""
 
     def __init__(self, local_model, alpha, group=None, micro_batches=None):
-        from . import _hip
-        from .fused import _workspace
+        from . import _hip, fused
 
-        self._hip, self._workspace = _hip, _workspace
+        self._hip, self._fused = _hip, fused
         self.model, self.alpha, self.group = local_model, float(alpha), group
         self.rank, self.world, self.gamma, self.uses_gamma = local_model._dim_shard
         self.micro_batches = (2 if self.world > 1 else 1) if micro_batches is None else micro_batches
 
     def sampled(self, sample, weight, sampler, mode):
-        """``step(sample, weight, sampler.generate(sample, mode), mode)`` with the sampler folded into the row-lazy
-        optimizer's catch-up launch (see ``FusedTrainStep.sampled``); every rank draws the same negatives."""
-        ent = self.model.entity_embedding
-        lazy = _links.owner(ent)
-        sample = self._hip.contiguous(sample, torch.int64)
-        if lazy is not None and sampler.size <= 512 and sample.is_cuda:
-            neg = sampler.generate_with_catch_up(sample, mode, lazy, ent)
-        else:
-            neg = sampler.generate(sample=sample, mode=mode)
-        self.negative_sample = neg
-        return self(sample, weight, neg, mode)
+        """``fused.sampled_step``: the sampler rides the row-lazy optimizer's catch-up launch; every rank draws the same negatives."""
+        return self._fused.sampled_step(self, sample, weight, sampler, mode)
 
     def __call__(self, sample, weight, negative_sample, mode):
         _hip, m = self._hip, self.model
@@ -250,20 +241,11 @@ class DimShardedStep:
         weight = _hip.contiguous(weight, torch.float32)
         B, K = sample.shape[0], info.size
         dev = sample.device
-        params = [m.entity_embedding, m.relation_embedding] + ([m.modulus] if m.name == "pRotatE" else [])
-        for p in params:
-            if p.grad is None:
-                p.grad = torch.zeros_like(p)
-        gr = _hip.Grads(m.entity_embedding.grad.data_ptr(), m.relation_embedding.grad.data_ptr(),
-                        m.modulus.grad.data_ptr() if m.name == "pRotatE" else None)
+        gr = self._fused.grad_buffers(m)
         ent = m.entity_embedding
         lazy = _links.owner(ent)
-        if lazy is not None:
-            ids = info.touched if info.touched is not None else torch.cat([info.pool, sample[:, 0], sample[:, 2]])
-            done = lazy._state(ent).get("caught_up")
-            if done is None or done[0] is not ids or done[1] != lazy._state(ent)["n"]:  # (sampled() already did it)
-                lazy.catch_up(ent, ids)
-            _links.mark_touched(ent, ids)
+        if lazy is not None:  # (what it returns, rows_clear, is not used by this step)
+            lazy.begin_step_on(ent, info.rows(sample))
         lib, tb = _hip.lib(), m._tables()
         nmb = max(1, min(self.micro_batches, B // 8))
         bounds = [(B * i // nmb, B * (i + 1) // nmb) for i in range(nmb)]
@@ -274,7 +256,7 @@ class DimShardedStep:
                 b = hi - lo
                 scores = torch.empty(b * (2 * K + 1), dtype=torch.float32, device=dev)  # [pos | pool]: one collective
                 pos, S = scores[:b], scores[b:].view(b, 2 * K)
-                ws = self._workspace(m, b, K, slot=len(parts))
+                ws = self._fused._workspace(m, b, K, slot=len(parts))
                 _hip.check(lib.mkb_pool_step_fwd(tb, _hip.ptr(sample[lo:hi]), _hip.ptr(info.pool), _hip.ptr(info.cnt[lo:hi]),
                                                  b, K, mode_id, _hip.ptr(pos), _hip.ptr(S), _hip.ptr(ws),
                                                  _hip.stream_ptr()), "mkb_pool_step_fwd")

@@ -68,10 +68,14 @@ class PoolInfo:
 
     enabled = False  # flipped on by mkb_amd.fused once the pooled kernels are loaded
 
-    def __init__(self, pool, pos, cnt, size, mode_id, sample):
+    def __init__(self, pool, pos, cnt, size, mode_id, sample, touched=None):
         self.pool, self.pos, self.cnt, self.size, self.mode_id = pool, pos, cnt, size, mode_id
         self.sample_ptr, self.batch = sample.data_ptr(), sample.shape[0]
-        self.touched = None  # [2K + 2B] entity rows a step on this batch reads: pool | heads | tails
+        self.touched = touched  # [2K + 2B] entity rows a step on this batch reads, when the sampler listed them: pool | heads | tails
+
+    def rows(self, sample):
+        """int64 ids (duplicates allowed) of the entity rows a step on this batch reads and writes: pool | heads | tails."""
+        return self.touched if self.touched is not None else torch.cat([self.pool, sample[:, 0], sample[:, 2]])
 
     @classmethod
     def discover(cls, negative_sample, sample, mode_id):
@@ -174,29 +178,23 @@ class NegativeSampling:
         if origin != dev:
             self.check()
             return neg.to(origin)
-        neg._mkb_pool = PoolInfo(pool, pos, cnt, self.size, mode_id, sample)
-        neg._mkb_pool.touched = touched
+        neg._mkb_pool = PoolInfo(pool, pos, cnt, self.size, mode_id, sample, touched)
         return neg
 
-    def _generate_riding(self, sample, mode, optimizer, param, shard=None):
+    def _generate_riding(self, sample, mode, optimizer, param, shard=None, listed_as=None):
         """``generate`` inside ``optimizer``'s catch-up launch for ``param``; ``shard``: None, or (world, rank, local_ids) when
-        ``param`` is a row shard."""
+        ``param`` is a row shard, whose caller lists the rows it will report as ``listed_as``."""
         if mode not in ("head-batch", "tail-batch"):
             raise ValueError("mode must be 'head-batch' or 'tail-batch'")
         sample = _hip.contiguous(sample, torch.int64)
         _hip.require_device(param, sample)
         dev = sample.device
         self._ensure_handle(dev)
-        B = sample.shape[0]
-        neg, pool, pos, cnt, touched = self._outputs(B, dev)
+        outputs = neg, pool, pos, cnt, touched = self._outputs(sample.shape[0], dev)
         mode_id = _hip.mode_id(mode)
-        if shard is None:
-            optimizer.catch_up_generate(param, self._handle, sample, B, mode_id, neg, pool, pos, cnt, touched)
-        else:
-            optimizer.catch_up_sharded_generate(param, *shard, self._handle, sample, B, mode_id, neg, pool, pos, cnt, touched)
-        neg._mkb_pool = PoolInfo(pool, pos, cnt, self.size, mode_id, sample)
-        if shard is None:  # (a shard's list holds global ids: its caller lists the shard's rows itself)
-            neg._mkb_pool.touched = touched
+        optimizer.catch_up_with_sampler(param, shard, self._handle, sample, mode_id, outputs, touched if shard is None else listed_as)
+        # (a shard's list holds global ids: its caller lists the shard's rows itself)
+        neg._mkb_pool = PoolInfo(pool, pos, cnt, self.size, mode_id, sample, touched if shard is None else None)
         return neg
 
     def generate_with_catch_up(self, sample, mode, optimizer, param):
@@ -206,11 +204,11 @@ class NegativeSampling:
         and multiplicities, bit for bit, as ``generate``."""
         return self._generate_riding(sample, mode, optimizer, param)
 
-    def generate_with_sharded_catch_up(self, sample, mode, optimizer, param, world, rank, local_ids):
+    def generate_with_sharded_catch_up(self, sample, mode, optimizer, param, world, rank, local_ids, listed_as=None):
         """``generate(sample, mode)`` for this rank's rows of a global batch and ``optimizer.catch_up_sharded(param, pool, world,
-        rank, local_ids)`` for a ROW SHARD of the entity table (``mkb_amd.table_rows``) as one launch that also draws the next
-        pool.  Same negatives, pool and multiplicities, bit for bit, as ``generate``."""
-        return self._generate_riding(sample, mode, optimizer, param, (world, rank, local_ids))
+        rank, local_ids, listed_as)`` for a ROW SHARD of the entity table (``mkb_amd.table_rows``) as one launch that also draws
+        the next pool.  Same negatives, pool and multiplicities, bit for bit, as ``generate``."""
+        return self._generate_riding(sample, mode, optimizer, param, (world, rank, local_ids), listed_as)
 
     def check(self):
         """Raise what the reference would have raised for the batches generated so far (synchronises)."""

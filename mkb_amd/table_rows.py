@@ -677,13 +677,12 @@ class TableRowShardedStep:
         if self._occ is None or self._occ.device != dev:
             self._occ = torch.zeros(tb.data.shape[0], dtype=torch.int32, device=dev)
         if _sampler is not None:  # sampler + catch-up of [owned pool rows | requested rows] in one launch
-            negative_sample = _sampler.generate_with_sharded_catch_up(sample, mode, opt, tb.data, self.world, tb.rank, want)
+            negative_sample = _sampler.generate_with_sharded_catch_up(sample, mode, opt, tb.data, self.world, tb.rank, want,
+                                                                      listed_as=touched)
             self.negative_sample = negative_sample
-            opt._state(tb.data)["caught_up"] = (touched, opt._state(tb.data)["n"])
         info = negative_sample._mkb_pool
         if opt is not None and _sampler is None:
-            opt.catch_up_sharded(tb.data, info.pool, self.world, self.rank_of_table, want)
-            opt._state(tb.data)["caught_up"] = (touched, opt._state(tb.data)["n"])
+            opt.catch_up_sharded(tb.data, info.pool, self.world, self.rank_of_table, want, listed_as=touched)
         # (one rank and no forced collectives: the all-to-alls are the identity -- the owner IS the user --, so the rows are
         # read straight into the compact table and their gradients taken straight from it: no stand-in copies)
         direct = not _collectives_run(self.world)
@@ -733,7 +732,7 @@ class TableRowShardedStep:
                 mod.grad = torch.zeros_like(mod)
             mod.grad.add_(bufs["g_mod"].view_as(mod.grad))
         if opt is not None:
-            _links.mark_touched(tb.data, touched)
+            opt.rows_written(tb.data, touched)
         return loss.reshape(())
 
     def check(self):

@@ -392,3 +392,85 @@ def test_readme_loop_keeps_the_row_lazy_route(name, defer, monkeypatch):
     for x, y in zip(got[:2], ref[:2]):
         assert torch.allclose(x, y, rtol=0, atol=3e-4), float((x - y).abs().max())
         assert float((x - y).abs().mean()) < 2e-6, float((x - y).abs().mean())
+
+
+@pytest.mark.parametrize("defer", [True, False])
+def test_ensure_current_launches_once_per_id_tensor_and_step_count(defer):
+    """``ensure_current`` is the idempotent ``catch_up``: nothing is launched when the last catch-up was of this very tensor
+    (identity: equal contents are another tensor) at this step count.  Then the fused step: ``sampled()`` folds the catch-up into
+    the sampler's launch and ``__call__`` must recognise the sampler's row list, so one advance launch per optimizer step."""
+    from mkb_amd import models, optim, sampling
+    from mkb_amd.fused import FusedTrainStep, pooled_supported
+
+    def count(opt):
+        calls, inner = [], opt._advance
+        opt._advance = lambda *a, **k: (calls.append(1), inner(*a, **k))[1]
+        return calls
+
+    ent, rel = _tables()
+    opt = optim.Adam([ent, rel], lr=1e-2, lazy_rows=True, defer_step=defer)
+    _synthetic_steps(opt, ent, rel, range(1))
+    calls = count(opt)
+    ids = torch.randint(ent.shape[0], (300,), generator=torch.Generator().manual_seed(3)).cuda()
+    opt.ensure_current(ent, ids)
+    opt.ensure_current(ent, ids)
+    assert len(calls) == 1
+    opt.ensure_current(ent, ids.clone())
+    assert len(calls) == 2
+    opt.ensure_current(ent, ids)  # (the record is of the clone now)
+    assert len(calls) == 3
+    opt.ensure_current(ent, ids)
+    assert len(calls) == 3
+    ent.grad[torch.unique(ids)] += 1.0
+    opt.rows_written(ent, ids)
+    opt.step()
+    opt.zero_grad()
+    del calls[:]
+    opt.ensure_current(ent, ids)
+    assert len(calls) == 1
+
+    N, R = 5000, 4
+    ents, rels = {i: i for i in range(N)}, {i: i for i in range(R)}
+    rs = np.random.RandomState(1)
+    train = np.stack([rs.randint(N, size=3000), rs.randint(R, size=3000), rs.randint(N, size=3000)], 1)
+    t = torch.as_tensor(train).cuda()
+    torch.manual_seed(3)
+    m = models.TransE(hidden_dim=16, entities=ents, relations=rels, gamma=6.0).cuda()
+    assert pooled_supported(m, 32, 16)
+    ns = sampling.NegativeSampling(size=16, train_triples=train, entities=ents, relations=rels, seed=1)
+    opt = optim.Adam([m.entity_embedding, m.relation_embedding], lr=1e-2, lazy_rows=True, draw_ahead=ns, defer_step=defer)
+    calls = count(opt)
+    step = FusedTrainStep(m, 1.0)
+    for it in range(3):
+        step.sampled(t[it * 32: (it + 1) * 32].contiguous(), torch.ones(32, device="cuda"), ns, "tail-batch" if it % 2 else "head-batch")
+        opt.step()
+        opt.zero_grad()
+        assert len(calls) == it + 1, (it, len(calls))
+
+
+@pytest.mark.parametrize("d", [64, 33])
+def test_detach_and_attach_round_trip_keeps_the_row_lazy_state(d):
+    """What the benchmark does around its dense-gradient loops: ``_links.detach`` + ``_links.attach`` of a flushed table drop
+    what was pending in the links and nothing of the optimizer's state: the run goes on row-lazily, bit for bit."""
+    from mkb_amd import _links, optim
+
+    out = []
+    for round_trip in (False, True):
+        ent, rel = _tables(d=d)
+        opt = optim.Adam([ent, rel], lr=1e-2, lazy_rows=True, defer_step=True)
+
+        def on_step(it):
+            if round_trip and it == 3:
+                opt.flush()
+                owner = _links.owner(ent)
+                assert owner is opt
+                _links.detach(ent)
+                assert _links.owner(ent) is None
+                _links.attach(ent, owner)
+
+        _synthetic_steps(opt, ent, rel, range(8), on_step=on_step)
+        assert "last" in opt.state[ent] and _links.owner(ent) is opt, "the optimizer fell back to the dense kernel"
+        opt.flush()
+        out.append((ent.detach().clone(), rel.detach().clone(), opt.state[ent]["m"].clone(), opt.state[ent]["v"].clone()))
+    for a, b in zip(*out):
+        assert torch.equal(a, b)

@@ -102,8 +102,7 @@ def test_sharded_catch_up_is_the_plain_catch_up_on_the_materialised_list(defer):
             mine = (pool % world) == rank
             ids = torch.cat([torch.where(mine, pool // world, torch.full_like(pool, -1)), want])
             if sharded:
-                opt.catch_up_sharded(p, pool, world, rank, want)
-                opt._state(p)["caught_up"] = (ids, opt._state(p)["n"])
+                opt.catch_up_sharded(p, pool, world, rank, want, listed_as=ids)
             else:
                 opt.catch_up(p, ids)   # (negative entries are skipped by the kernels)
             rows = torch.unique(ids[ids >= 0])

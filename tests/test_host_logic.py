@@ -225,6 +225,80 @@ def test_weak_id_table_is_keyed_by_identity_and_forgets_dead_parameters():
     assert len(t) == 0
 
 
+def test_links_record_keeps_one_parameters_pending_facts_and_drops_them_together():
+    """mkb_amd._links: one record per parameter (owner, touched rows, the marks, the autograd-wrote flag, the ``.grad`` signature,
+    the hook).  On CPU parameters, no optimizer needed: the owner is any object."""
+    import gc
+
+    from mkb_amd import _links
+
+    owner = object()
+    p = torch.nn.Parameter(torch.zeros(6, 2))
+    before = len(_links._table)
+    _links.attach(p, owner)
+    rec = _links.record(p)
+    assert _links.owner(p) is owner and len(_links._table) == before + 1
+    assert _links.touched(p) is None and not _links.autograd_wrote(p) and not rec.all_marks_current()
+    # rows accumulate across calls (the same tensor again is not repeated), replace=True starts over
+    a, b = torch.tensor([0, 1]), torch.tensor([1, 4])
+    _links.mark_touched(p, a, current=True)
+    assert _links.touched(p) is a and rec.all_marks_current()
+    _links.mark_touched(p, a, current=True)
+    assert _links.touched(p) is a
+    _links.mark_touched(p, b)
+    assert torch.equal(_links.touched(p), torch.tensor([0, 1, 1, 4])) and not rec.all_marks_current()  # one mark was not current
+    _links.mark_touched(p, b, replace=True, current=True)
+    assert _links.touched(p) is b and rec.all_marks_current()
+    # the hook: a real backward into .grad counts ...
+    (p * 2.0).sum().backward()
+    assert _links.autograd_wrote(p)
+    assert rec.take_touched() is b
+    assert _links.touched(p) is None and not _links.autograd_wrote(p) and not rec.all_marks_current() and rec.marks == 0
+    # ... a backward pass that reaches the parameter but hands autograd None for it (the rows went straight into .grad) does not
+
+    class Direct(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x.sum()
+
+        @staticmethod
+        def backward(ctx, g):
+            rec.rebase(p)
+            return None
+
+    Direct.apply(p).backward()
+    assert not _links.autograd_wrote(p)
+    (Direct.apply(p) + p.sum()).backward()  # another contributor in the same pass does change .grad
+    assert _links.autograd_wrote(p)
+    # detach: nothing is left, and a backward pass no longer reports; attach again: a fresh record, the hook is back
+    _links.mark_touched(p, a)
+    _links.detach(p)
+    assert _links.record(p) is None and _links.owner(p) is None and _links.touched(p) is None and not _links.autograd_wrote(p)
+    assert len(_links._table) == before
+    p.sum().backward()
+    assert not _links.autograd_wrote(p) and _links.record(p) is None
+    _links.attach(p, owner)
+    assert _links.record(p) is not rec and _links.owner(p) is owner and _links.touched(p) is None and not _links.autograd_wrote(p)
+    p.sum().backward()
+    assert _links.autograd_wrote(p)
+    # a dead parameter's record goes with it
+    assert len(_links._table) == before + 1
+    del p, Direct
+    gc.collect()
+    assert len(_links._table) == before
+
+
+def test_only_the_optimizer_reads_or_writes_the_row_lazy_protocol_state():
+    """A step that reads a row-lazily stepped table goes through the methods of ``mkb_amd.optim.Adam`` ("What a step
+    that reads a row-lazy table must call"): no other module of the package reaches into the optimizer's per-parameter dict."""
+    from conftest import ROOT
+
+    banned = ("._state(", '["caught_up"]', '["fwd_n"]', '["defer"]', '["flushed"]')
+    found = [(str(src.relative_to(ROOT)), word) for src in sorted((ROOT / "mkb_amd").rglob("*.py")) if src.name != "optim.py"
+             for word in banned if word in src.read_text()]
+    assert not found, found
+
+
 def test_pipeline_host_stager_is_a_plain_copy_off_the_gpu():
     """compose.pipeline._HostStager stages host batches through page-locked buffers for a ROCm device; for any other device (the
     reference's default device="cpu") it must be the plain ``.to(device)`` of the reference's loop."""
