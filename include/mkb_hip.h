@@ -418,6 +418,27 @@ int mkb_topk_nearest(const float *Q, int64_t ldq, const float *X, int64_t ldx, c
 int mkb_topk_nearest_dists(const float *Q, int64_t ldq, const float *X, int64_t ldx, const int64_t *cand, int64_t n_cand, int64_t B,
                            int64_t D, int k, int64_t *ids, float *dists, float *block, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- grouped evaluation report ---------------------------------------------------------------------------
+ * The two reductions behind evaluation.Evaluation.types_relations / detail_eval (evaluation/evaluation.py:282-464).  Neither
+ * needs a workspace; n == 0 (or an empty key array) is a valid call that writes zeros; integer atomics and a fixed-order
+ * double sum only, so two runs give bit-identical output.  A non-positive table size, a negative count, or a null pointer
+ * with a non-zero count -> MKB_ERR_INVALID before any launch.
+ *
+ * mkb_relation_fanout: what types_relations' two pandas group-bys count.  triples [n, 3] int64: the true triples as given,
+ * duplicates included; head_keys [n_head] / tail_keys [n_tail]: the ascending, deduplicated keys of mkb_rank
+ * ((t*n_relation + r)*n_entity + h and (h*n_relation + r)*n_entity + t).  counts [n_relation, 3] int64 out, per relation r:
+ * the triples with relation r (with multiplicity), the distinct (t, r) pairs (boundaries of key / n_entity in head_keys,
+ * bucketed by (key / n_entity) % n_relation), the distinct (h, r) pairs (the same from tail_keys).  A relation id outside
+ * [0, n_relation) is not counted. */
+int mkb_relation_fanout(const int64_t *triples, int64_t n, const int64_t *head_keys, int64_t n_head, const int64_t *tail_keys,
+                        int64_t n_tail, int64_t n_entity, int64_t n_relation, int64_t *counts, void *stream);
+/* mkb_rank_metrics: the five running means of compute_detailled_score as sums per group.  ranks [n] int64 (1-based) belong to
+ * sample [n, 3]; item i is of group group_of_relation[sample[i][1]] ([n_relation] int32; negative, or >= n_groups: the item is
+ * left out).  counts [n_groups, 5] int64 out: items, sum of ranks, ranks <= 1, <= 3, <= 10; rr_sum [n_groups] double out: sum
+ * of 1 / rank.  One workgroup per group strides over all n items: meant for a whole test split and n_groups = 4 or n_relation. */
+int mkb_rank_metrics(const int64_t *ranks, const int64_t *sample, int64_t n, const int32_t *group_of_relation, int64_t n_relation,
+                     int n_groups, int64_t *counts, double *rr_sum, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

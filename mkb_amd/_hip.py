@@ -139,6 +139,8 @@ _SIGNATURES = {
                                  c_void_p, c_int64, c_void_p]),
     "mkb_topk_nearest_dists": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_relation_fanout": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "mkb_rank_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -40,6 +40,20 @@ def _report(metrics, suffix=""):
     return {f"{name}{suffix}": round(metric.get(), 4) for name, metric in metrics.items()}
 
 
+_MODES = ("head-batch", "tail-batch")
+_TYPES = ("1_1", "1_M", "M_1", "M_M")
+_METRICS = ("MRR", "MR", "HITS@1", "HITS@3", "HITS@10")
+_FANOUT_CACHE = []  # [(true_triples, len, device or None, n_entity, n_relation, counts)], most recent first
+
+
+def _from_sums(counts, rr_sum):
+    """The five rounded metrics of one group from ``mkb_rank_metrics``' sums (items, rank sum, ranks <= 1, <= 3, <= 10; sum of
+    1 / rank); 0.0 for a group without items, like a fresh ``Mean``."""
+    n = int(counts[0])
+    means = [float(rr_sum) / n] + [int(c) / n for c in counts[1:]] if n else [0.0] * 5
+    return {name: round(value, 4) for name, value in zip(_METRICS, means)}
+
+
 class Evaluation:
     def __init__(self, entities, relations, batch_size, true_triples=[], device="cpu", num_workers=1):
         self.entities = entities
@@ -182,3 +196,152 @@ class Evaluation:
         if training:
             model = model.train()
         return metrics
+
+    # ------------------------------------------------------------------ grouped report (reference evaluation.py:282-464)
+    def _grouped_on_device(self, model):
+        return isinstance(model, BaseModel) and self._device_ok(model) and not getattr(self, "force_reference_path", False)
+
+    def _fanout(self, model):
+        """``int64 [R, 3]`` per relation id: its true triples (with multiplicity), its distinct (tail, relation) pairs, its
+        distinct (head, relation) pairs -- the three counts the reference's two pandas group-bys reduce to.  On the device from
+        ``mkb_relation_fanout`` over the triples and the sorted keys of ``utils.true_keys``; otherwise numpy on the same
+        definition.  Cached like the keys: per triple collection (the same object with the same length), device and table size."""
+        n_ent, n_rel = len(self.entities), len(self.relations)
+        dev = model.entity_embedding.device if self._grouped_on_device(model) else None
+        n = len(self.true_triples)
+        for j, (obj, length, d, ne, nr, counts) in enumerate(_FANOUT_CACHE):
+            if obj is self.true_triples and length == n and d == dev and ne == n_ent and nr == n_rel:
+                _FANOUT_CACHE.insert(0, _FANOUT_CACHE.pop(j))
+                return counts
+        a = np.asarray(self.true_triples, dtype=np.int64).reshape(-1, 3)
+        if dev is not None:
+            keys = true_keys(self.true_triples, dev, n_ent, n_rel)
+            head, tail = keys["head-batch"], keys["tail-batch"]
+            triples = torch.as_tensor(a, device=dev)
+            out = torch.empty((n_rel, 3), dtype=torch.int64, device=dev)
+            with _hip.on_device(dev):
+                _hip.check(_hip.lib().mkb_relation_fanout(_hip.ptr(triples), len(a), _hip.ptr(head), head.numel(), _hip.ptr(tail),
+                                                          tail.numel(), n_ent, n_rel, _hip.ptr(out), _hip.stream_ptr()),
+                           "mkb_relation_fanout")
+            counts = out.cpu().numpy()
+        else:
+            a = a[(a[:, 1] >= 0) & (a[:, 1] < n_rel)]
+            h, r, t = a[:, 0], a[:, 1], a[:, 2]
+            counts = np.stack([np.bincount(r, minlength=n_rel), np.bincount(np.unique(t * n_rel + r) % n_rel, minlength=n_rel),
+                               np.bincount(np.unique(h * n_rel + r) % n_rel, minlength=n_rel)], axis=1).astype(np.int64)
+        _FANOUT_CACHE.insert(0, (self.true_triples, n, dev, n_ent, n_rel, counts))
+        del _FANOUT_CACHE[4:]
+        return counts
+
+    def types_relations(self, model, dataset, threshold=1.5):
+        """``{relation name: "1_1" | "1_M" | "M_1" | "M_M"}`` over ``true_triples`` (Bordes et al. 2013; reference
+        evaluation.py:342-383).  The first character is "1" when a (relation, tail) pair has at most ``threshold`` heads on
+        average -- the relation's triples, each occurrence counted, over its distinct (tail, relation) pairs -- and "M"
+        otherwise; the second character says the same of the tails per (head, relation) pair.
+
+        The result is keyed by relation id: a relation that never occurs in ``true_triples`` is left out.  The reference keys
+        its frame by the row index after ``reset_index()``, which is the relation id only when every relation id occurs: then
+        the two agree; otherwise the reference shifts the categories onto the wrong relations."""
+        counts = self._fanout(model)
+        name_of = {value: key for key, value in self.relations.items()}
+        out = {}
+        for r in np.flatnonzero(counts[:, 0] > 0).tolist():
+            n, per_tail, per_head = (float(c) for c in counts[r])
+            out[name_of[r]] = ("1" if n / per_tail <= threshold else "M") + "_" + ("1" if n / per_head <= threshold else "M")
+        return out
+
+    def _group_sums(self, model, dataset, group_of_relation, n_groups):
+        """Per mode ``(int64 [G, 5], float64 [G])``: the items of each group, their rank sum, the ranks <= 1, <= 3, <= 10, and
+        the sum of 1 / rank.  ``ranks`` per mode as ``eval`` computes them (with its generator draw per side), then one
+        ``mkb_rank_metrics`` launch on the whole rank tensor and one read-back of ``6 G`` numbers."""
+        dev = model.entity_embedding.device
+        table = torch.as_tensor(np.asarray(group_of_relation, dtype=np.int32), device=dev)
+        triples = torch.as_tensor(np.asarray(dataset, dtype=np.int64).reshape(-1, 3), device=dev)
+        out = {}
+        with torch.no_grad():
+            for mode in _MODES:  # same order as get_entity_stream
+                torch.empty((), dtype=torch.int64).random_()  # see eval: the reference's DataLoader iterator draws its base seed
+                ranks = self.ranks(model, dataset, mode)
+                buf = torch.empty(6 * n_groups, dtype=torch.int64, device=dev)  # counts [G, 5] int64, then sum of 1 / rank [G] double
+                with _hip.on_device(dev):
+                    _hip.check(_hip.lib().mkb_rank_metrics(_hip.ptr(ranks), _hip.ptr(triples), len(triples), _hip.ptr(table),
+                                                           table.numel(), n_groups, _hip.ptr(buf), _hip.ptr(buf[5 * n_groups:]),
+                                                           _hip.stream_ptr()), "mkb_rank_metrics")
+                host = buf.cpu().numpy()
+                out[mode] = (host[: 5 * n_groups].reshape(n_groups, 5), host[5 * n_groups:].view(np.float64))
+        return out
+
+    @classmethod
+    def compute_detailled_score(cls, model, test_set, metrics, types_relations, device):
+        """The reference's method (evaluation.py:281-340): ``compute_score`` with the five means kept per
+        ``metrics[mode][types_relations[relation id]]``.  An item whose relation has no category (it never occurs in
+        ``true_triples``; the reference raises ``KeyError``) is left out."""
+        training = model.training
+        if training:
+            model = model.eval()
+        bar = Bar(dataset=test_set, update_every=1)
+        bar.set_description("Evaluation")
+        for batch in bar:
+            sample = batch["sample"].to(device)
+            negative_sample = batch["negative_sample"].to(device)
+            filter_bias = batch["filter_bias"].to(device)
+            mode = batch["mode"]
+            score = model(sample=sample, negative_sample=negative_sample, mode=mode) + filter_bias
+            argsort = torch.argsort(score, dim=1, descending=True)
+            positive_arg = sample[:, 0] if mode == "head-batch" else sample[:, 2]
+            hit = argsort == positive_arg.unsqueeze(1)
+            assert bool((hit.sum(dim=1) == 1).all())
+            found = torch.stack([hit.float().argmax(dim=1) + 1, sample[:, 1]], dim=1).tolist()  # one D2H copy per batch
+            for ranking, relation in found:
+                if relation in types_relations:
+                    _update(metrics[mode][types_relations[relation]], [ranking])
+        if training:
+            model = model.train()
+        return metrics
+
+    def detail_metrics(self, model, dataset, threshold=1.5):
+        """``detail_eval`` as a plain nested dict: ``{"head-batch" | "tail-batch": {"1_1" | "1_M" | "M_1" | "M_M": {"MRR", "MR",
+        "HITS@1", "HITS@3", "HITS@10"}}}`` of the items of ``dataset`` whose relation is of that category (``types_relations``),
+        rounded to 4 places, 0.0 for a category without items, plus ``"frequency": {category: share of the relations}``.
+
+        On a ROCm device (the conditions of ``eval``) the ranks stay on the device and ``mkb_rank_metrics`` reduces them per
+        category; otherwise (or with ``force_reference_path = True``) ``compute_detailled_score`` walks the reference's stream."""
+        type_of = {self.relations[name]: kind for name, kind in self.types_relations(model, dataset, threshold).items()}
+        if self._grouped_on_device(model):
+            table = np.full(len(self.relations), -1, dtype=np.int32)
+            for relation, kind in type_of.items():
+                table[relation] = _TYPES.index(kind)
+            sums = self._group_sums(model, dataset, table, len(_TYPES))
+            out = {mode: {kind: _from_sums(sums[mode][0][g], sums[mode][1][g]) for g, kind in enumerate(_TYPES)} for mode in _MODES}
+        else:
+            metrics = {mode: {kind: _metrics() for kind in _TYPES} for mode in _MODES}
+            with torch.no_grad():
+                for test_set in self.get_entity_stream(dataset):
+                    metrics = self.compute_detailled_score(model=model, test_set=test_set, metrics=metrics, types_relations=type_of,
+                                                           device=self.device)
+            out = {mode: {kind: _report(metrics[mode][kind]) for kind in _TYPES} for mode in _MODES}
+        kinds = list(type_of.values())
+        out["frequency"] = {kind: kinds.count(kind) / len(kinds) if kinds else 0.0 for kind in _TYPES}
+        return out
+
+    def detail_eval(self, model, dataset, threshold=1.5):
+        """The reference's table (evaluation.py:385-464): a ``pandas.DataFrame`` with the categories ``1_1 .. M_M`` as index
+        (named ``relation``), the column blocks ``head`` / ``tail`` x MRR, MR, HITS@1, HITS@3, HITS@10 and
+        ``("metadata", "frequency")``; the numbers of ``detail_metrics``.  (The reference names the index too, but its last
+        ``concat`` with the unnamed frequency frame drops the name again; here it stays.)"""
+        import pandas as pd  # here only: the package imports without pandas
+
+        found = self.detail_metrics(model, dataset, threshold)
+        columns = [(side, metric) for side in ("head", "tail") for metric in _METRICS] + [("metadata", "frequency")]
+        rows = [[found[mode][kind][metric] for mode in _MODES for metric in _METRICS] + [found["frequency"][kind]] for kind in _TYPES]
+        return pd.DataFrame(rows, index=pd.Index(_TYPES, name="relation"), columns=pd.MultiIndex.from_tuples(columns))
+
+    def eval_per_relation(self, model, dataset):
+        """``{relation name: {"head-batch": {MRR, MR, HITS@1, HITS@3, HITS@10, "count"}, "tail-batch": {...}}}``: the filtered
+        metrics of ``eval`` for the items of each relation (``mkb_rank_metrics`` with one group per relation); on a ROCm device
+        only."""
+        _hip.require_device(model.entity_embedding)
+        n_rel = len(self.relations)
+        sums = self._group_sums(model, dataset, np.arange(n_rel, dtype=np.int32), n_rel)
+        return {name: {mode: {**_from_sums(sums[mode][0][r], sums[mode][1][r]), "count": int(sums[mode][0][r][0])} for mode in _MODES}
+                for name, r in self.relations.items()}

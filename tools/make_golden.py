@@ -256,8 +256,9 @@ def gen_pipeline():
                    "torch": torch.__version__, "numpy": np.__version__}, f, indent=1)
 
 
-def gen_eval():
-    """evaluation.py:43-119 known-answer (5 epochs, no zero_grad, Adam lr .5) + score rows."""
+def _toy_rotate():
+    """The trained 4-entity RotatE of the class docstring (evaluation.py:43-119: 5 epochs, no zero_grad, Adam lr .5)
+    -> (model, initial tables, train, valid, test, entities, relations)."""
     torch.manual_seed(42)
     train = [(0, 0, 1), (0, 1, 1), (2, 0, 3), (2, 1, 3)]
     valid = [(0, 0, 1), (2, 1, 3)]
@@ -277,6 +278,12 @@ def gen_eval():
             s, w, mode = data["sample"], data["weight"], data["mode"]
             lossf(model(s), model(s, ns.generate(sample=s, mode=mode), mode), w).backward()
             opt.step()
+    return model.eval(), out, train, valid, test, ents, rels
+
+
+def gen_eval():
+    """evaluation.py:43-119 known-answer (5 epochs, no zero_grad, Adam lr .5) + score rows."""
+    model, out, train, valid, test, ents, rels = _toy_rotate()
     model = model.eval()
     out["ent"], out["rel"] = npy(model.entity_embedding), npy(model.relation_embedding)
     ev = evaluation.Evaluation(true_triples=train + valid + test, entities=ents, relations=rels, batch_size=2)
@@ -695,6 +702,92 @@ def _gen_topk_sampling_transe():
     out["kd/m1_rel_after"], out["kd/m2_rel_after"] = npy(m1.relation_embedding), npy(m2.relation_embedding)
     np.savez_compressed(OUT / "topk_sampling_transe.npz", **out)
     (OUT / "topk_sampling_transe.json").write_text(json.dumps(js, indent=1))
+
+
+def _frame_record(frame):
+    """A detail_eval frame as data: nested lists for the frame itself, and the same numbers as the nested dict
+    ``{mode: {category: {metric: value}}, "frequency": {category: share}}``."""
+    nested = {mode: {kind: {metric: float(frame.loc[kind, (side, metric)]) for metric in frame[side].columns}
+                     for kind in frame.index}
+              for mode, side in (("head-batch", "head"), ("tail-batch", "tail"))}
+    nested["frequency"] = {kind: float(frame.loc[kind, ("metadata", "frequency")]) for kind in frame.index}
+    return {"index": list(frame.index), "index_name": frame.index.name, "columns": [list(c) for c in frame.columns],
+            "values": frame.values.tolist()}, nested
+
+
+def _reference_ranks(ev, model, test):
+    """Per-item ranks of both sides by the arithmetic of compute_detailled_score (evaluation.py:292-322), in stream order.
+    The reference reads the rank off an unstable argsort: a candidate whose biased score equals the target's would leave the
+    rank undefined, so any such row (or a near tie) fails the generation."""
+    ranks = {}
+    with torch.no_grad():
+        for loader in ev.get_entity_stream(test):
+            for data in loader:
+                mode = data["mode"]
+                score = model(sample=data["sample"], negative_sample=data["negative_sample"], mode=mode)
+                score += data["filter_bias"]
+                target = data["sample"][:, 0] if mode == "head-batch" else data["sample"][:, 2]
+                at_target = score.gather(1, target.unsqueeze(1))
+                gap = (score - at_target).abs().scatter_(1, target.unsqueeze(1), float("inf")).min().item()
+                # no tie -- and no near tie either: another implementation's fp32 score differs by a few ulp (sum order; one ulp
+                # is 4.8e-7 at these scores), which must not move a rank
+                assert gap >= 1e-5, f"a candidate within {gap} of the target's score ({mode}): pick another seed"
+                argsort = torch.argsort(score, dim=1, descending=True)
+                ranks.setdefault(mode, []).extend(1 + (argsort[i, :] == target[i]).nonzero().item() for i in range(len(target)))
+    return {mode: np.asarray(r, dtype=np.int64) for mode, r in ranks.items()}
+
+
+def gen_detail_eval():
+    """Evaluation.types_relations / detail_eval (evaluation.py:342-464) from the live reference: (a) the class docstring's
+    trained 4-entity RotatE with its duplicate-bearing ``train + valid + test`` filter set; (b) CountriesS1 and Umls, each with a
+    TransE and a RotatE of small hidden size after a few reference training steps: weights, per-item ranks of both sides, the
+    category map at thresholds 1.5 and 1.0 and the rounded table at both."""
+    out, js = {}, {}
+    model, _, train, valid, test, ents, rels = _toy_rotate()
+    recorded = np.load(OUT / "evaluation.npz")
+    assert np.array_equal(npy(model.entity_embedding), recorded["ent"]) and np.array_equal(npy(model.relation_embedding), recorded["rel"])
+    ev = evaluation.Evaluation(true_triples=train + valid + test, entities=ents, relations=rels, batch_size=2)
+    frame, nested = _frame_record(ev.detail_eval(model=model, dataset=test, threshold=1.5))
+    js["toy"] = {"types": ev.types_relations(model=model, dataset=test, threshold=1.5), "frame": frame, "metrics": nested}
+    for mode, r in _reference_ranks(ev, model, test).items():
+        out[f"toy/{mode}/ranks"] = r
+    hidden, gamma, steps = 8, 4.0, 40
+    for cls in ["CountriesS1", "Umls"]:
+        for mi, name in enumerate(["TransE", "RotatE"]):
+            for seed in range(100 + mi, 200, 10):  # the first seed whose model ranks every test row without a (near) tie
+                ds = getattr(datasets, cls)(batch_size=64, shuffle=True, seed=42)
+                torch.manual_seed(seed)  # after the dataset, which seeds torch itself (dataset.py:185-186)
+                assert {r for _, r, _ in ds.true_triples} == set(ds.relations.values()), "a relation id never occurs: id- and row-keyed maps differ"
+                m = getattr(models, name)(hidden_dim=hidden, entities=ds.entities, relations=ds.relations, gamma=gamma)
+                opt = torch.optim.Adam(filter(lambda p: p.requires_grad, m.parameters()), lr=0.05)
+                lossf = losses.Adversarial(alpha=0.5)
+                for _, data in zip(range(steps), ds):
+                    s, w, mode = data["sample"], data["weight"], data["mode"]
+                    # unfiltered uniform negatives: the reference's filtered sampler does not terminate on Umls' dense rows
+                    lossf(m(s), m(s, torch.randint(len(ds.entities), (len(s), 8)), mode), w).backward()
+                    opt.step()
+                    opt.zero_grad()
+                m = m.eval()
+                ev = evaluation.Evaluation(true_triples=ds.true_triples, entities=ds.entities, relations=ds.relations, batch_size=32)
+                try:
+                    ranks = _reference_ranks(ev, m, ds.test)
+                    break
+                except AssertionError as e:
+                    print(cls, name, "seed", seed, e, file=sys.stderr)
+            else:
+                raise AssertionError("no seed without a near tie")
+            tag = f"{cls}/{name}"
+            out[f"{tag}/ent"], out[f"{tag}/rel"] = npy(m.entity_embedding), npy(m.relation_embedding)
+            for mode, r in ranks.items():
+                out[f"{tag}/{mode}/ranks"] = r
+            rec = {"hidden": hidden, "gamma": gamma, "seed": seed, "types": {}, "metrics": {}}
+            for threshold in (1.5, 1.0):
+                rec["types"][str(threshold)] = ev.types_relations(model=m, dataset=ds.test, threshold=threshold)
+                rec["metrics"][str(threshold)] = _frame_record(ev.detail_eval(model=m, dataset=ds.test, threshold=threshold))[1]
+            js[tag] = rec
+            print(tag, rec["metrics"]["1.5"]["frequency"], file=sys.stderr)
+    np.savez_compressed(OUT / "detail_eval.npz", **out)
+    (OUT / "detail_eval.json").write_text(json.dumps(js, indent=1))
 
 
 if __name__ == "__main__":
