@@ -439,6 +439,33 @@ int mkb_relation_fanout(const int64_t *triples, int64_t n, const int64_t *head_k
 int mkb_rank_metrics(const int64_t *ranks, const int64_t *sample, int64_t n, const int32_t *group_of_relation, int64_t n_relation,
                      int n_groups, int64_t *counts, double *rr_sum, void *stream);
 
+/* ---- triple classification (evaluation/classif.py:89-155: find_threshold, _accuracy) ----------------------
+ * mkb_threshold_search: per group, the threshold find_threshold returns: thresholds[argmax(tpr - fpr)] of
+ * sklearn.metrics.roc_curve(y, score) with drop_intermediate=True.  score [n] fp32, label [n] int64 (> 0: positive),
+ * group [n] int32 or null (null: every item is of group 0; an id < 0 or >= n_groups: the item is of no group).  Among the
+ * items of a group with a finite score, write for a score v: tp_ge / fp_ge the positives / negatives with a score >= v,
+ * tp_gt / fp_gt those with a score > v, tp_nx / fp_nx those with a score >= the largest score below v.  The distinct score v
+ * is a point of the curve when it is the highest or the lowest, or fp_nx - 2 fp_ge + fp_gt != 0, or the same of tp; its value is
+ * J = (double)tp_ge / P - (double)fp_ge / N (P, N: the group's positives, negatives), and one more point, threshold +inf with
+ * J = 0.0, comes first.  threshold [n_groups] fp32 out: the first point in descending threshold order with the largest J (-0.0
+ * and +0.0 are one score: either may be written); +inf for a group with P == 0 or N == 0.  stats [n_groups, 6] int64 out: P, N,
+ * tp_ge and fp_ge at the threshold written (0, 0 at +inf), the items of the group whose score is not finite (they take no part
+ * and are not in P or N), all items of the group.  An all-pairs count, quadratic in n: n above MKB_THRESHOLD_SEARCH_MAX_N (from
+ * where a host sort was measured faster) is refused with MKB_ERR_INVALID.  ws: mkb_threshold_search_workspace_bytes, 4-byte aligned (may be null when n == 0).
+ * The selection, like mkb_threshold_accuracy, runs one workgroup per group over all n items (as mkb_rank_metrics does): the cost
+ * has a term n_groups * n, meant for a few hundred groups; n_groups * n above 2^32 is refused by both entries. */
+#ifndef MKB_THRESHOLD_SEARCH_MAX_N /* a measurement build may raise it: tools/eval_speed.py classif cap */
+#define MKB_THRESHOLD_SEARCH_MAX_N 131072
+#endif
+int64_t mkb_threshold_search_workspace_bytes(int64_t n, int n_groups);
+int mkb_threshold_search(const float *score, const int64_t *label, const int32_t *group, int64_t n, int n_groups, float *threshold,
+                         int64_t *stats, void *ws, int64_t ws_bytes, void *stream);
+/* mkb_threshold_accuracy: _accuracy as counts.  counts [n_groups, 2] int64 out per group: the items with (score >= threshold[g]
+ * and label > 0) or (score < threshold[g] and label <= 0), and all items of the group (a NaN score is neither >= nor <: wrong).
+ * group as above.  Every output is written, for an empty group and for n == 0 too. */
+int mkb_threshold_accuracy(const float *score, const int64_t *label, const int32_t *group, int64_t n, const float *threshold,
+                           int n_groups, int64_t *counts, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

@@ -20,6 +20,7 @@ MODEL_IDS = {"TransE": 0, "RotatE": 1, "ComplEx": 2, "DistMult": 3, "pRotatE": 4
 MODE_DEFAULT, MODE_HEAD, MODE_TAIL = 0, 1, 2
 ERR_INVALID, ERR_KEY, ERR_EMPTY = -1, -3, -4
 TOPK_MAX_K, TOPK_KEEP_TARGET = 1024, 1  # MKB_TOPK_MAX_K, MKB_TOPK_KEEP_TARGET
+THRESHOLD_SEARCH_MAX_N = 131072  # MKB_THRESHOLD_SEARCH_MAX_N
 
 
 def mode_id(mode):
@@ -141,6 +142,9 @@ _SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mkb_relation_fanout": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "mkb_rank_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "mkb_threshold_search_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "mkb_threshold_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_threshold_accuracy": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -160,7 +164,11 @@ def lib():
             raise HipLibraryError(f"ABI version mismatch: library {handle.mkb_abi_version()}, binding {ABI_VERSION} "
                                   "(rebuild with `python -m mkb_amd.csrc.build`)")
         for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError here = header / library mismatch
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:  # symbols are added without a version bump: a library built before this binding lacks them
+                raise HipLibraryError(f"{_LIB_PATH} does not export {name}: it was built from older sources "
+                                      "(rebuild with `python -m mkb_amd.csrc.build`)") from None
             fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib

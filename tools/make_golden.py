@@ -58,7 +58,7 @@ _install_river_stub()
 sys.dont_write_bytecode = True
 sys.path.insert(0, "/root/reference")
 import mkb  # noqa: E402
-from mkb import compose, datasets, evaluation, losses, models, sampling  # noqa: E402
+from mkb import compose, datasets, evaluation, losses, models, sampling, utils  # noqa: E402
 
 MODELS = ["TransE", "RotatE", "ComplEx", "DistMult", "pRotatE"]
 MODES = [None, "head-batch", "tail-batch"]
@@ -788,6 +788,70 @@ def gen_detail_eval():
             print(tag, rec["metrics"]["1.5"]["frequency"], file=sys.stderr)
     np.savez_compressed(OUT / "detail_eval.npz", **out)
     (OUT / "detail_eval.json").write_text(json.dumps(js, indent=1))
+
+
+def gen_classif():
+    """Triple classification (evaluation/classif.py) from the live reference on Umls' classification_valid / classification_test:
+    the doctest's TransE (hidden 3, gamma 6, seed 42), the four other models at hidden 8 (seed 42, gamma 6) and one TransE of
+    hidden 8 after a few epochs of reference training steps, so that one case sits far from 50 %.  Per model: the tables, the
+    reference's scores of both sets, find_threshold on valid, accuracy on valid and test at it, and find_threshold on the valid
+    triples of each relation (+inf where sklearn has one class only and returns its extra point)."""
+    import warnings
+
+    import sklearn
+
+    warnings.simplefilter("ignore")  # roc_curve on a one-class subset: UndefinedMetricWarning, then +inf
+    out = {}
+    js = {"versions": {"sklearn": sklearn.__version__, "numpy": np.__version__, "torch": torch.__version__}, "models": {}}
+
+    def dataset(**kw):
+        torch.manual_seed(42)  # the doctest's order: seed, dataset, model (classif.py:27-37)
+        return datasets.Umls(batch_size=2, **kw)
+
+    ds = dataset()
+    sets = {"valid": ds.classification_valid, "test": ds.classification_test}
+    for split, s in sets.items():
+        out[f"{split}/X"], out[f"{split}/y"] = np.asarray(s["X"], dtype=np.int16), np.asarray(s["y"], dtype=np.int8)
+    js["n_entity"], js["n_relation"] = len(ds.entities), len(ds.relations)
+
+    def record(tag, m, name, hidden, gamma):
+        m = m.eval()
+        out[f"{tag}/ent"], out[f"{tag}/rel"] = npy(m.entity_embedding), npy(m.relation_embedding)
+        if name == "pRotatE":
+            out[f"{tag}/modulus"] = npy(m.modulus)
+        for split, s in sets.items():
+            out[f"{tag}/{split}/score"] = npy(utils.make_prediction(model=m, dataset=s["X"], batch_size=128, num_workers=0, device="cpu"))
+        call = dict(model=m, batch_size=128, num_workers=0, device="cpu")
+        thr = evaluation.find_threshold(X=sets["valid"]["X"], y=sets["valid"]["y"], **call)
+        assert thr.dtype == np.float32
+        X, y = np.asarray(sets["valid"]["X"]), np.asarray(sets["valid"]["y"])
+        per = np.full(len(ds.relations), np.nan, dtype=np.float32)  # NaN: the relation has no valid triple
+        for r in sorted(set(X[:, 1].tolist())):
+            rows = X[:, 1] == r
+            per[r] = evaluation.find_threshold(X=X[rows].tolist(), y=y[rows].tolist(), **call)
+        out[f"{tag}/threshold"], out[f"{tag}/threshold_per_relation"] = np.asarray(thr), per
+        js["models"][tag] = {"model": name, "hidden": hidden, "gamma": gamma, "threshold": repr(float(thr)), "threshold_str": str(thr),
+                             "accuracy": {split: evaluation.accuracy(X=s["X"], y=s["y"], threshold=thr, **call) for split, s in sets.items()}}
+        print(tag, js["models"][tag], file=sys.stderr)
+
+    for tag, name, hidden in [("TransE3", "TransE", 3), ("RotatE", "RotatE", 8), ("ComplEx", "ComplEx", 8), ("DistMult", "DistMult", 8),
+                              ("pRotatE", "pRotatE", 8)]:
+        ds = dataset()
+        record(tag, getattr(models, name)(entities=ds.entities, relations=ds.relations, hidden_dim=hidden, gamma=6), name, hidden, 6)
+    ds = datasets.Umls(batch_size=64, shuffle=True, seed=42)
+    torch.manual_seed(7)
+    m = models.TransE(entities=ds.entities, relations=ds.relations, hidden_dim=8, gamma=6)
+    opt = torch.optim.Adam(filter(lambda p: p.requires_grad, m.parameters()), lr=0.05)
+    lossf = losses.Adversarial(alpha=0.5)
+    for _, data in zip(range(400), ds):
+        s, w, mode = data["sample"], data["weight"], data["mode"]
+        # unfiltered uniform negatives: the reference's filtered sampler does not terminate on Umls' dense rows
+        lossf(m(s), m(s, torch.randint(len(ds.entities), (len(s), 8)), mode), w).backward()
+        opt.step()
+        opt.zero_grad()
+    record("TransE_trained", m, "TransE", 8, 6)
+    np.savez_compressed(OUT / "classif.npz", **out)
+    (OUT / "classif.json").write_text(json.dumps(js, indent=1))
 
 
 if __name__ == "__main__":
