@@ -466,6 +466,39 @@ int mkb_threshold_search(const float *score, const int64_t *label, const int32_t
 int mkb_threshold_accuracy(const float *score, const int64_t *label, const int32_t *group, int64_t n, const float *threshold,
                            int n_groups, int64_t *counts, void *stream);
 
+/* ---- relation prediction (h, ?, t): scores, filtered rank, top k -------------------------------------------------
+ * The relation-batch side of evaluation.Evaluation.compute_score (evaluation/evaluation.py:217-279) with the candidates and
+ * bias of datasets.base.TestDatasetRelation (datasets/base.py:254-305), and the batched "which relation links these two
+ * entities" call (mkb_amd/csrc/score_relation.hip).  New symbols under ABI 8: the version is not bumped.
+ *   Every score is bit-identical to what mkb_score_fwd writes for the same (h, r, t) in MKB_MODE_DEFAULT on the same tables.
+ *   true_keys: the ascending tail-batch keys of mkb_rank, (h*n_relation + r)*n_entity + t; n_true == 0 filters nothing.
+ *   Order of the rank and of the top k: NaN first, then higher score, then lower relation id.
+ *   mkb_rel_rank: with s the score block of a query and r its relation, v[r'] = s[r] + (-1.0f) where r' != r and (h, r', t) is a
+ *   key, v[r'] = s[r'] elsewhere; rank = 1 + the number of r' != r with v[r'] ahead of v[r].  r must lie in [0, n_relation) (not
+ *   checked: device memory).
+ *   mkb_rel_topk: the k best relations of each query, every r' whose (h, r', t) is a key left out; MKB_TOPK_KEEP_TARGET keeps
+ *   sample's own r in (the candidates of the rank) -- without it the relation column is not read.  1 <= k <= MKB_TOPK_MAX_K;
+ *   past the candidates left: id -1, score -inf.  scores are the block's bits.
+ *   B == 0 is a valid call that launches nothing (ws may then be null); 0 <= B <= 2^31 - 1.  A null pointer, a bad B / n_rel / ld /
+ *   k / flags, n_true > 0 without keys, a short or misaligned (256 bytes) workspace, an unknown model -> MKB_ERR_INVALID before any
+ *   launch; entity rows too long for the kernel's LDS staging (6 * entity_dim floats > 64 KB) -> MKB_ERR_UNSUPPORTED.  The
+ *   workspace functions return 0 for B <= 0 or a bad k.  Nothing is allocated in a call; no float atomics: two runs give the
+ *   same bits. */
+/* scores[i * ld + j] = score of (h_i, rel_ids ? rel_ids[j] : j, t_i); sample [B, 3], its relation column is not read.
+ * rel_ids [n_rel] int64 device, duplicates and any order allowed; null: n_rel must equal tb->n_relation. ld >= n_rel. */
+int mkb_rel_scores(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *rel_ids, int64_t n_rel,
+                   float *scores, int64_t ld, void *stream);
+
+int64_t mkb_rel_rank_workspace_bytes(const mkb_tables_t *tb, int64_t B);
+/* filtered rank (1-based) of sample's relation among all n_relation; scores: null, or [B, n_relation] out = the block
+ * the ranks were counted on (before the filter), bit-identical to mkb_rel_scores */
+int mkb_rel_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *true_keys, int64_t n_true,
+                 int64_t *rank, float *scores, void *ws, int64_t ws_bytes, void *stream);
+
+int64_t mkb_rel_topk_workspace_bytes(const mkb_tables_t *tb, int64_t B, int k);
+int mkb_rel_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *true_keys, int64_t n_true,
+                 int k, int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

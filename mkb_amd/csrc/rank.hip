@@ -15,6 +15,7 @@
 //           (a contiguous range of the sorted key array) and take back the ones that were counted.
 #include "common.h"
 #include "query_side.h"
+#include "rank_order.h"      // ranks_before: the order every rank and top k here is counted in
 #include "score_pool_tile.h"  // the pooled forward's outer-product register tile, for the all-entity block of RotatE / TransE
 #include "gemm_mfma.h"        // ... and the matrix-core product for ComplEx / DistMult, whose score is a dot product
 
@@ -113,17 +114,6 @@ __global__ __launch_bounds__(NW * 64) void all_fwd_kernel(AllArgs A) {
             }
         }
     }
-}
-
-// Position of the target in the reference's torch.argsort(score, descending=True) (evaluation.py:245-262).  Ties and NaN
-// need care: "1 + #{S[e] > S[target]}" alone ranks the target FIRST whenever nothing compares greater, i.e. for a collapsed
-// model (all scores equal) or a diverged one (NaN anywhere in the comparison) -- MRR = HITS@k = 1.0 for a broken run, which
-// the early-stopping logic of Pipeline.learn would then keep.  The order used here is the one of a stable descending sort
-// with torch's NaN convention: NaN sorts before every number, equal keys keep candidate order (lower entity id first).
-__device__ __forceinline__ bool ranks_before(float a, int64_t ia, float b, int64_t ib) {
-    const bool an = a != a, bn = b != b;
-    if (an || bn) return an && (!bn || ia < ib);
-    return a > b || (a == b && ia < ib);
 }
 
 // one wave per query

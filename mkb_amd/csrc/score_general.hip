@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "query_side.h"
+#include "score_row.h"  // TablesDev, and the pair sum of one candidate row
 
 #include <stdlib.h>
 
@@ -30,24 +31,6 @@ namespace mkb {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-
-struct TablesDev {
-    const float *ent, *rel, *modulus;
-    int64_t De, Dr;
-    int d;
-    float gamma, kd;
-    int vec4;  // rows (and their complex halves) are 16-byte aligned and a multiple of 4 units long
-};
-
-static TablesDev to_dev(const mkb_tables_t *tb) {
-    TablesDev t;
-    t.ent = tb->ent; t.rel = tb->rel; t.modulus = tb->modulus;
-    t.De = tb->entity_dim; t.Dr = tb->relation_dim; t.d = tb->hidden_dim;
-    t.gamma = tb->gamma; t.kd = tb->phase_div;
-    const bool cp = tb->model == MKB_ROTATE;
-    t.vec4 = ((((uintptr_t)tb->ent) & 15) == 0 && tb->entity_dim % 4 == 0 && (!cp || tb->hidden_dim % 4 == 0)) ? 1 : 0;
-    return t;
-}
 
 template <int MODEL, bool HEAD>
 __global__ __launch_bounds__(kBlock) void score_fwd_kernel(TablesDev T, const int64_t *__restrict__ sample,
@@ -69,31 +52,7 @@ __global__ __launch_bounds__(kBlock) void score_fwd_kernel(TablesDev T, const in
     for (int j = wave; j < K; j += kWaves) {
         const int64_t c = cand ? cand[(int64_t)i * K + j] : R.t;
         const float *x = T.ent + c * T.De;
-        float acc = 0.f;
-        if constexpr (ModelTraits<MODEL>::cplx_pair) {
-            if (vec4) {  // 16-byte loads of the candidate row halves and of the staged query
-                for (int k = lane * 4; k < T.d; k += 256) {
-                    const float4 xr = *reinterpret_cast<const float4 *>(x + k), xi = *reinterpret_cast<const float4 *>(x + T.d + k);
-                    const float4 qr = *reinterpret_cast<const float4 *>(q_lds + k), qi = *reinterpret_cast<const float4 *>(q_lds + T.d + k);
-                    const f2 t0 = pair_term_cmod2(f2{qr.x, qr.y}, f2{qi.x, qi.y}, f2{xr.x, xr.y}, f2{xi.x, xi.y});
-                    const f2 t1 = pair_term_cmod2(f2{qr.z, qr.w}, f2{qi.z, qi.w}, f2{xr.z, xr.w}, f2{xi.z, xi.w});
-                    acc += (t0.x + t0.y) + (t1.x + t1.y);
-                }
-            } else {
-                for (int k = lane; k < T.d; k += 64)
-                    acc += pair_term_cmod(Cplx{q_lds[k], q_lds[T.d + k]}, Cplx{x[k], x[T.d + k]});
-            }
-        } else {
-            if (vec4) {
-                for (int k = lane * 4; k < (int)T.De; k += 256) {
-                    const float4 xv = *reinterpret_cast<const float4 *>(x + k), qv = *reinterpret_cast<const float4 *>(q_lds + k);
-                    acc += (pair_term_real<MODEL, HEAD>(qv.x, xv.x, T.kd) + pair_term_real<MODEL, HEAD>(qv.y, xv.y, T.kd))
-                           + (pair_term_real<MODEL, HEAD>(qv.z, xv.z, T.kd) + pair_term_real<MODEL, HEAD>(qv.w, xv.w, T.kd));
-                }
-            } else {
-                for (int k = lane; k < (int)T.De; k += 64) acc += pair_term_real<MODEL, HEAD>(q_lds[k], x[k], T.kd);
-            }
-        }
+        float acc = pair_row_sum<MODEL, HEAD>(T, q_lds, x, lane, vec4);
         acc = wave_sum(acc);
         if (lane == 0) score[(int64_t)i * K + j] = finish_score<MODEL>(acc, T.gamma, modulus);
     }

@@ -7,8 +7,8 @@ The reference loops over the triples on the host with three ``argsort``s per tri
 sampler shares (the mappings, sizes, checks, device tables, the random columns and the one ``get``), and each live sampler
 answers one question, ``side(part, sample, teacher)``: the k candidates of one part ("head", "relation" or "tail") of these
 triples, in teacher and in student ids.  ``TopKSampling.side`` is one ``mkb_topk_masked`` launch per entity side and batch (the
-all-entity score block, restricted to the shared entities by a bitmask), and for the relation side one general forward of the
-``[b, shared relations, 3]`` block (as ``Evaluation.relation_ranks`` scores it) and one ``mkb_topk_block``.
+all-entity score block, restricted to the shared entities by a bitmask), and for the relation side one ``mkb_rel_scores`` of the
+``[b, shared relations]`` block (the scores ``Evaluation.relation_ranks`` counts on) and one ``mkb_topk_block``.
 ``TopKSamplingTransE.side`` is the reference's sampler for a TransE teacher: the shared entities / relations nearest in L2 to
 the teacher's translated queries, with the device's exact squared-L2 k nearest rows (``mkb_topk_nearest``) in place of the
 reference's faiss ``IndexFlatL2``.  ``FastTopKSampling`` runs one loop over the distinct keys of the three parts and asks the
@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _hip
+from ..utils.predict_relations import rel_scores_launch
 from ..utils.predict_top_k import _launch, candidate_bits, topk_block, topk_nearest
 
 __all__ = ["FastTopKSampling", "TopKSampling", "TopKSamplingTransE"]
@@ -157,6 +158,11 @@ class TopKSampling(_Sampler):
     A top k larger than the number of shared entities / relations raises ``ValueError`` (the reference would return fewer
     columns and fail later)."""
 
+    # The teachers whose relation side runs on mkb_rel_scores: where it was measured faster at B = 1024 by more than the general
+    # route's spread (profiles/r14_relation_side_speed.txt).  A RotatE teacher keeps the general forward (0.404 against 0.376 ms:
+    # 1,024 workgroups that each rebuild 237 rotated queries do not fill the device; the general forward's 242 k do).
+    RELATION_KERNEL_MODELS = frozenset({"TransE", "ComplEx", "DistMult", "pRotatE"})
+
     def side(self, part, sample, teacher, chunk=1024):
         """-> (teacher ids, student ids) [b, k] of one part ("head", "relation" or "tail") for ``sample`` [b, 3] int64 on the
         teacher's device, ``chunk`` rows per launch: the teacher's k best shared entities / relations in that place.  No random
@@ -169,6 +175,24 @@ class TopKSampling(_Sampler):
             _launch(teacher, sample, f"{part}-batch", k, torch.empty(0, dtype=torch.int64, device=dev), 0, tb["ent_bits"], chunk, ids,
                     torch.empty((b, k), dtype=torch.float32, device=dev))
             return ids, tb["ent_map"][ids]
+        rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
+        if teacher.name not in self.RELATION_KERNEL_MODELS:
+            return self._relation_side_general(sample, teacher, chunk)
+        score = torch.empty((min(b, chunk), n_rel), dtype=torch.float32, device=dev)
+        for lo in range(0, b, chunk):  # mkb_rel_scores of [b, R_shared], then the block selection
+            s = sample[lo: lo + chunk].contiguous()
+            if not rel_scores_launch(teacher, s, rel_t, score[: s.shape[0]]):
+                return self._relation_side_general(sample, teacher, chunk)
+            topk_block(score[: s.shape[0]], k, ids=ids[lo: lo + chunk])
+        return rel_t[ids], tb["rel_s"][ids]
+
+    def _relation_side_general(self, sample, teacher, chunk=1024):
+        """The relation side through the general forward of the ``[b, R_shared, 3]`` block: the route of teachers
+        ``mkb_rel_scores`` does not support or was not measured faster for, and what the tests compare the kernel's route with."""
+        dev = teacher.entity_embedding.device
+        tb = self.tables(dev)
+        b, k = sample.shape[0], self._k("relation")
+        ids = torch.empty((b, k), dtype=torch.int64, device=dev)
         rel_t, n_rel = tb["rel_t"], tb["rel_t"].numel()
         for lo in range(0, b, chunk):  # the general forward of [b, R_shared, 3], then the block selection
             s = sample[lo: lo + chunk]

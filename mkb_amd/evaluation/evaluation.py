@@ -4,9 +4,10 @@ mkb/evaluation/evaluation.py:137-279) with the same constructor and return dicti
 ``eval`` on a ROCm device runs ``mkb_rank``: every test triple is scored against ALL entity rows by a tiled HIP
 kernel (no ``[B, N, D]`` gather, no per-item python loop over ``n_entity`` candidates as in
 ``datasets.base.TestDataset``, base.py:196-241) and the filtered rank is counted on the device; exact score ties
-count in the target's favour.  ``force_reference_path = True`` (and ``eval_relations`` always) takes the
-reference's route instead: ``TestDataset`` candidate lists + filter bias, ``model(sample, negative_sample, mode)``
-through the general HIP forward, rank read off a descending argsort (evaluation.py:245-262).
+count in the target's favour.  ``eval_relations`` runs ``mkb_rel_rank`` the same way (``relation_ranks``).
+``force_reference_path = True`` takes the reference's route instead: ``TestDataset`` candidate lists + filter bias,
+``model(sample, negative_sample, mode)`` through the general HIP forward, rank read off a descending argsort
+(evaluation.py:245-262).
 """
 import collections
 
@@ -17,7 +18,7 @@ from torch.utils import data
 from .. import _hip
 from ..datasets import base
 from ..models.base import BaseModel
-from ..utils import Bar, Mean, predict_top_k, true_keys
+from ..utils import Bar, Mean, predict_top_k, predict_top_k_relations, true_keys
 
 __all__ = ["Evaluation"]
 
@@ -43,6 +44,9 @@ def _report(metrics, suffix=""):
 _MODES = ("head-batch", "tail-batch")
 _TYPES = ("1_1", "1_M", "M_1", "M_M")
 _METRICS = ("MRR", "MR", "HITS@1", "HITS@3", "HITS@10")
+# the models whose relation_ranks runs on mkb_rel_rank by default: all five were measured faster on FB15k-237's test split by more
+# than the torch route's spread (profiles/r14_relation_side_speed.txt)
+RELATION_KERNEL_MODELS = frozenset({"TransE", "RotatE", "ComplEx", "DistMult", "pRotatE"})
 _FANOUT_CACHE = []  # [(true_triples, len, device or None, n_entity, n_relation, counts)], most recent first
 
 
@@ -130,16 +134,61 @@ class Evaluation:
                 metrics = self.compute_score(model=model, test_set=test_set, metrics=metrics, device=self.device)
         return _report(metrics)
 
-    def relation_ranks(self, model, dataset, chunk=4096):
+    def top_k_relations(self, model, dataset, k, keep_target=True, chunk=4096):
+        """The k best relations of every ``(h, ?, t)`` of ``dataset`` on the device, filtered by ``true_triples`` (with
+        ``keep_target=True`` the candidate set ``relation_ranks`` counts on: wherever the target's rank is at most k, it sits at
+        that position) -> ``(ids [n, k], scores [n, k])``; see ``utils.predict_top_k_relations``."""
+        return predict_top_k_relations(model, dataset, k, true_triples=self.true_triples, keep_target=keep_target, chunk=chunk)
+
+    def relation_ranks(self, model, dataset, chunk=4096, with_scores=False):
         """Filtered rank (1-based) of the true relation of every triple among all relations, on the device: what
         ``compute_score`` does with the ``relation-batch`` stream (datasets/base.py:254-305: the other true relations of
-        (h, ., t) are replaced by the target relation and biased by -1), without the per-item host loop."""
+        (h, ., t) are replaced by the target relation and biased by -1), without the per-item host loop.  One ``mkb_rel_rank``
+        call per ``chunk`` triples (csrc/score_relation.hip: one workgroup per (h, ?, t) scores all relations, the filter is a
+        bitmask, one wave counts the rank); the scores, and so the ranks, are those of ``_relation_ranks_torch``, which stays
+        the route of shapes the kernel does not support.  ``with_scores=True`` -> ``(ranks, scores [n, n_relation])``: the block
+        the ranks were counted on, before the filter.
+
+        ``RELATION_KERNEL_MODELS`` names the models whose default route the kernel is (where it was measured faster, DESIGN
+        section 5); the others keep ``_relation_ranks_torch``.  Both give the same ranks."""
+        found = self._relation_ranks_kernel(model, dataset, chunk, with_scores) if model.name in RELATION_KERNEL_MODELS else None
+        return self._relation_ranks_torch(model, dataset, chunk, with_scores) if found is None else found
+
+    def _relation_ranks_kernel(self, model, dataset, chunk=4096, with_scores=False):
+        """``relation_ranks`` on ``mkb_rel_rank``; None when the library does not support the model's rows."""
+        dev = model.entity_embedding.device
+        _hip.require_device(model.entity_embedding)
+        model.sync_parameters()
+        n_ent, n_rel = model.n_entity, model.n_relation
+        triples = torch.as_tensor(np.asarray(dataset, dtype=np.int64).reshape(-1, 3), device=dev).contiguous()
+        limits = torch.tensor([n_ent, n_rel, n_ent], device=dev)
+        if len(triples) and bool(((triples < 0) | (triples >= limits)).any()):
+            raise ValueError("dataset holds an entity or relation id outside the model's tables")
+        keys = true_keys(self.true_triples, dev, n_ent, n_rel)["tail-batch"]  # sorted (h * R + r) * N + t
+        out = torch.empty(len(triples), dtype=torch.int64, device=dev)
+        scores = torch.empty((len(triples), n_rel), dtype=torch.float32, device=dev) if with_scores else None
+        lib, tb, ws = _hip.lib(), model._tables(), _hip.Workspace(dev)
+        with _hip.on_device(dev):
+            for lo in range(0, len(triples), chunk):
+                s = triples[lo: lo + chunk]
+                need = lib.mkb_rel_rank_workspace_bytes(tb, s.shape[0])
+                rc = lib.mkb_rel_rank(tb, _hip.ptr(s), s.shape[0], _hip.ptr(keys), keys.numel(), _hip.ptr(out[lo: lo + chunk]),
+                                      _hip.ptr(scores[lo: lo + chunk]) if with_scores else None, ws.ptr(need), need,
+                                      _hip.stream_ptr())
+                if rc == _hip.ERR_UNSUPPORTED:  # rows too long for the kernel: nothing was launched
+                    return None
+                _hip.check(rc, "mkb_rel_rank")
+        return (out, scores) if with_scores else out
+
+    def _relation_ranks_torch(self, model, dataset, chunk=4096, with_scores=False):
+        """``relation_ranks`` as torch glue around the general forward of the ``[b, R, 3]`` block of every chunk: the route of
+        shapes ``mkb_rel_rank`` does not support, and the device oracle of its tests."""
         dev = model.entity_embedding.device
         n_ent, n_rel = model.n_entity, model.n_relation
         keys = true_keys(self.true_triples, dev, n_ent, n_rel)["tail-batch"]  # sorted (h * R + r) * N + t
         triples = torch.as_tensor(np.asarray(dataset, dtype=np.int64).reshape(-1, 3), device=dev)
         cand = torch.arange(n_rel, device=dev)
-        out = []
+        out, blocks = [], []
         for lo in range(0, len(triples), chunk):
             s = triples[lo: lo + chunk]
             h, r, t = s[:, 0:1], s[:, 1:2], s[:, 2:3]
@@ -150,13 +199,18 @@ class Evaluation:
             bias = torch.where(true & (cand != r), -1.0, 0.0)
             neg = torch.stack([h.expand_as(k), rel, t.expand_as(k)], dim=-1)  # [b, R, 3]
             score = model(neg.contiguous()) + bias
+            if with_scores:  # the block before the filter: one more forward, of (h, r', t) itself
+                blocks.append(model(torch.stack([h.expand_as(k), cand.expand_as(k), t.expand_as(k)], dim=-1).contiguous()))
             # position in a stable descending sort with NaN first (see ranks_before in csrc/rank.hip): a collapsed or
             # diverged model must not rank its targets first
             key = torch.nan_to_num(score, nan=float("inf"), posinf=float("inf"))
             target = key.gather(1, r)
             before = (key > target) | ((key == target) & (cand < r))
             out.append(1 + before.sum(dim=1))
-        return torch.cat(out) if out else torch.empty(0, dtype=torch.int64, device=dev)
+        ranks = torch.cat(out) if out else torch.empty(0, dtype=torch.int64, device=dev)
+        if with_scores:
+            return ranks, (torch.cat(blocks) if blocks else torch.empty((0, n_rel), dtype=torch.float32, device=dev))
+        return ranks
 
     def eval_relations(self, model, dataset):
         metrics = _metrics()

@@ -7,6 +7,10 @@ python tools/eval_speed.py classif: triple classification on sets made by datase
 the device route and on the host route (device="cpu" after the scores: sort, cumulative sums; and the reference's own per-item
 Python loop for the accuracy), the device search apart from the scoring of the same call, and the search at 32,768 .. 262,144 items.
 
+python tools/eval_speed.py relations [Model ...]: the relation side of the same split -- evaluation.Evaluation.eval_relations as a whole
+call and relation_ranks alone, 20,466 triples x 237 relations, through the general forward of the [b, 237, 3] block with torch glue
+and through mkb_rel_rank.
+
 python tools/eval_speed.py classif cap: the sweep over sizes alone.  The device search refuses more than MKB_THRESHOLD_SEARCH_MAX_N
 items, so the sizes above it are measured on a build with a higher value (the measurement that placed the cap):
     python -c "import os; from mkb_amd.csrc import build; build.build(extra_flags=['-DMKB_THRESHOLD_SEARCH_MAX_N=262144'], out=os.path.abspath('variants/libmkb_hip_cap.so'), objdir=os.path.abspath('variants/obj_cap'))"
@@ -17,29 +21,57 @@ from mkb_amd import datasets, evaluation, models
 ds = datasets.Fb15k237(batch_size=1024, shuffle=False, seed=42, num_workers=0)
 
 
+class Best(float):  # the best of the runs, with all of them for the record
+    runs = ()
+
+def timed(call, runs=5):
+    call()  # warm: code objects, allocator
+    times, out = [], None
+    for _ in range(runs):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    best = Best(min(times))
+    best.runs = tuple(times)
+    return best, out
+
+def line(what, seconds, note=""):
+    runs = "  (runs: " + " ".join(f"{1e3 * t:.3f}" for t in seconds.runs) + ")" if getattr(seconds, "runs", ()) else ""
+    print(f"{what:58s} {1e3 * seconds:10.3f} ms{runs}  {note}", flush=True)
+
+
+def relations_speed(names):
+    """eval_relations as a whole call, and relation_ranks alone, on FB15k-237's test split at hidden 1000: through the torch glue
+    around the general forward (Evaluation._relation_ranks_torch) and through mkb_rel_rank (Evaluation._relation_ranks_kernel)."""
+    import mkb_amd.evaluation.evaluation as ev_mod
+
+    ev = evaluation.Evaluation(true_triples=ds.true_triples, entities=ds.entities, relations=ds.relations, batch_size=1024, device="cuda",
+                               num_workers=0)
+    print(f"test: {len(ds.test)} triples x {len(ds.relations)} relations, hidden 1000; best of 5 runs after one warm run, every run listed",
+          flush=True)
+    default = ev_mod.RELATION_KERNEL_MODELS
+    for name in names:
+        torch.manual_seed(1)
+        m = getattr(models, name)(hidden_dim=1000, entities=ds.entities, relations=ds.relations, gamma=9.0).cuda().eval()
+        with torch.no_grad():
+            t_old, r_old = timed(lambda: ev._relation_ranks_torch(m, ds.test))
+            t_new, r_new = timed(lambda: ev._relation_ranks_kernel(m, ds.test))
+        spread = max(t_old.runs) - min(t_old.runs)
+        line(f"{name} relation_ranks, general forward + torch", t_old, f"spread {1e3 * spread:.3f} ms")
+        line(f"{name} relation_ranks, mkb_rel_rank", t_new,
+             f"same ranks: {bool(torch.equal(r_old, r_new))}; faster by more than the spread: {bool(t_old - t_new > spread)}")
+        for route, members in (("general forward + torch", frozenset()), ("mkb_rel_rank", frozenset([name]))):
+            ev_mod.RELATION_KERNEL_MODELS = members
+            t, out = timed(lambda: ev.eval_relations(model=m, dataset=ds.test))
+            line(f"{name} eval_relations, {route}", t, str(out))
+        ev_mod.RELATION_KERNEL_MODELS = default
+
+
 def classif_speed(sweep_only=False):
     import numpy as np
     from mkb_amd import _hip
     from mkb_amd.evaluation import classif
-
-    class Best(float):  # the best of the runs, with all of them for the record
-        runs = ()
-
-    def timed(call, runs=5):
-        call()  # warm: code objects, allocator
-        times, out = [], None
-        for _ in range(runs):
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            out = call()
-            torch.cuda.synchronize()
-            times.append(time.perf_counter() - t0)
-        best = Best(min(times))
-        best.runs = tuple(times)
-        return best, out
-
-    def line(what, seconds, note=""):
-        runs = "  (runs: " + " ".join(f"{1e3 * t:.3f}" for t in seconds.runs) + ")" if getattr(seconds, "runs", ()) else ""
-        print(f"{what:58s} {1e3 * seconds:10.3f} ms{runs}  {note}", flush=True)
 
     R = len(ds.relations)
     if not sweep_only:
@@ -113,6 +145,9 @@ def classif_calls(timed, line, R):
     line("accuracy count, the reference's per-item loop (one run)", time.perf_counter() - t0, f"same count: {correct == int(counts[0, 0])}")
 
 
+if sys.argv[1:2] == ["relations"]:
+    relations_speed(sys.argv[2:] or ["TransE", "RotatE", "ComplEx", "DistMult", "pRotatE"])
+    sys.exit(0)
 if sys.argv[1:2] == ["classif"]:
     classif_speed(sweep_only=sys.argv[2:3] == ["cap"])
     sys.exit(0)

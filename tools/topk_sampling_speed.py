@@ -2,7 +2,9 @@
   - TopKSampling.get at B = 1024, split into the entity side (two mkb_topk_masked launches) and the relation side (the general
     forward of [B, 237, 3] plus mkb_topk_block);
   - building FastTopKSampling over the FB15k-237 training split;
-  - mkb_topk_masked with a 50 % mask against mkb_topk on the same 1024-query chunk.
+  - mkb_topk_masked with a 50 % mask against mkb_topk on the same 1024-query chunk;
+  - TopKSampling.side("relation") at B = 1024 for the five teachers at hidden 1000, through the general forward and through
+    mkb_rel_scores: five measurements of --reps calls each, every one listed.
 
     python tools/topk_sampling_speed.py [--reps 20]
 
@@ -79,6 +81,16 @@ def main():
             out[f"mkb_topk_k{k}_ms"] = timed(lambda: _launch(teacher, sample, "tail-batch", k, none, 0, None, 1024, ids_k, sc_k), args.reps)
             out[f"mkb_topk_masked50_k{k}_ms"] = timed(lambda: _launch(teacher, sample, "tail-batch", k, none, 0, half, 1024, ids_k, sc_k),
                                                       args.reps)
+        for name in ("TransE", "RotatE", "ComplEx", "DistMult", "pRotatE"):
+            e_tab, r_tab, mod = eval_tables(name, seed=77)
+            t = make_model(name, e_tab, r_tab, 1000, 9.0, mod).eval()
+            sampler.RELATION_KERNEL_MODELS = frozenset([name])
+            same = all(torch.equal(x, y) for x, y in zip(sampler.side("relation", sample, t), sampler._relation_side_general(sample, t)))
+            for route, fn in (("general", lambda: sampler._relation_side_general(sample, t)), ("kernel", lambda: sampler.side("relation", sample, t))):
+                out[f"relation_side_{name}_{route}_ms"] = [round(timed(fn, args.reps), 4) for _ in range(5)]
+            out[f"relation_side_{name}_same_ids"] = same
+            del t
+        del sampler.RELATION_KERNEL_MODELS
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
