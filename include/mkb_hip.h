@@ -499,6 +499,30 @@ int64_t mkb_rel_topk_workspace_bytes(const mkb_tables_t *tb, int64_t B, int k);
 int mkb_rel_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *true_keys, int64_t n_true,
                  int k, int flags, int64_t *ids, float *scores, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- candidate lists in any one slot of a triple, differentiable ---------------------------------------------------
+ * What distillation.Distillation.distill scores (distillation/distillation.py:82-92): for row i of sample [B, 3] the M triples
+ * that replace column `part` of the row by cand[i, 0 .. M) (mkb_amd/csrc/score_relation.hip).  New symbols under ABI 8: the
+ * version is not bumped.
+ *   mkb_cand_score_fwd: score[i, j] has the bits mkb_score_fwd gives the substituted triple in MKB_MODE_DEFAULT.  The column of
+ *   sample that `part` names is not read.  cand [B, M] int64 device: entity ids (head, tail) or relation ids; duplicates and the
+ *   row's own ids allowed.  An id outside its table is read (and its gradient added) as the nearest row of the table: the glue
+ *   flags it with mkb_check_ids.
+ *   mkb_cand_score_bwd: accumulates d loss / d tables given dscore [B, M] into gr (never zeroed; g_modulus for pRotatE).  Head
+ *   and relation part: a row pass (one workgroup per row: the two fixed operands' gradients, one atomic per element and row) and
+ *   a candidate pass over the B*M pairs radix-sorted by candidate (the varying table's gradient, one atomic per element and run
+ *   of equal candidates in a 64-pair chunk).  Tail part: the general two-pass backward of mkb_score_bwd in tail-batch mode.
+ *   ws: mkb_cand_score_bwd_workspace_bytes(tb, B, M, part) bytes, 256-byte aligned, caller-owned; nothing is allocated in a call.
+ *   0 <= B <= 2^31 - 1, 1 <= M, B * M <= 2^31 - 1; B == 0 is a valid call that launches nothing.  A null pointer, a bad B / M /
+ *   part, a short or misaligned workspace, an unknown model -> MKB_ERR_INVALID before any launch; entity rows too long for the LDS
+ *   staging ((2 + 4) * entity_dim * 4 > 64 KB) -> MKB_ERR_UNSUPPORTED for every part.  The workspace function returns 0 for
+ *   B <= 0, M < 1, a bad part or null tables. */
+typedef enum { MKB_PART_HEAD = 0, MKB_PART_RELATION = 1, MKB_PART_TAIL = 2 } mkb_part_t;
+int mkb_cand_score_fwd(const mkb_tables_t *tb, const int64_t *sample, const int64_t *cand, int64_t B, int64_t M, int part,
+                       float *score, void *stream);
+int64_t mkb_cand_score_bwd_workspace_bytes(const mkb_tables_t *tb, int64_t B, int64_t M, int part);
+int mkb_cand_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const int64_t *cand, int64_t B,
+                       int64_t M, int part, const float *dscore, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

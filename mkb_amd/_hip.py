@@ -18,6 +18,7 @@ ABI_VERSION = 8  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a sy
 
 MODEL_IDS = {"TransE": 0, "RotatE": 1, "ComplEx": 2, "DistMult": 3, "pRotatE": 4}
 MODE_DEFAULT, MODE_HEAD, MODE_TAIL = 0, 1, 2
+PART_HEAD, PART_RELATION, PART_TAIL = 0, 1, 2  # mkb_part_t
 ERR_INVALID, ERR_KEY, ERR_EMPTY, ERR_UNSUPPORTED = -1, -3, -4, -5
 TOPK_MAX_K, TOPK_KEEP_TARGET = 1024, 1  # MKB_TOPK_MAX_K, MKB_TOPK_KEEP_TARGET
 THRESHOLD_SEARCH_MAX_N = 131072  # MKB_THRESHOLD_SEARCH_MAX_N
@@ -151,6 +152,10 @@ _SIGNATURES = {
     "mkb_rel_topk_workspace_bytes": (c_int64, [POINTER(Tables), c_int64, c_int]),
     "mkb_rel_topk": (c_int, [POINTER(Tables), c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
                              c_void_p]),
+    "mkb_cand_score_fwd": (c_int, [POINTER(Tables), c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "mkb_cand_score_bwd_workspace_bytes": (c_int64, [POINTER(Tables), c_int64, c_int64, c_int]),
+    "mkb_cand_score_bwd": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                   c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -76,6 +76,65 @@ class _ScoreFn(torch.autograd.Function):
         return (g_ent if fresh_e else None), (g_rel if fresh_r else None), g_mod, None, None, None, None
 
 
+PARTS = {"head": _hip.PART_HEAD, "relation": _hip.PART_RELATION, "tail": _hip.PART_TAIL}  # mkb_part_t = the column of a triple
+
+
+class _Unsupported(Exception):
+    """mkb_cand_score_fwd answered MKB_ERR_UNSUPPORTED: the caller keeps the block route."""
+
+
+def _part_rows(sample, cand, part):
+    """int64 ids of the (entity rows, relation rows) that the scores of ``cand`` in column ``part`` of ``sample`` read and whose
+    gradient rows their backward writes; the column itself is not read."""
+    if part == 1:
+        return sample[:, 0::2].reshape(-1), cand.reshape(-1)
+    return torch.cat([sample[:, 2 - part], cand.reshape(-1)]), sample[:, 1]
+
+
+class _CandScoreFn(torch.autograd.Function):
+    """score[i, j] = the score of sample[i] with column ``part`` replaced by cand[i, j]; backward = dense d loss / d tables."""
+
+    @staticmethod
+    def forward(ctx, ent, rel, modulus, model, sample, cand, part):
+        B, M = cand.shape
+        score = torch.empty((B, M), dtype=torch.float32, device=ent.device)
+        tb = model._tables(ent, rel, modulus)
+        with _hip.on_device(ent.device):
+            rc = _hip.lib().mkb_cand_score_fwd(tb, _hip.ptr(sample), _hip.ptr(cand), B, M, part, _hip.ptr(score), _hip.stream_ptr())
+        if rc == _hip.ERR_UNSUPPORTED:
+            raise _Unsupported()
+        _hip.check(rc, "mkb_cand_score_fwd")
+        ctx.model, ctx.part = model, part
+        ctx.save_for_backward(ent, rel, modulus, sample, cand)
+        return score
+
+    @staticmethod
+    def backward(ctx, dscore):
+        ent, rel, modulus, sample, cand = ctx.saved_tensors
+        model, part = ctx.model, ctx.part
+        B, M = cand.shape
+        dscore = _hip.contiguous(dscore, torch.float32)
+        # (a row-lazy optimizer's table takes its rows straight into .grad: _gradshare.direct; as in _ScoreFn.backward)
+        g_ent = g_rel = None
+        if _few(cand):
+            g_ent = _gradshare.direct(model.entity_embedding, ent, lambda: _part_rows(sample, cand, part)[0])
+            g_rel = _gradshare.direct(model.relation_embedding, rel, lambda: _part_rows(sample, cand, part)[1])
+        fresh_e = fresh_r = False
+        if g_ent is None:
+            g_ent, fresh_e = _gradshare.take(model.entity_embedding, ent)
+        if g_rel is None:
+            g_rel, fresh_r = _gradshare.take(model.relation_embedding, rel)
+        g_mod = torch.zeros_like(modulus) if model.name == "pRotatE" else None
+        tb = model._tables(ent, rel, modulus)
+        gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
+        with _hip.on_device(ent.device):
+            n_ws = _hip.lib().mkb_cand_score_bwd_workspace_bytes(tb, B, M, part)  # the glue owns every buffer (mkb_hip.h)
+            ws = _hip.aligned_bytes(n_ws, ent.device) if n_ws > 0 else None
+            _hip.check(_hip.lib().mkb_cand_score_bwd(tb, gr, _hip.ptr(sample), _hip.ptr(cand), B, M, part, _hip.ptr(dscore),
+                                                     _hip.ptr(ws), max(n_ws, 0), _hip.stream_ptr()), "mkb_cand_score_bwd")
+        return (g_ent if fresh_e else None), (g_rel if fresh_r else None), g_mod, None, None, None, None
+
+
 # candidate lists up to this many ids are made current row by row in front of a forward pass (and their gradient rows recorded
 # one by one behind the backward pass) when the table steps row-lazily; longer ones flush the table / take the dense gradient
 DIRECT_MAX_IDS = 16384
@@ -178,9 +237,10 @@ class BaseModel(Base):
             if opt is not None:
                 opt.flush(p)
 
-    def _make_current(self, sample, entity_ids):
-        """``optim.Adam.before_forward`` for the tables a row-lazy optimizer steps (the flush this replaces was 150 us per call)."""
-        for p, ids in ((self.entity_embedding, entity_ids), (self.relation_embedding, False)):
+    def _make_current(self, sample, entity_ids, relation_ids=False):
+        """``optim.Adam.before_forward`` for the tables a row-lazy optimizer steps (the flush this replaces was 150 us per call).
+        ``relation_ids``: the relation rows read, where they are not ``sample``'s own."""
+        for p, ids in ((self.entity_embedding, entity_ids), (self.relation_embedding, relation_ids)):
             opt = _links.owner(p)
             if opt is not None:
                 opt.before_forward(p, sample[:, 1] if ids is False else ids)
@@ -251,7 +311,53 @@ class BaseModel(Base):
         score = _ScoreFn.apply(self.entity_embedding, self.relation_embedding, modulus, self, sample, cand, mode_id)
         return score.view(shape)
 
+    def score_candidates(self, sample, candidates, part):
+        """float32 ``[B, M]``: ``out[i, j]`` is the score of the triple ``sample[i]`` with its ``part`` (``"head"``, ``"relation"``
+        or ``"tail"``) replaced by ``candidates[i, j]`` -- the bits of ``model(block)`` on the substituted ``[B, M, 3]`` block, and
+        differentiable like it -- without gathering the two rows that a row's candidates share once per candidate (forward), nor
+        adding to their gradient once per candidate (backward).  The ``part`` column of ``sample`` is not read.  Ids are handled
+        as in ``forward``: an id outside its table surfaces as IndexError at ``model.check_ids()``."""
+        if part not in PARTS:
+            raise ValueError(f"part must be one of 'head', 'relation', 'tail', not {part!r}")
+        _hip.require_device(self.entity_embedding, sample, candidates)
+        if sample.dim() != 2 or sample.shape[1] != 3 or candidates.dim() != 2 or candidates.shape[0] != sample.shape[0]:
+            raise ValueError("sample must be [B, 3] and candidates [B, M]")
+        col = PARTS[part]
+        sample, cand = _hip.contiguous(sample, torch.int64), _hip.contiguous(candidates, torch.int64)
+        if cand.numel() == 0:  # an empty batch (or no candidates): no launch; differentiable, backward adds nothing
+            return (self.entity_embedding.sum() * 0.0).expand(cand.shape)
+        if VALIDATE_IDS:
+            self._launch_candidate_check(sample, cand, col)
+        if _links.owner(self.entity_embedding) is not None or _links.owner(self.relation_embedding) is not None:
+            ent_ids, rel_ids = _part_rows(sample, cand, col) if _few(cand) else (None, None)
+            self._make_current(sample, ent_ids, rel_ids)
+        modulus = getattr(self, "modulus", None)
+        if modulus is None:  # autograd.Function needs a tensor slot; never read by the kernels
+            modulus = self.gamma
+        try:
+            return _CandScoreFn.apply(self.entity_embedding, self.relation_embedding, modulus, self, sample, cand, col)
+        except _Unsupported:  # rows too long for the kernel's LDS staging: the general kernels on the substituted block
+            block = sample.unsqueeze(1).repeat(1, cand.shape[1], 1)
+            block[:, :, col] = cand
+            return self(block)
+
     # ------------------------------------------------------------------ id validation
+    def _launch_candidate_check(self, sample, cand, col):
+        """``_launch_id_check`` for ``score_candidates``: the two columns of ``sample`` that are read, and the candidates against
+        the table they index (relation candidates have a flag of their own: ``mkb_check_ids`` knows candidates as entities)."""
+        checked = sample.clone()
+        checked[:, col] = 0
+        if col != 1:
+            return self._launch_id_check(checked, cand)
+        self._launch_id_check(checked, None)
+        dev = self.entity_embedding.device
+        flag = self.__dict__.get("_rel_cand_flag")
+        if flag is None or flag.device != dev:
+            flag = self.__dict__["_rel_cand_flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        with _hip.on_device(dev):
+            _hip.check(_hip.lib().mkb_check_ids(None, 0, _hip.ptr(cand), cand.numel(), self.n_relation, self.n_relation,
+                                                _hip.ptr(flag), _hip.stream_ptr()), "mkb_check_ids")
+
     def _launch_id_check(self, sample, negative_sample):
         """One small launch (``mkb_check_ids``) that flags ids outside the tables; nothing is synchronised here.  The
         reference's ``index_select`` raises IndexError on such ids; the kernels index the tables directly."""
@@ -269,13 +375,16 @@ class BaseModel(Base):
     def check_ids(self):
         """Raise IndexError if any ``model(sample, negative_sample)`` call since the last check used an id outside the
         tables (synchronises; ``compose.Pipeline`` calls it once per epoch, like ``sampling.check()``)."""
-        flag = self.__dict__.get("_id_flag")
-        if flag is None:
+        flag, rel_flag = self.__dict__.get("_id_flag"), self.__dict__.get("_rel_cand_flag")
+        if flag is None and rel_flag is None:
             return
-        bits = int(flag.item())
+        bits = (int(flag.item()) if flag is not None else 0) | (8 if rel_flag is not None and int(rel_flag.item()) else 0)
         if bits:
-            flag.zero_()
-            what = [name for bit, name in ((1, "entity id in sample"), (2, "relation id in sample"), (4, "candidate entity id")) if bits & bit]
+            for f in (flag, rel_flag):
+                if f is not None:
+                    f.zero_()
+            what = [name for bit, name in ((1, "entity id in sample"), (2, "relation id in sample"), (4, "candidate entity id"),
+                                           (8, "candidate relation id")) if bits & bit]
             raise IndexError("index out of range in self: " + ", ".join(what)
                              + f" (tables hold {self.n_entity} entities, {self.n_relation} relations)")
 
