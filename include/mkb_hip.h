@@ -105,6 +105,27 @@ int mkb_adversarial(const float *pos, const float *neg, const float *weight, con
                     int64_t K, float alpha, const float *weight_sum, float *loss, float *dpos, float *dneg,
                     float *scratch, void *stream);
 
+/* ---- negative-sampling loss family: margin ranking, pairwise logistic, sampled softmax ----------------------
+ * No reference counterpart (the reference trains with Adversarial only); mkb_amd/csrc/ns_loss.hip.  New symbol under ABI 8: the
+ * version is not bumped.  pos [B], neg [B, K] row-major, weight [B] or null (all ones), cnt [B, K] uint16 or null (all ones):
+ * per-column multiplicities c_ij as for mkb_adversarial.  W = sum of weight (B when weight is null), or weight_sum[0] when given
+ * (the rows are a shard, as for mkb_adversarial).  Scores are "higher is more plausible".
+ *   MKB_LOSS_MARGIN / MKB_LOSS_PAIR_LOGISTIC (param = margin): a_ij = param + neg_ij - pos_i, row_i = sum_j p_ij f(a_ij) with
+ *     f = max(0, a) / softplus(a) and the detached weight p_ij = c_ij exp(alpha neg_ij) / sum_l c_il exp(alpha neg_il)
+ *     (alpha = 0: c_ij / C_i);  dneg_ij = (w_i / W) p_ij f'(a_ij) (margin: 1 where a > 0, else 0), dpos_i = -sum_j dneg_ij.
+ *   MKB_LOSS_SOFTMAX (param = temperature T > 0; alpha is not used): row_i = log(exp(pos_i / T) + sum_j c_ij exp(neg_ij / T))
+ *     - pos_i / T;  dneg_ij = (w_i / (W T)) c_ij exp(neg_ij / T) / Z_i, dpos_i = (w_i / (W T)) (exp(pos_i / T) / Z_i - 1).
+ *   loss [1] = sum_i w_i row_i / W; dpos [B], dneg [B, K] = d loss / d pos, d loss / d neg.  A position with c_ij = 0 takes no part:
+ *   its neg value is not used (it may be NaN) and its dneg is written as 0; a row that uses no position contributes 0.
+ * scratch: B + 1 floats.  Forward and seeds in one pass over each row; fixed-order reductions, no float atomics: two runs give the
+ * same bits.  Any K (rows of more than 1024 columns are re-read from global memory instead of staged in LDS).
+ * A null pos / neg / loss / dpos / dneg / scratch, an unknown kind, B < 1, K < 1, B * K > 2^31 - 1, alpha < 0 or not finite, a
+ * non-finite param, T <= 0 for the softmax -> MKB_ERR_INVALID before any launch. */
+typedef enum { MKB_LOSS_MARGIN = 0, MKB_LOSS_PAIR_LOGISTIC = 1, MKB_LOSS_SOFTMAX = 2 } mkb_loss_t;
+int mkb_ns_loss(int kind, const float *pos, const float *neg, const float *weight, const uint16_t *cnt, int64_t B, int64_t K,
+                float param, float alpha, const float *weight_sum, float *loss, float *dpos, float *dneg, float *scratch,
+                void *stream);
+
 /* ---- negative sampler --------------------------------------------------------------------------------
  * mkb_sampler_create == sampling.NegativeSampling.__init__ (negative_sampling.py:133-151): takes the two
  *   filter dictionaries of positive_triples() (negative_sampling.py:7-28) as CSR on the HOST:

@@ -22,6 +22,7 @@ PART_HEAD, PART_RELATION, PART_TAIL = 0, 1, 2  # mkb_part_t
 ERR_INVALID, ERR_KEY, ERR_EMPTY, ERR_UNSUPPORTED = -1, -3, -4, -5
 TOPK_MAX_K, TOPK_KEEP_TARGET = 1024, 1  # MKB_TOPK_MAX_K, MKB_TOPK_KEEP_TARGET
 THRESHOLD_SEARCH_MAX_N = 131072  # MKB_THRESHOLD_SEARCH_MAX_N
+LOSS_MARGIN, LOSS_PAIR_LOGISTIC, LOSS_SOFTMAX = 0, 1, 2  # mkb_loss_t
 
 
 def mode_id(mode):
@@ -72,6 +73,8 @@ _SIGNATURES = {
                               c_void_p, c_void_p]),
     "mkb_adversarial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mkb_ns_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "mkb_sampler_create": (c_int, [POINTER(c_void_p), c_int64, c_int64, c_int64, c_uint32, c_void_p, c_int64, c_void_p,
                                    c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mkb_sampler_generate": (c_int, _SAMPLER_TAIL),

@@ -13,14 +13,18 @@ README, or ``mkb_amd.optim.Adam``).
 import torch
 
 from ..datasets.device import DeviceBatches
-from ..fused import FusedTrainStep, pooled_supported
-from ..losses import Adversarial
+from ..fused import FusedTrainStep, PooledLossStep, pooled_supported
+from ..losses import Adversarial, CrossEntropy, MarginRanking, PairwiseLogistic
 from ..models.base import BaseModel
 from ..sampling import NegativeSampling
 from ..utils import Bar, RollingMean
 
 __all__ = ["Pipeline"]
 
+
+# the losses routed to fused.PooledLossStep: measured ahead of the explicit sequence for every (model, loss) cell
+# (profiles/r17_loss_family_speed.txt)
+_POOLED_LOSSES = (MarginRanking, PairwiseLogistic, CrossEntropy)
 
 _WATCHED = ("HITS@3", "HITS@1")  # a round only counts as "no improvement" when both fall (pipeline.py:272-299)
 
@@ -91,9 +95,10 @@ class Pipeline:
 
     # ------------------------------------------------------------------ one epoch of steps (pipeline.py:206-244)
     def _fused_step_for(self, model, dataset, sampling, optimizer, loss):
-        """``FusedTrainStep`` when model, sampler and loss are the mkb_amd ones on a ROCm device, else None."""
+        """``FusedTrainStep`` (``Adversarial``) or ``PooledLossStep`` (``MarginRanking`` / ``PairwiseLogistic`` / ``CrossEntropy``)
+        when model, sampler and loss are the mkb_amd ones on a ROCm device, else None."""
         if not (self.fuse and isinstance(model, BaseModel) and isinstance(sampling, NegativeSampling)
-                and type(loss) is Adversarial and model.entity_embedding.is_cuda
+                and type(loss) in (Adversarial,) + _POOLED_LOSSES and model.entity_embedding.is_cuda
                 and pooled_supported(model, dataset.batch_size, sampling.size)):
             return None
         self._borrowed = []  # optimizer settings this loop switches on and learn() switches back off before it returns
@@ -104,6 +109,8 @@ class Pipeline:
             optimizer.defer_step = True  # this loop clears gradients through optimizer.zero_grad() only: the real step of
             #                              the touched rows may wait for the next catch-up launch (mkb_amd/optim.py)
             self._borrowed.append("defer_step")
+        if type(loss) in _POOLED_LOSSES:
+            return PooledLossStep(model, loss)
         return FusedTrainStep(model, loss.alpha)
 
     def _give_back(self, optimizer):

@@ -8,58 +8,16 @@
 //   softmax and the sums run over columns weighted by cnt; dneg_ij is the summed gradient of its copies.
 //
 // One launch up to 8192 rows: every workgroup (one wave per row, 4 rows) first reduces W itself with the fixed tree
-//   below (B / 256 loads per lane from L2; bit-identical in every workgroup), then row max / partition sum / weighted
+//   of loss_math.h (B / 256 loads per lane from L2; bit-identical in every workgroup), then row max / partition sum / weighted
 //   log-sigmoid sum with wave64 shuffle reductions, writes dpos, dneg and the per-row partial.  A second single-
 //   workgroup kernel sums the partials in a fixed order -- or, inside mkb_pool_step, the last workgroup of the row
 //   backward kernel does (adversarial_finish_block), so the fused step spends ONE launch on the loss.
 //   No float atomics: the loss is bit-reproducible run to run.
 #include "common.h"
+#include "loss_math.h"
 #include "model_math.h"
 
 namespace mkb {
-
-// (the first 256 lanes of the workgroup do the work: the same tree, hence the same bits, for 256- and 512-lane workgroups)
-__device__ __forceinline__ float block_sum_256(float v, float *red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0 && wave < 4) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-// the same sum with its first four strides' loads already made by the caller (v[z] = w[min(tid + 256 z, B - 1)], lanes < 256):
-// the loss rows request them in front of their own loads
-__device__ __forceinline__ float weight_sum_block_ahead(const float *__restrict__ w, int B, float *red, const float (&v)[4]) {
-    float acc = 0.f;
-    if (threadIdx.x < 256) {
-#pragma unroll
-        for (int z = 0; z < 4; ++z) acc += (int)threadIdx.x + 256 * z < B ? v[z] : 0.f;
-        for (int i0 = threadIdx.x + 1024; i0 < B; i0 += 1024) {
-            float u[4];
-#pragma unroll
-            for (int z = 0; z < 4; ++z) u[z] = w[min(i0 + 256 * z, B - 1)];
-#pragma unroll
-            for (int z = 0; z < 4; ++z) acc += i0 + 256 * z < B ? u[z] : 0.f;
-        }
-    }
-    return block_sum_256(acc, red);
-}
-
-__device__ __forceinline__ float weight_sum_block(const float *__restrict__ w, int B, float *red) {
-    // four strides' loads at a time (a loop with a run-time trip count is one round trip per iteration: every workgroup of the
-    // loss launch walked 1024 weights in four of them); added in the order of the plain loop
-    float acc = 0.f;
-    if (threadIdx.x < 256)
-        for (int i0 = threadIdx.x; i0 < B; i0 += 1024) {
-            float v[4];
-#pragma unroll
-            for (int z = 0; z < 4; ++z) v[z] = w[min(i0 + 256 * z, B - 1)];
-#pragma unroll
-            for (int z = 0; z < 4; ++z) acc += i0 + 256 * z < B ? v[z] : 0.f;
-        }
-    return block_sum_256(acc, red);
-}
 
 // scal[0] = W
 __global__ __launch_bounds__(256) void weight_sum_kernel(const float *__restrict__ w, int B, float *__restrict__ scal) {
@@ -67,15 +25,6 @@ __global__ __launch_bounds__(256) void weight_sum_kernel(const float *__restrict
     const float acc = weight_sum_block(w, B, red);
     if (threadIdx.x == 0) scal[0] = acc;
 }
-
-// exp / log on the hardware transcendental unit (v_exp_f32 / v_log_f32, ~1 ulp of the base-2 function): the arguments
-// here are scores of magnitude <= ~20, so exp's relative error stays ~1e-6 and log1p's absolute error ~1e-7 -- two
-// orders below the 1e-4 / 1e-5 parity tolerances -- at a tenth of the instructions of the correctly rounded libm forms.
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-__device__ __forceinline__ float fast_log_sigmoid(float z) {  // min(z,0) - log1p(exp(-|z|)), the form ATen uses
-    return fminf(z, 0.f) - 0.69314718055994531f * __builtin_amdgcn_logf(1.f + fast_exp(-fabsf(z)));
-}
-__device__ __forceinline__ float fast_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.f + fast_exp(-z)); }
 
 // one wave per row; rowpart[i] = w_i * (ps_i + ns_i).
 // Columns are handled 64 at a time (column group t: lane l owns column l + 64 t).  Rows of up to kStageCols columns are read

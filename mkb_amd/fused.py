@@ -7,13 +7,16 @@
 ``FusedTrainStep``   -- one call = lines 211-236 of the reference's compose/pipeline.py (positive forward,
                         negative forward, Adversarial, backward into dense ``.grad``) through ``mkb_pool_step``,
                         bypassing autograd.  Used by ``compose.Pipeline`` when model / sampler / loss are ours.
+``PooledLossStep``   -- the same step for ``losses.MarginRanking`` / ``PairwiseLogistic`` / ``CrossEntropy``: the separate
+                        pooled entry points around ``mkb_ns_loss``, bypassing autograd.
 """
 import torch
 
 from . import _gradshare, _hip, _links
+from .losses import ns_losses
 from .sampling.negative_sampling import PoolInfo
 
-__all__ = ["FusedTrainStep", "pooled_forward", "pooled_supported"]
+__all__ = ["FusedTrainStep", "PooledLossStep", "pooled_forward", "pooled_supported"]
 
 _workspaces = {}
 
@@ -171,6 +174,76 @@ class FusedTrainStep:
                                                 _hip.ptr(info.cnt), B, K, mode_id, self.alpha, _hip.ptr(weight_sum),
                                                 _hip.ptr(pos), _hip.ptr(S),
                                                 _hip.ptr(loss), _hip.ptr(ws), _hip.stream_ptr()), "mkb_pool_step")
+        self.positive_score, self._S, self._info = pos, S, info
+        return loss.reshape(())
+
+    @property
+    def negative_score(self):
+        return self._S.gather(1, self._info.pos.long())
+
+
+class PooledLossStep:
+    """``FusedTrainStep`` for a loss of the ``mkb_ns_loss`` family (``losses.MarginRanking``, ``PairwiseLogistic``, ``CrossEntropy``):
+    ``loss = step(sample, weight, negative_sample, mode)`` fills ``param.grad`` (dense, accumulated) and returns the loss as a
+    0-dim device tensor; ``positive_score`` [B,1] and ``negative_score`` [B,size] of the last call stay available.
+
+    Five library calls, no autograd: positive scores (``mkb_score_fwd``), pool scores (``mkb_pool_score_fwd``), ``mkb_ns_loss``
+    over the ``[B, 2 size]`` pool block with the sampler's multiplicities, then ``mkb_pool_score_bwd`` on its seeds and the
+    positive pair's ``mkb_score_bwd``.  Against the explicit autograd sequence this drops the gather of the ``[B, size]`` view,
+    the scatter of its gradient back onto pool positions and the dense zero-filled buffers autograd adds into ``.grad``."""
+
+    def __init__(self, model, loss):
+        if getattr(loss, "kind", None) not in (_hip.LOSS_MARGIN, _hip.LOSS_PAIR_LOGISTIC, _hip.LOSS_SOFTMAX):
+            raise TypeError("PooledLossStep takes losses.MarginRanking, losses.PairwiseLogistic or losses.CrossEntropy")
+        self.model, self.loss = model, loss
+
+    def sampled(self, sample, weight, sampler, mode, weight_sum=None):
+        return sampled_step(self, sample, weight, sampler, mode, weight_sum=weight_sum)
+
+    def __call__(self, sample, weight, negative_sample, mode, weight_sum=None):
+        """``weight_sum``: as for ``FusedTrainStep`` (the sum of weights of the whole batch when these rows are a shard of it)."""
+        m = self.model
+        info = getattr(negative_sample, "_mkb_pool", None)
+        if info is None:
+            raise ValueError("negative_sample does not come from mkb_amd.sampling.NegativeSampling.generate")
+        mode_id = _hip.mode_id(mode)
+        sample = _hip.contiguous(sample, torch.int64)
+        weight = None if weight is None else _hip.contiguous(weight, torch.float32)
+        _hip.require_device(m.entity_embedding, sample, weight)
+        B, K = sample.shape[0], info.size
+        dev = sample.device
+        pos = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        S = torch.empty((B, 2 * K), dtype=torch.float32, device=dev)
+        ws = _workspace(m, B, K)
+        gr = grad_buffers(m)
+        ent = m.entity_embedding
+        lazy = _links.owner(ent)
+        if lazy is not None:
+            # row-lazy Adam: the rows read become current, and are marked as written, before anything writes a gradient row.
+            # (rows_clear stays 0 whatever this answers: the promise is only honoured by mkb_pool_step / _bwd, and the two
+            # backward calls below both add to the rows of the batch's heads and tails -- they must accumulate.)
+            lazy.begin_step_on(ent, info.rows(sample))
+        lib, tb, st = _hip.lib(), m._tables(), _hip.stream_ptr(dev)
+        with _hip.on_device(dev):
+            _hip.check(lib.mkb_score_fwd(tb, _hip.ptr(sample), None, B, 1, _hip.MODE_DEFAULT, _hip.ptr(pos), st), "mkb_score_fwd")
+            _hip.check(lib.mkb_pool_score_fwd(tb, _hip.ptr(sample), _hip.ptr(info.pool), _hip.ptr(info.cnt), B, K, mode_id,
+                                              _hip.ptr(S), _hip.ptr(ws), st), "mkb_pool_score_fwd")
+        loss, dpos, dS = ns_losses.launch(self.loss.kind, pos, S, weight, info.cnt, float(self.loss.param), float(self.loss.alpha),
+                                          weight_sum)
+        # pRotatE's modulus: one scalar takes every pair's term, and the negatives' total and the positives' total nearly cancel.
+        # Each backward call sums its own from zero and the two totals are added once, as autograd does for the explicit
+        # sequence; the positives' small terms added one by one onto the negatives' large total lose its low bits.
+        parts = [gr, gr]
+        if gr.g_modulus:
+            mod_parts = torch.zeros((2,) + tuple(m.modulus.shape), dtype=torch.float32, device=dev)
+            parts = [_hip.Grads(gr.g_ent, gr.g_rel, mod_parts[k].data_ptr()) for k in range(2)]
+        with _hip.on_device(dev):
+            _hip.check(lib.mkb_pool_score_bwd(tb, parts[0], _hip.ptr(sample), _hip.ptr(info.pool), _hip.ptr(info.cnt), B, K, mode_id,
+                                              _hip.ptr(dS), _hip.ptr(ws), st), "mkb_pool_score_bwd")
+            _hip.check(lib.mkb_score_bwd(tb, parts[1], _hip.ptr(sample), None, B, 1, _hip.MODE_DEFAULT, _hip.ptr(dpos), None, st),
+                       "mkb_score_bwd")
+        if gr.g_modulus:
+            m.modulus.grad += mod_parts[0] + mod_parts[1]
         self.positive_score, self._S, self._info = pos, S, info
         return loss.reshape(())
 

@@ -1,4 +1,5 @@
 from .adversarial import Adversarial
 from .kl_divergence import KlDivergence
+from .ns_losses import CrossEntropy, MarginRanking, PairwiseLogistic
 
-__all__ = ["Adversarial", "KlDivergence"]
+__all__ = ["Adversarial", "KlDivergence", "MarginRanking", "PairwiseLogistic", "CrossEntropy"]

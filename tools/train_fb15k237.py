@@ -2,6 +2,11 @@
 FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamma=9, Adam.
 
     python tools/train_fb15k237.py [--epochs 200] [--lr 5e-5] [--eval-every 50] [--model RotatE]
+                                   [--loss adversarial|margin|pairwise|softmax]
+
+--loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
+--alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
+PooledLossStep.
 
 Uses the public mkb_amd API only (models / sampling / losses / compose.Pipeline-equivalent loop / evaluation) plus
 the device batch producer.  Prints one JSON line per evaluation."""
@@ -14,7 +19,7 @@ import torch
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from mkb_amd import datasets, evaluation, losses, models, optim, sampling  # noqa: E402
-from mkb_amd.fused import FusedTrainStep  # noqa: E402
+from mkb_amd.fused import FusedTrainStep, PooledLossStep  # noqa: E402
 
 
 def main():
@@ -29,6 +34,8 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--dataset", default="Fb15k237")
+    ap.add_argument("--loss", default="adversarial", choices=["adversarial", "margin", "pairwise", "softmax"])
+    ap.add_argument("--temperature", type=float, default=1.0, help="--loss softmax")
     ap.add_argument("--no-defer", action="store_true", help="apply the optimizer step at once (one more launch per step)")
     args = ap.parse_args()
 
@@ -41,7 +48,12 @@ def main():
                                         relations=ds.relations, seed=42)
     opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=sampler,
                      defer_step=not args.no_defer)  # gradients are cleared through opt.zero_grad() only: the step may wait
-    step = FusedTrainStep(model, args.alpha)
+    if args.loss == "adversarial":
+        step = FusedTrainStep(model, args.alpha)
+    else:
+        step = PooledLossStep(model, {"margin": lambda: losses.MarginRanking(margin=args.gamma, alpha=args.alpha),
+                                      "pairwise": lambda: losses.PairwiseLogistic(margin=0.0, alpha=args.alpha),
+                                      "softmax": lambda: losses.CrossEntropy(temperature=args.temperature)}[args.loss]())
     ev = evaluation.Evaluation(true_triples=ds.true_triples, entities=ds.entities, relations=ds.relations,
                                batch_size=1024, device="cuda", num_workers=0)
     n_steps, t_train = 0, 0.0
