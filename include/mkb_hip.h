@@ -522,7 +522,7 @@ int mkb_rel_topk(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const
 
 /* ---- candidate lists in any one slot of a triple, differentiable ---------------------------------------------------
  * What distillation.Distillation.distill scores (distillation/distillation.py:82-92): for row i of sample [B, 3] the M triples
- * that replace column `part` of the row by cand[i, 0 .. M) (mkb_amd/csrc/score_relation.hip).  New symbols under ABI 8: the
+ * that replace column `part` of the row by cand[i, 0 .. M) (mkb_amd/csrc/score_cand.hip).  New symbols under ABI 8: the
  * version is not bumped.
  *   mkb_cand_score_fwd: score[i, j] has the bits mkb_score_fwd gives the substituted triple in MKB_MODE_DEFAULT.  The column of
  *   sample that `part` names is not read.  cand [B, M] int64 device: entity ids (head, tail) or relation ids; duplicates and the

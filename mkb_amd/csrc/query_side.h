@@ -1,8 +1,8 @@
 // The query side of a score, written once: every score is pair(q_i, x) (model_math.h), q_i is built from the two fixed
 // operands of sample row i (h and r; r and t for head-batch) and its gradient is chained back into those operands' rows.
 // What a kernel needs to know about that lives here: where the row's operands are, how a unit of them is laid out, how a
-// unit of q is built and how dq goes back.  The general kernels (score_general.hip), the pooled path's row kernels
-// (score_pool.hip) and the all-entity evaluation (rank.hip) all go through it.
+// unit of q is built and how dq goes back.  The general kernels (score_general.hip, score_relation.hip, score_cand.hip), the
+// pooled path's row kernels (score_pool.hip) and the all-entity evaluation (rank.hip) all go through it.
 //
 // Units: real models have one float per unit (De units per row).  Complex-query models (RotatE, ComplEx) have d complex
 // units per row, re at u and im at d + u; ComplEx's relation row has an imaginary half as well, RotatE's holds d phases.
@@ -37,6 +37,11 @@ __device__ __forceinline__ QueryRow query_row(const Args &A, const int64_t *__re
 __device__ __forceinline__ Cplx ent_unit(const float *e, int d, int u) { return Cplx{e[u], e[d + u]}; }
 template <int MODEL>
 __device__ __forceinline__ Cplx rel_unit(const float *er, int d, int u) { return Cplx{er[u], MODEL == MKB_COMPLEX ? er[d + u] : 0.f}; }
+// ... and for any model: the halves the row has (a real model's unit is its .re); rel_unit<MODEL> already is that
+template <int MODEL>
+__device__ __forceinline__ Cplx ent_unit(const float *e, int d, int u) {
+    return Cplx{e[u], ModelTraits<MODEL>::cplx_query ? e[d + u] : 0.f};
+}
 
 // ---------------------------------------------------------------- one unit of q and of its chain, on loaded operands
 // e = the entity operand (h; t for head-batch), r = the relation operand, whichever side the query is built for
@@ -87,16 +92,20 @@ __device__ __forceinline__ void query_unit_bwd(const QueryRow &R, int u, const f
     }
 }
 
-// ... and the common way to add them: one atomic per element into the operands' gradient rows (duplicate rows add).
-// Issued in operand order, like the loads: a head-batch real model's relation comes first.
+// ... and the common way to add them: one atomic per element into a gradient row (duplicate rows add).  Which halves the row
+// has: an entity row both for the complex-query models, a relation row only ComplEx's.
+template <int MODEL, bool REL_ROW>
+__device__ __forceinline__ void row_grad_atomic(float *g_row, int d, int u, Cplx v) {
+    atomicAdd(g_row + u, v.re);
+    if constexpr (ModelTraits<MODEL>::cplx_query && (!REL_ROW || MODEL == MKB_COMPLEX)) atomicAdd(g_row + d + u, v.im);
+}
+// Both operands' rows, issued in operand order, like the loads: a head-batch real model's relation comes first.
 template <int MODEL, bool HEAD>
 __device__ __forceinline__ void query_grad_atomic(float *g_e, float *g_r, int d, int u, Cplx de, Cplx dr) {
     constexpr bool rel_first = HEAD && !ModelTraits<MODEL>::cplx_query;
-    if constexpr (rel_first) atomicAdd(g_r + u, dr.re);
-    atomicAdd(g_e + u, de.re);
-    if constexpr (ModelTraits<MODEL>::cplx_query) atomicAdd(g_e + d + u, de.im);
-    if constexpr (!rel_first) atomicAdd(g_r + u, dr.re);
-    if constexpr (MODEL == MKB_COMPLEX) atomicAdd(g_r + d + u, dr.im);
+    if constexpr (rel_first) row_grad_atomic<MODEL, true>(g_r, d, u, dr);
+    row_grad_atomic<MODEL, false>(g_e, d, u, de);
+    if constexpr (!rel_first) row_grad_atomic<MODEL, true>(g_r, d, u, dr);
 }
 
 // ---------------------------------------------------------------- Q[i] = query of row i, one workgroup of 256 lanes per row

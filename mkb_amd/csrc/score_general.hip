@@ -11,19 +11,19 @@
 //            reduction), neither writes a gradient per pair:
 //              dq pass   one workgroup per batch row; dq accumulates in registers over the row's K candidates and is chained
 //                        into the fixed operands' rows (one atomic per element and row): score_bwd_kernel<.., DX = false>;
-//              dx pass   the pairs are SORTED BY CANDIDATE (hipCUB radix sort of B*K int32 keys); a workgroup walks 64
-//                        consecutive sorted pairs, keeps the candidate row and its running gradient in registers and adds
-//                        them to the table gradient only when the candidate changes: B*K/64 ... #distinct flushes instead
-//                        of one fp32 atomic per (pair, dim) -- 524 M at the headline shape, which was ~2/3 of the step.
+//              dx pass   the pairs are SORTED BY CANDIDATE (pair_sort.h: a radix sort of B*K int32 keys); a workgroup walks 64
+//                        consecutive sorted pairs (walk_sorted_pairs, score_row.h), keeps the candidate row and its running
+//                        gradient in registers and adds them to the table gradient only when the candidate changes: B*K/64 ...
+//                        #distinct flushes instead of one fp32 atomic per (pair, dim) -- 524 M at the headline shape, which
+//                        was ~2/3 of the step.
 //            The pair term is evaluated in both passes (cheaper than the atomics it replaces).  Positive triples
 //            (no candidates, K = 1) keep the one-pass kernel: the dq pass with its per-pair gradient writes (DX = true).
 //            The dx pass reads the rows' queries from Q [B, De], written by query_side.h's query_build_kernel.
 // The [B,K,D] intermediates of the reference are never materialised.
-#include <hipcub/hipcub.hpp>
-
 #include "common.h"
+#include "pair_sort.h"
 #include "query_side.h"
-#include "score_row.h"  // TablesDev, and the pair sum of one candidate row
+#include "score_row.h"  // TablesDev, the pair sum of one candidate row, one pair's gradient, the walk over sorted pairs
 
 #include <stdlib.h>
 
@@ -82,28 +82,10 @@ __global__ __launch_bounds__(kBlock) void score_bwd_kernel(TablesDev T, mkb_grad
         for (int j = 0; j < K; ++j) {
             const float g = dscore[(int64_t)i * K + j];
             const int64_t c = (DX && !cand) ? R.t : cand[(int64_t)i * K + j];
-            const float *x = T.ent + c * T.De;
-            auto add_x = [&](int k, float v) {  // the per-pair gradient write, where the parent pass has one
-                if constexpr (DX) atomicAdd(G.g_ent + c * T.De + k, v);
-            };
-            if constexpr (ModelTraits<MODEL>::cplx_pair) {
-                Cplx dq, dx;
-                pair_bwd_cmod(Cplx{q0, q1}, Cplx{x[u], x[T.d + u]}, g, dq, dx);
-                dq0 += dq.re; dq1 += dq.im;
-                add_x(u, dx.re);
-                add_x(T.d + u, dx.im);
-            } else if constexpr (ModelTraits<MODEL>::cplx_query) {  // ComplEx: dot over both halves
-                float a, b, e0 = 0.f;
-                pair_bwd_real<MODEL, HEAD>(q0, x[u], g, T.kd, modulus, a, b, e0);
-                dq0 += a; add_x(u, b);
-                pair_bwd_real<MODEL, HEAD>(q1, x[T.d + u], g, T.kd, modulus, a, b, e0);
-                dq1 += a; add_x(T.d + u, b);
-            } else {
-                float a, b, e0 = 0.f;
-                pair_bwd_real<MODEL, HEAD>(q0, x[u], g, T.kd, modulus, a, b, e0);
-                dq0 += a; add_x(u, b);
-                extra += g * e0;
-            }
+            Cplx dq, dx;
+            pair_unit_bwd<MODEL, HEAD>(Cplx{q0, q1}, ent_unit<MODEL>(T.ent + c * T.De, T.d, u), g, T.kd, modulus, dq, dx, extra);
+            dq0 += dq.re; dq1 += dq.im;
+            if constexpr (DX) row_grad_atomic<MODEL, false>(G.g_ent + c * T.De, T.d, u, dx);  // the per-pair gradient write
         }
         Cplx de, dr;
         query_unit_bwd<MODEL, HEAD>(R, u, dq0, dq1, de, dr);
@@ -116,7 +98,6 @@ __global__ __launch_bounds__(kBlock) void score_bwd_kernel(TablesDev T, mkb_grad
 }
 
 // dx pass of the two-pass backward: workgroup = kChunkPairs consecutive pairs of the candidate-sorted pair list
-constexpr int kChunkPairs = 64;
 template <int MODEL, bool HEAD>
 __global__ __launch_bounds__(kBlock) void score_bwd_x_kernel(TablesDev T, mkb_grads_t G, const int *__restrict__ sorted_cand,
                                                              const int *__restrict__ sorted_pair, int n_pairs, int K,
@@ -125,127 +106,73 @@ __global__ __launch_bounds__(kBlock) void score_bwd_x_kernel(TablesDev T, mkb_gr
     const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
     const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
     for (int u = threadIdx.x; u < U; u += kBlock) {
-        int cur = -1;
-        float x0 = 0.f, x1 = 0.f, dx0 = 0.f, dx1 = 0.f;
-        auto flush = [&]() {
-            if (cur < 0) return;
-            float *gx = G.g_ent + (int64_t)cur * T.De;
-            atomicAdd(gx + u, dx0);
-            if constexpr (ModelTraits<MODEL>::cplx_query) atomicAdd(gx + T.d + u, dx1);
-        };
-        for (int p = lo; p < hi; ++p) {
-            const int c = sorted_cand[p];  // (uniform across the workgroup)
-            if (c != cur) {
-                flush();
-                cur = c;
-                const float *x = T.ent + (int64_t)c * T.De;
-                x0 = x[u];
-                x1 = ModelTraits<MODEL>::cplx_query ? x[T.d + u] : 0.f;
-                dx0 = dx1 = 0.f;
-            }
-            const int pair = sorted_pair[p];
-            const float g = dscore[pair];
-            const float *q = Q + (int64_t)(pair / K) * T.De;
-            if constexpr (ModelTraits<MODEL>::cplx_pair) {
-                Cplx dq, dx;
-                pair_bwd_cmod(Cplx{q[u], q[T.d + u]}, Cplx{x0, x1}, g, dq, dx);
-                dx0 += dx.re; dx1 += dx.im;
-            } else if constexpr (ModelTraits<MODEL>::cplx_query) {
-                float a, b, e0 = 0.f;
-                pair_bwd_real<MODEL, HEAD>(q[u], x0, g, T.kd, modulus, a, b, e0);
-                dx0 += b;
-                pair_bwd_real<MODEL, HEAD>(q[T.d + u], x1, g, T.kd, modulus, a, b, e0);
-                dx1 += b;
-            } else {
-                float a, b, e0 = 0.f;
-                pair_bwd_real<MODEL, HEAD>(q[u], x0, g, T.kd, modulus, a, b, e0);
-                dx0 += b;
-            }
-        }
-        flush();
+        Cplx x{0.f, 0.f}, dx{0.f, 0.f};
+        float unused = 0.f;
+        walk_sorted_pairs(
+            sorted_cand, sorted_pair, lo, hi,
+            [&](int c) {
+                x = ent_unit<MODEL>(T.ent + (int64_t)c * T.De, T.d, u);
+                dx = Cplx{0.f, 0.f};
+            },
+            [&](int pair) {
+                const float g = dscore[pair];
+                Cplx dq, d;
+                pair_unit_bwd<MODEL, HEAD>(ent_unit<MODEL>(Q + (int64_t)(pair / K) * T.De, T.d, u), x, g, T.kd, modulus, dq, d, unused);
+                dx.re += d.re; dx.im += d.im;
+            },
+            [&](int c) { row_grad_atomic<MODEL, false>(G.g_ent + (int64_t)c * T.De, T.d, u, dx); });
     }
 }
 
-__global__ __launch_bounds__(256) void pair_keys_kernel(const int64_t *__restrict__ cand, int n, int *__restrict__ keys, int *__restrict__ vals) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { keys[i] = (int)cand[i]; vals[i] = i; }
-}
-
-// Scratch of the two-pass backward: queries, the pair list twice (radix sort ping-pong) and the sort's own storage.
+// Scratch of the two-pass backward: the queries, then the pair sort's
 struct Bwd2Scratch {
-    size_t q_bytes, l_bytes, sort_bytes, total;
-    int bits;
+    size_t q_bytes, total;
+    PairSortPlan sort;
 };
 static int bwd2_scratch(const mkb_tables_t *tb, int64_t B, int64_t K, Bwd2Scratch &S) {
-    const int64_t n = B * K;
-    S.bits = 1;
-    while (S.bits < 31 && ((int64_t)1 << S.bits) < tb->n_entity) ++S.bits;
-    S.sort_bytes = 0;
-    MKB_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, S.sort_bytes, (const int *)nullptr, (int *)nullptr, (const int *)nullptr,
-                                                     (int *)nullptr, (int)n, 0, S.bits, (hipStream_t)0));
+    if (int rc = pair_sort_plan(tb->n_entity, B * K, S.sort)) return rc;
     S.q_bytes = ((size_t)B * tb->entity_dim * 4 + 255) & ~(size_t)255;
-    S.l_bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-    S.total = S.q_bytes + 4 * S.l_bytes + ((S.sort_bytes + 255) & ~(size_t)255);
+    S.total = S.q_bytes + S.sort.total;
     return MKB_OK;
 }
 static bool bwd2_applies(const mkb_tables_t *tb, const int64_t *cand, int64_t B, int64_t K) {
     return cand && K > 1 && B * K <= INT32_MAX && tb->n_entity <= INT32_MAX;
 }
 
-template <int MODEL>
+template <int MODEL, bool HEAD>
 static int launch_bwd2(const TablesDev &T, const mkb_tables_t *tb, const mkb_grads_t &G, const int64_t *sample, const int64_t *cand,
-                       int64_t B, int K, bool head, const float *dscore, void *ws, hipStream_t st) {
+                       int64_t B, int K, const float *dscore, void *ws, hipStream_t st) {
     const int64_t n = B * K;
     Bwd2Scratch S;
     if (int rc = bwd2_scratch(tb, B, K, S)) return rc;
-    unsigned char *buf = (unsigned char *)ws;  // caller-owned (mkb_score_bwd_workspace_bytes): nothing is allocated here
-    const size_t q_bytes = S.q_bytes, l_bytes = S.l_bytes;
-    size_t sort_bytes = S.sort_bytes;
-    const int bits = S.bits;
-    float *Q = (float *)buf;
-    int *k_in = (int *)(buf + q_bytes), *v_in = (int *)(buf + q_bytes + l_bytes), *k_out = (int *)(buf + q_bytes + 2 * l_bytes),
-        *v_out = (int *)(buf + q_bytes + 3 * l_bytes);
-    void *tmp = buf + q_bytes + 4 * l_bytes;
+    float *Q = (float *)ws;  // caller-owned (mkb_score_bwd_workspace_bytes): nothing is allocated here
+    const int *sorted_cand, *sorted_pair;
     ProfScope ps(MKB_PROF_GENERAL_BWD, st);
-    hipLaunchKernelGGL(pair_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand, (int)n, k_in, v_in);
-    MKB_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, k_in, k_out, v_in, v_out, (int)n, 0, bits, st));
+    if (int rc = pair_sort_launch(cand, n, tb->n_entity, (unsigned char *)ws + S.q_bytes, S.sort, st, &sorted_cand, &sorted_pair)) return rc;
     const unsigned chunks = (unsigned)((n + kChunkPairs - 1) / kChunkPairs);
     static_assert(kBlock == 256, "query_build_kernel strides its row by 256 lanes");
     const RowArgs qa = query_build_args(T.ent, T.rel, sample, Q, T.De, T.Dr, T.d, B, T.kd);
-    if (head) {
-        hipLaunchKernelGGL((query_build_kernel<MODEL, true>), dim3((unsigned)B), dim3(kBlock), 0, st, qa);
-        hipLaunchKernelGGL((score_bwd_kernel<MODEL, true, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
-        hipLaunchKernelGGL((score_bwd_x_kernel<MODEL, true>), dim3(chunks), dim3(kBlock), 0, st, T, G, k_out, v_out, (int)n, K, Q, dscore);
-    } else {
-        hipLaunchKernelGGL((query_build_kernel<MODEL, false>), dim3((unsigned)B), dim3(kBlock), 0, st, qa);
-        hipLaunchKernelGGL((score_bwd_kernel<MODEL, false, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
-        hipLaunchKernelGGL((score_bwd_x_kernel<MODEL, false>), dim3(chunks), dim3(kBlock), 0, st, T, G, k_out, v_out, (int)n, K, Q, dscore);
-    }
+    hipLaunchKernelGGL((query_build_kernel<MODEL, HEAD>), dim3((unsigned)B), dim3(kBlock), 0, st, qa);
+    hipLaunchKernelGGL((score_bwd_kernel<MODEL, HEAD, false>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
+    hipLaunchKernelGGL((score_bwd_x_kernel<MODEL, HEAD>), dim3(chunks), dim3(kBlock), 0, st, T, G, sorted_cand, sorted_pair, (int)n, K, Q, dscore);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
 
-template <int MODEL>
-static int launch_fwd(const TablesDev &T, const int64_t *sample, const int64_t *cand, int64_t B, int K, bool head,
-                      float *score, hipStream_t st) {
+template <int MODEL, bool HEAD>
+static int launch_fwd(const TablesDev &T, const int64_t *sample, const int64_t *cand, int64_t B, int K, float *score, hipStream_t st) {
     const size_t lds = (size_t)T.De * sizeof(float);
     ProfScope ps(MKB_PROF_GENERAL_FWD, st);
-    if (head)
-        hipLaunchKernelGGL((score_fwd_kernel<MODEL, true>), dim3((unsigned)B), dim3(kBlock), lds, st, T, sample, cand, K, score);
-    else
-        hipLaunchKernelGGL((score_fwd_kernel<MODEL, false>), dim3((unsigned)B), dim3(kBlock), lds, st, T, sample, cand, K, score);
+    hipLaunchKernelGGL((score_fwd_kernel<MODEL, HEAD>), dim3((unsigned)B), dim3(kBlock), lds, st, T, sample, cand, K, score);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
 
-template <int MODEL>
-static int launch_bwd(const TablesDev &T, const mkb_grads_t &G, const int64_t *sample, const int64_t *cand, int64_t B,
-                      int K, bool head, const float *dscore, hipStream_t st) {
+template <int MODEL, bool HEAD>
+static int launch_bwd(const TablesDev &T, const mkb_grads_t &G, const int64_t *sample, const int64_t *cand, int64_t B, int K,
+                      const float *dscore, hipStream_t st) {
     ProfScope ps(MKB_PROF_GENERAL_BWD, st);
-    if (head)
-        hipLaunchKernelGGL((score_bwd_kernel<MODEL, true, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
-    else
-        hipLaunchKernelGGL((score_bwd_kernel<MODEL, false, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
+    hipLaunchKernelGGL((score_bwd_kernel<MODEL, HEAD, true>), dim3((unsigned)B), dim3(kBlock), 0, st, T, G, sample, cand, K, dscore);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
@@ -272,15 +199,9 @@ extern "C" int mkb_score_fwd(const mkb_tables_t *tb, const int64_t *sample, cons
     if (B == 0) return MKB_OK;
     const TablesDev T = to_dev(tb);
     hipStream_t st = (hipStream_t)stream;
-    const bool head = mode_is_head(mode);
-    switch (tb->model) {
-        case MKB_TRANSE: return launch_fwd<MKB_TRANSE>(T, sample, cand, B, (int)K, head, score, st);
-        case MKB_ROTATE: return launch_fwd<MKB_ROTATE>(T, sample, cand, B, (int)K, head, score, st);
-        case MKB_COMPLEX: return launch_fwd<MKB_COMPLEX>(T, sample, cand, B, (int)K, head, score, st);
-        case MKB_DISTMULT: return launch_fwd<MKB_DISTMULT>(T, sample, cand, B, (int)K, head, score, st);
-        case MKB_PROTATE: return launch_fwd<MKB_PROTATE>(T, sample, cand, B, (int)K, head, score, st);
-    }
-    return set_error(MKB_ERR_INVALID, "unknown model");
+    return dispatch_model_side(tb->model, mode_is_head(mode), [&](auto m, auto h) {
+        return launch_fwd<m(), h()>(T, sample, cand, B, (int)K, score, st);
+    });
 }
 
 extern "C" int64_t mkb_score_bwd_workspace_bytes(const mkb_tables_t *tb, int64_t B, int64_t K, int mode) {
@@ -298,24 +219,11 @@ extern "C" int mkb_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, cons
     if (B == 0) return MKB_OK;
     const TablesDev T = to_dev(tb);
     hipStream_t st = (hipStream_t)stream;
-    const bool head = mode_is_head(mode);
-    if (bwd2_applies(tb, cand, B, K)) {
-        MKB_REQUIRE(ws != nullptr && (((uintptr_t)ws) & 255) == 0,
-                    "mkb_score_bwd needs a 256-byte aligned workspace of mkb_score_bwd_workspace_bytes() bytes");
-        switch (tb->model) {
-            case MKB_TRANSE: return launch_bwd2<MKB_TRANSE>(T, tb, *gr, sample, cand, B, (int)K, head, dscore, ws, st);
-            case MKB_ROTATE: return launch_bwd2<MKB_ROTATE>(T, tb, *gr, sample, cand, B, (int)K, head, dscore, ws, st);
-            case MKB_COMPLEX: return launch_bwd2<MKB_COMPLEX>(T, tb, *gr, sample, cand, B, (int)K, head, dscore, ws, st);
-            case MKB_DISTMULT: return launch_bwd2<MKB_DISTMULT>(T, tb, *gr, sample, cand, B, (int)K, head, dscore, ws, st);
-            case MKB_PROTATE: return launch_bwd2<MKB_PROTATE>(T, tb, *gr, sample, cand, B, (int)K, head, dscore, ws, st);
-        }
-    }
-    switch (tb->model) {
-        case MKB_TRANSE: return launch_bwd<MKB_TRANSE>(T, *gr, sample, cand, B, (int)K, head, dscore, st);
-        case MKB_ROTATE: return launch_bwd<MKB_ROTATE>(T, *gr, sample, cand, B, (int)K, head, dscore, st);
-        case MKB_COMPLEX: return launch_bwd<MKB_COMPLEX>(T, *gr, sample, cand, B, (int)K, head, dscore, st);
-        case MKB_DISTMULT: return launch_bwd<MKB_DISTMULT>(T, *gr, sample, cand, B, (int)K, head, dscore, st);
-        case MKB_PROTATE: return launch_bwd<MKB_PROTATE>(T, *gr, sample, cand, B, (int)K, head, dscore, st);
-    }
-    return set_error(MKB_ERR_INVALID, "unknown model");
+    const bool two_pass = bwd2_applies(tb, cand, B, K);
+    MKB_REQUIRE(!two_pass || (ws != nullptr && (((uintptr_t)ws) & 255) == 0),
+                "mkb_score_bwd needs a 256-byte aligned workspace of mkb_score_bwd_workspace_bytes() bytes");
+    return dispatch_model_side(tb->model, mode_is_head(mode), [&](auto m, auto h) {
+        return two_pass ? launch_bwd2<m(), h()>(T, tb, *gr, sample, cand, B, (int)K, dscore, ws, st)
+                        : launch_bwd<m(), h()>(T, *gr, sample, cand, B, (int)K, dscore, st);
+    });
 }

@@ -20,32 +20,31 @@
 //           thousand; no atomics, nothing to sort.
 // Nothing is allocated in a call and nothing is accumulated with atomics: two runs give the same bits.
 //
-// Candidate lists in any one slot, with a backward: mkb_cand_score_fwd / mkb_cand_score_bwd (what Distillation.distill scores).
-// Forward : the score kernel above with a list per row; with the heads varying, r and t are the staged rows and the turn's four
-//           head rows come from the entity table (default-mode arithmetic, query_of<MODEL, false>(h', r): not the head-batch
-//           kernels, whose order of operations gives other bits).  The tail part is the general forward / two-pass backward.
-// Backward: head and relation part, two passes, neither writes a gradient per pair.  Row pass: the gradients of the two fixed rows
-//           accumulate in registers over the row's candidates (one atomic per element and row).  Candidate pass: the B*M pairs
-//           radix-sorted by candidate, 64 consecutive pairs per workgroup, one atomic per element and run of equal candidates.
-#include <hipcub/hipcub.hpp>
-
+// The score kernel is the slot forward: with a list per row it scores candidate relations or -- the heads varying, r and t the
+// staged rows, the turn's four head rows from the entity table (default-mode arithmetic, query_of<MODEL, false>(h', r): not the
+// head-batch kernels, whose order of operations gives other bits) -- candidate heads.  launch_slot_scores (score_slot.h) is how
+// score_cand.hip reaches it; nothing here depends on the candidate-list entry points or on the general kernels.
 #include "common.h"
 #include "query_side.h"
 #include "rank_order.h"
 #include "score_row.h"
+#include "score_slot.h"
 
 #include <algorithm>
 
 namespace mkb {
 
-constexpr int kRelBlock = 256, kRelWaves = kRelBlock / 64;
 constexpr size_t kRelLdsMax = 64 * 1024;
 
 // LDS of the score kernel: the h row, the t row and one query row per wave
-static size_t rel_lds_bytes(const mkb_tables_t *tb) { return (size_t)(2 + kRelWaves) * (size_t)tb->entity_dim * sizeof(float); }
+static size_t rel_lds_bytes(const mkb_tables_t *tb) { return (size_t)(2 + kSlotWaves) * (size_t)tb->entity_dim * sizeof(float); }
 
-// An id as a row of its table: one outside it reads as the nearest row (the glue flags it, mkb_check_ids), nothing out of bounds.
-__device__ __forceinline__ int64_t table_row(int64_t id, int64_t n) { return id < 0 ? 0 : (id < n ? id : n - 1); }
+int slot_rows_check(const mkb_tables_t *tb) {
+    if (rel_lds_bytes(tb) > kRelLdsMax)
+        return set_error(MKB_ERR_UNSUPPORTED, "entity rows of more than %d floats are not supported by the slot kernels",
+                         (int)(kRelLdsMax / sizeof(float) / (2 + kSlotWaves)));
+    return MKB_OK;
+}
 
 // query_of<MKB_COMPLEX, false>(e, r) with the contraction spelled out that the general forward's compilation of it has: the
 // products with r.re fused, the other two rounded.  Left to the compiler, a loop in which r is the invariant operand (the heads
@@ -59,7 +58,7 @@ __device__ __forceinline__ Cplx complex_query_of(Cplx e, Cplx r) {
 //   cand: row i's list is cand + i * cand_stride (stride 0: one list for the whole batch, mkb_rel_scores); null = the ids 0 ..
 //   n_cand - 1.  n_table = the rows of the table the candidates index.
 template <int MODEL, bool VARY_HEAD>
-__global__ __launch_bounds__(kRelBlock) void slot_score_kernel(TablesDev T, const int64_t *__restrict__ sample,
+__global__ __launch_bounds__(kSlotBlock) void slot_score_kernel(TablesDev T, const int64_t *__restrict__ sample,
                                                                const int64_t *__restrict__ cand, int64_t cand_stride, int n_cand,
                                                                int64_t n_table, float *__restrict__ scores, int64_t ld) {
     extern __shared__ __attribute__((aligned(16))) float rel_lds[];
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(kRelBlock) void slot_score_kernel(TablesDev T, cons
         const float *ea = VARY_HEAD ? T.rel + sample[3 * i + 1] * T.Dr : T.ent + sample[3 * i] * T.De;
         const float *et = T.ent + sample[3 * i + 2] * T.De;
         const int na = VARY_HEAD ? (int)T.Dr : (int)T.De;
-        for (int k = threadIdx.x; k < (int)T.De; k += kRelBlock) {
+        for (int k = threadIdx.x; k < (int)T.De; k += kSlotBlock) {
             if (!VARY_HEAD || k < na) s_a[k] = ea[k];
             s_t[k] = et[k];
         }
@@ -82,27 +81,27 @@ __global__ __launch_bounds__(kRelBlock) void slot_score_kernel(TablesDev T, cons
     const int64_t *list = cand ? cand + i * cand_stride : nullptr;
     const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
     const bool vec4 = T.vec4 != 0;
-    for (int j0 = 0; j0 < n_cand; j0 += kRelWaves) {  // a turn: kRelWaves candidates, one per wave
+    for (int j0 = 0; j0 < n_cand; j0 += kSlotWaves) {  // a turn: kSlotWaves candidates, one per wave
         const int j = j0 + wave;
         // The turn's queries are built by the whole workgroup: a lane owns units, loads its unit of the fixed operand once and the
         // turn's candidate units together (independent loads in flight: one wave building its own candidate's query alone waited for
         // one row load per 64 units), then builds each with the arithmetic of query_unit.  (Past the last candidate: the last one
         // again, not used.)
-        const float *ec[kRelWaves];
+        const float *ec[kSlotWaves];
 #pragma unroll
-        for (int w = 0; w < kRelWaves; ++w) {
+        for (int w = 0; w < kSlotWaves; ++w) {
             const int jw = min(j0 + w, n_cand - 1);
             const int64_t id = table_row(list ? list[jw] : (int64_t)jw, n_table);
             ec[w] = VARY_HEAD ? T.ent + id * T.De : T.rel + id * T.Dr;
         }
-        for (int u = threadIdx.x; u < U; u += kRelBlock) {
+        for (int u = threadIdx.x; u < U; u += kSlotBlock) {
             if constexpr (ModelTraits<MODEL>::cplx_query) {
                 const Cplx a = VARY_HEAD ? rel_unit<MODEL>(s_a, T.d, u) : ent_unit(s_a, T.d, u);
-                Cplx c[kRelWaves];
+                Cplx c[kSlotWaves];
 #pragma unroll
-                for (int w = 0; w < kRelWaves; ++w) c[w] = VARY_HEAD ? ent_unit(ec[w], T.d, u) : rel_unit<MODEL>(ec[w], T.d, u);
+                for (int w = 0; w < kSlotWaves; ++w) c[w] = VARY_HEAD ? ent_unit(ec[w], T.d, u) : rel_unit<MODEL>(ec[w], T.d, u);
 #pragma unroll
-                for (int w = 0; w < kRelWaves; ++w) {
+                for (int w = 0; w < kSlotWaves; ++w) {
                     Cplx q;
                     if constexpr (VARY_HEAD && MODEL == MKB_COMPLEX) q = complex_query_of(c[w], a);
                     else q = VARY_HEAD ? query_of<MODEL, false>(c[w], a, T.kd) : query_of<MODEL, false>(a, c[w], T.kd);
@@ -111,11 +110,11 @@ __global__ __launch_bounds__(kRelBlock) void slot_score_kernel(TablesDev T, cons
                 }
             } else {
                 const float a = s_a[u];
-                float c[kRelWaves];
+                float c[kSlotWaves];
 #pragma unroll
-                for (int w = 0; w < kRelWaves; ++w) c[w] = ec[w][u];
+                for (int w = 0; w < kSlotWaves; ++w) c[w] = ec[w][u];
 #pragma unroll
-                for (int w = 0; w < kRelWaves; ++w)
+                for (int w = 0; w < kSlotWaves; ++w)
                     rel_lds[(2 + w) * T.De + u] = VARY_HEAD ? query_of<MODEL, false>(c[w], a, T.kd) : query_of<MODEL, false>(a, c[w], T.kd);
             }
         }
@@ -127,142 +126,6 @@ __global__ __launch_bounds__(kRelBlock) void slot_score_kernel(TablesDev T, cons
         }
         __syncthreads();
     }
-}
-
-// ---------------------------------------------------------------- backward of the head and relation parts
-// One unit of one pair: q = query(e, r) against x with the seed g -> the contributions to e, r and x.  Real models use the .re
-// halves.  extra: pRotatE's g * |sin z| (the modulus gradient), where the caller wants it.
-template <int MODEL>
-__device__ __forceinline__ Cplx slot_ent_unit(const float *row, int d, int u) {
-    if constexpr (ModelTraits<MODEL>::cplx_query) return ent_unit(row, d, u);
-    else return Cplx{row[u], 0.f};
-}
-template <int MODEL>
-__device__ __forceinline__ Cplx slot_rel_unit(const float *row, int d, int u) {
-    if constexpr (ModelTraits<MODEL>::cplx_query) return rel_unit<MODEL>(row, d, u);
-    else return Cplx{row[u], 0.f};
-}
-template <int MODEL>
-__device__ __forceinline__ void slot_pair_bwd(Cplx e, Cplx r, Cplx x, float g, float kd, float modulus, Cplx &de, Cplx &dr, Cplx &dx,
-                                              float &extra) {
-    if constexpr (ModelTraits<MODEL>::cplx_query) {
-        const Cplx q = query_of<MODEL, false>(e, r, kd);
-        Cplx dq;
-        if constexpr (ModelTraits<MODEL>::cplx_pair) {
-            pair_bwd_cmod(q, x, g, dq, dx);
-        } else {  // ComplEx: a dot product over both halves
-            float e0 = 0.f;
-            pair_bwd_real<MODEL, false>(q.re, x.re, g, kd, modulus, dq.re, dx.re, e0);
-            pair_bwd_real<MODEL, false>(q.im, x.im, g, kd, modulus, dq.im, dx.im, e0);
-        }
-        query_chain<MODEL, false>(e, r, dq, kd, de, dr);
-    } else {
-        const float q = query_of<MODEL, false>(e.re, r.re, kd);
-        float dq, e0 = 0.f;
-        pair_bwd_real<MODEL, false>(q, x.re, g, kd, modulus, dq, dx.re, e0);
-        extra += g * e0;
-        query_chain<MODEL, false>(e.re, r.re, dq, kd, de.re, dr.re);
-        de.im = dr.im = dx.im = 0.f;
-    }
-}
-// which halves of a gradient row a model has: entity rows both for the complex-query models, relation rows only ComplEx's
-template <int MODEL, bool REL_ROW>
-__device__ __forceinline__ void slot_row_atomic(float *g_row, int d, int u, Cplx v) {
-    atomicAdd(g_row + u, v.re);
-    if constexpr (ModelTraits<MODEL>::cplx_query && (!REL_ROW || MODEL == MKB_COMPLEX)) atomicAdd(g_row + d + u, v.im);
-}
-
-// Row pass: one workgroup per row, lanes own units.  The units of the two fixed operands stay in registers, their gradients
-// accumulate over the row's M candidates and leave as one atomic per element and row; nothing is written per pair.
-template <int MODEL, bool VARY_HEAD>
-__global__ __launch_bounds__(kRelBlock) void slot_bwd_row_kernel(TablesDev T, mkb_grads_t G, const int64_t *__restrict__ sample,
-                                                                 const int64_t *__restrict__ cand, int M, int64_t n_table,
-                                                                 const float *__restrict__ dscore) {
-    __shared__ float red[kRelWaves];
-    const int64_t i = blockIdx.x;
-    const int64_t h = sample[3 * i], r = sample[3 * i + 1], t = sample[3 * i + 2];
-    const float *ea = VARY_HEAD ? T.rel + r * T.Dr : T.ent + h * T.De, *et = T.ent + t * T.De;
-    float *g_a = VARY_HEAD ? G.g_rel + r * T.Dr : G.g_ent + h * T.De, *g_t = G.g_ent + t * T.De;
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
-    const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
-    const int64_t *list = cand + i * M;
-    const float *seed = dscore + i * M;
-    float extra = 0.f;
-    for (int u = threadIdx.x; u < U; u += kRelBlock) {
-        const Cplx a = VARY_HEAD ? slot_rel_unit<MODEL>(ea, T.d, u) : slot_ent_unit<MODEL>(ea, T.d, u);
-        const Cplx x = slot_ent_unit<MODEL>(et, T.d, u);
-        Cplx da{0.f, 0.f}, dt{0.f, 0.f};
-        for (int j = 0; j < M; ++j) {
-            const int64_t id = table_row(list[j], n_table);  // (uniform across the workgroup)
-            Cplx de, dr, dx;
-            if constexpr (VARY_HEAD) {
-                slot_pair_bwd<MODEL>(slot_ent_unit<MODEL>(T.ent + id * T.De, T.d, u), a, x, seed[j], T.kd, modulus, de, dr, dx, extra);
-                da.re += dr.re; da.im += dr.im;
-            } else {
-                slot_pair_bwd<MODEL>(a, slot_rel_unit<MODEL>(T.rel + id * T.Dr, T.d, u), x, seed[j], T.kd, modulus, de, dr, dx, extra);
-                da.re += de.re; da.im += de.im;
-            }
-            dt.re += dx.re; dt.im += dx.im;
-        }
-        slot_row_atomic<MODEL, VARY_HEAD>(g_a, T.d, u, da);
-        slot_row_atomic<MODEL, false>(g_t, T.d, u, dt);
-    }
-    if constexpr (MODEL == MKB_PROTATE) {  // d score / d modulus = - sum_k |sin z|: once per pair, so in this pass only
-        extra = block_sum_4waves(extra, red);
-        if (threadIdx.x == 0) atomicAdd(G.g_modulus, -extra);
-    }
-}
-
-// Candidate pass: workgroup (x, y) = kSlotChunk consecutive pairs of the candidate-sorted pair list, units 256 y .. 256 y + 255.
-// A lane keeps its unit of the candidate's row and the running gradient in registers and adds to the candidate's gradient row
-// only when the candidate changes; the pair term is evaluated again from the pair's fixed rows.
-constexpr int kSlotChunk = 64;
-template <int MODEL, bool VARY_HEAD>
-__global__ __launch_bounds__(kRelBlock) void slot_bwd_cand_kernel(TablesDev T, mkb_grads_t G, const int *__restrict__ sorted_cand,
-                                                                  const int *__restrict__ sorted_pair, int n_pairs, int M,
-                                                                  const int64_t *__restrict__ sample,
-                                                                  const float *__restrict__ dscore) {
-    const int lo = blockIdx.x * kSlotChunk, hi = min(n_pairs, lo + kSlotChunk);
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
-    const int u = blockIdx.y * kRelBlock + threadIdx.x;
-    if (u >= U) return;
-    const float modulus = (MODEL == MKB_PROTATE) ? T.modulus[0] : 0.f;
-    int cur = -1;
-    Cplx c{0.f, 0.f}, dc{0.f, 0.f};
-    float unused = 0.f;
-    auto flush = [&]() {
-        if (cur < 0) return;
-        if constexpr (VARY_HEAD) slot_row_atomic<MODEL, false>(G.g_ent + (int64_t)cur * T.De, T.d, u, dc);
-        else slot_row_atomic<MODEL, true>(G.g_rel + (int64_t)cur * T.Dr, T.d, u, dc);
-    };
-    for (int p = lo; p < hi; ++p) {
-        const int id = sorted_cand[p];  // (uniform across the workgroup; a row of the table: slot_keys_kernel)
-        if (id != cur) {
-            flush();
-            cur = id;
-            c = VARY_HEAD ? slot_ent_unit<MODEL>(T.ent + (int64_t)id * T.De, T.d, u) : slot_rel_unit<MODEL>(T.rel + (int64_t)id * T.Dr, T.d, u);
-            dc = Cplx{0.f, 0.f};
-        }
-        const int pair = sorted_pair[p];
-        const int64_t i = pair / M;
-        const Cplx x = slot_ent_unit<MODEL>(T.ent + sample[3 * i + 2] * T.De, T.d, u);
-        Cplx de, dr, dx;
-        if constexpr (VARY_HEAD) {
-            slot_pair_bwd<MODEL>(c, slot_rel_unit<MODEL>(T.rel + sample[3 * i + 1] * T.Dr, T.d, u), x, dscore[pair], T.kd, modulus, de, dr, dx, unused);
-            dc.re += de.re; dc.im += de.im;
-        } else {
-            slot_pair_bwd<MODEL>(slot_ent_unit<MODEL>(T.ent + sample[3 * i] * T.De, T.d, u), c, x, dscore[pair], T.kd, modulus, de, dr, dx, unused);
-            dc.re += dr.re; dc.im += dr.im;
-        }
-    }
-    flush();
-}
-
-// the pair list to sort: key = the candidate as a row of its table, value = the pair's index in [B, M]
-__global__ __launch_bounds__(256) void slot_keys_kernel(const int64_t *__restrict__ cand, int n, int64_t n_table, int *__restrict__ keys,
-                                                        int *__restrict__ vals) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { keys[i] = (int)table_row(cand[i], n_table); vals[i] = i; }
 }
 
 // mask[i * W + w] bit b = (h_i, 32 w + b, t_i) is a key.  One wave per (query, 64 relations); every word of the mask is written.
@@ -346,12 +209,11 @@ __global__ __launch_bounds__(256) void rel_topk_kernel(const float *__restrict__
     }
 }
 
-// the scores of n_cand candidates per row in the relation slot (vary_head: the head slot); cand / cand_stride as the kernel takes them
-static int launch_slot_scores(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *cand, int64_t cand_stride,
-                              int64_t n_cand, bool vary_head, float *scores, int64_t ld, hipStream_t st) {
+int launch_slot_scores(const mkb_tables_t *tb, const int64_t *sample, int64_t B, const int64_t *cand, int64_t cand_stride, int64_t n_cand,
+                       bool vary_head, float *scores, int64_t ld, hipStream_t st) {
     const TablesDev T = to_dev(tb);
     const size_t lds = rel_lds_bytes(tb);
-    const dim3 grid((unsigned)B), block(kRelBlock);
+    const dim3 grid((unsigned)B), block(kSlotBlock);
     const int64_t n_table = vary_head ? tb->n_entity : tb->n_relation;
     return dispatch_model_side(tb->model, vary_head, [&](auto m, auto vh) {
         hipLaunchKernelGGL((slot_score_kernel<m(), vh()>), grid, block, lds, st, T, sample, cand, cand_stride, (int)n_cand, n_table, scores, ld);
@@ -376,10 +238,7 @@ static int check_rel_call(const mkb_tables_t *tb, const int64_t *sample, int64_t
     MKB_REQUIRE(n_true >= 0 && (true_keys != nullptr || n_true == 0), "n_true > 0 needs true_keys");
     MKB_REQUIRE(tb->n_relation <= INT32_MAX, "more than 2^31 - 1 relations");
     MKB_REQUIRE(B == 0 || (ws != nullptr && (((uintptr_t)ws) & 255) == 0 && ws_bytes >= need), "workspace null, too small or unaligned");
-    if (rel_lds_bytes(tb) > kRelLdsMax)
-        return set_error(MKB_ERR_UNSUPPORTED, "entity rows of more than %d floats are not supported on the relation side",
-                         (int)(kRelLdsMax / sizeof(float) / (2 + kRelWaves)));
-    return MKB_OK;
+    return slot_rows_check(tb);
 }
 
 // block (null: the workspace's) = the [B, n_relation] scores, then the filter mask behind the workspace's block
@@ -403,9 +262,7 @@ extern "C" int mkb_rel_scores(const mkb_tables_t *tb, const int64_t *sample, int
     MKB_REQUIRE(n_rel >= 1 && n_rel <= INT32_MAX, "n_rel must lie in [1, 2^31 - 1]");
     MKB_REQUIRE(rel_ids != nullptr || n_rel == tb->n_relation, "null rel_ids means every relation: n_rel must equal n_relation");
     MKB_REQUIRE(ld >= n_rel, "ld must be >= n_rel");
-    if (rel_lds_bytes(tb) > kRelLdsMax)
-        return set_error(MKB_ERR_UNSUPPORTED, "entity rows of more than %d floats are not supported on the relation side",
-                         (int)(kRelLdsMax / sizeof(float) / (2 + kRelWaves)));
+    if (int rc = slot_rows_check(tb)) return rc;
     if (B == 0) return MKB_OK;
     if (int rc = launch_scores(tb, sample, B, rel_ids, n_rel, scores, ld, (hipStream_t)stream)) return rc;
     MKB_LAUNCH_CHECK();
@@ -454,97 +311,4 @@ extern "C" int mkb_rel_topk(const mkb_tables_t *tb, const int64_t *sample, int64
                        mask_words(tb), sample, B, tb->n_relation, k, (flags & MKB_TOPK_KEEP_TARGET) ? 1 : 0, ids, scores);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
-}
-
-// ---------------------------------------------------------------- candidate lists in any one slot
-namespace mkb {
-
-// Scratch of the candidate pass: the pair list twice (radix sort ping-pong) and the sort's own storage.
-struct SlotScratch {
-    size_t l_bytes, sort_bytes, total;
-    int bits;
-};
-static int slot_scratch(int64_t n_table, int64_t n, SlotScratch &S) {
-    S.bits = 1;
-    while (S.bits < 31 && ((int64_t)1 << S.bits) < n_table) ++S.bits;
-    S.sort_bytes = 0;
-    MKB_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, S.sort_bytes, (const int *)nullptr, (int *)nullptr, (const int *)nullptr,
-                                                     (int *)nullptr, (int)n, 0, S.bits, (hipStream_t)0));
-    S.l_bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-    S.total = 4 * S.l_bytes + ((S.sort_bytes + 255) & ~(size_t)255);
-    return MKB_OK;
-}
-
-static bool part_ok(int part) { return part >= MKB_PART_HEAD && part <= MKB_PART_TAIL; }
-static bool shape_ok(const mkb_tables_t *tb, int64_t B, int64_t M) {
-    return B >= 0 && B <= INT32_MAX && M >= 1 && M <= INT32_MAX && B * M <= INT32_MAX && tb->n_entity <= INT32_MAX
-           && tb->n_relation <= INT32_MAX;
-}
-
-static int check_cand_call(const mkb_tables_t *tb, const int64_t *sample, const int64_t *cand, int64_t B, int64_t M, int part) {
-    if (int rc = validate_tables(tb)) return rc;
-    MKB_REQUIRE(sample != nullptr && cand != nullptr, "null pointer");
-    MKB_REQUIRE(part_ok(part), "bad part %d", part);
-    MKB_REQUIRE(shape_ok(tb, B, M), "B must lie in [0, 2^31 - 1], M in [1, 2^31 - 1], B * M and the tables' rows below 2^31");
-    if (rel_lds_bytes(tb) > kRelLdsMax)
-        return set_error(MKB_ERR_UNSUPPORTED, "entity rows of more than %d floats are not supported for candidate lists",
-                         (int)(kRelLdsMax / sizeof(float) / (2 + kRelWaves)));
-    return MKB_OK;
-}
-
-template <int MODEL, bool VARY_HEAD>
-static int launch_slot_bwd(const mkb_tables_t *tb, const mkb_grads_t &G, const int64_t *sample, const int64_t *cand, int64_t B, int M,
-                           const float *dscore, void *ws, const SlotScratch &S, hipStream_t st) {
-    const TablesDev T = to_dev(tb);
-    const int64_t n = B * M, n_table = VARY_HEAD ? tb->n_entity : tb->n_relation;
-    unsigned char *buf = (unsigned char *)ws;
-    int *k_in = (int *)buf, *v_in = (int *)(buf + S.l_bytes), *k_out = (int *)(buf + 2 * S.l_bytes), *v_out = (int *)(buf + 3 * S.l_bytes);
-    void *tmp = buf + 4 * S.l_bytes;
-    size_t sort_bytes = S.sort_bytes;
-    hipLaunchKernelGGL(slot_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand, (int)n, n_table, k_in, v_in);
-    MKB_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, k_in, k_out, v_in, v_out, (int)n, 0, S.bits, st));
-    hipLaunchKernelGGL((slot_bwd_row_kernel<MODEL, VARY_HEAD>), dim3((unsigned)B), dim3(kRelBlock), 0, st, T, G, sample, cand, M, n_table,
-                       dscore);
-    const int U = ModelTraits<MODEL>::cplx_query ? T.d : (int)T.De;
-    const dim3 grid((unsigned)((n + kSlotChunk - 1) / kSlotChunk), (unsigned)((U + kRelBlock - 1) / kRelBlock));
-    hipLaunchKernelGGL((slot_bwd_cand_kernel<MODEL, VARY_HEAD>), grid, dim3(kRelBlock), 0, st, T, G, k_out, v_out, (int)n, M, sample, dscore);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-}  // namespace mkb
-
-extern "C" int mkb_cand_score_fwd(const mkb_tables_t *tb, const int64_t *sample, const int64_t *cand, int64_t B, int64_t M, int part,
-                                  float *score, void *stream) {
-    if (int rc = check_cand_call(tb, sample, cand, B, M, part)) return rc;
-    MKB_REQUIRE(score != nullptr, "score is null");
-    if (B == 0) return MKB_OK;
-    if (part == MKB_PART_TAIL) return mkb_score_fwd(tb, sample, cand, B, M, MKB_MODE_TAIL, score, stream);  // default mode's instantiation
-    if (int rc = launch_slot_scores(tb, sample, B, cand, M, M, part == MKB_PART_HEAD, score, M, (hipStream_t)stream)) return rc;
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-extern "C" int64_t mkb_cand_score_bwd_workspace_bytes(const mkb_tables_t *tb, int64_t B, int64_t M, int part) {
-    if (!tb || B <= 0 || !part_ok(part) || !shape_ok(tb, B, M)) return 0;
-    if (part == MKB_PART_TAIL) return mkb_score_bwd_workspace_bytes(tb, B, M, MKB_MODE_TAIL);
-    SlotScratch S;
-    return slot_scratch(part == MKB_PART_HEAD ? tb->n_entity : tb->n_relation, B * M, S) ? -1 : (int64_t)S.total;
-}
-
-extern "C" int mkb_cand_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const int64_t *cand, int64_t B,
-                                  int64_t M, int part, const float *dscore, void *ws, int64_t ws_bytes, void *stream) {
-    if (int rc = check_cand_call(tb, sample, cand, B, M, part)) return rc;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && dscore, "null gradient buffer");
-    MKB_REQUIRE(tb->model != MKB_PROTATE || gr->g_modulus, "pRotatE needs g_modulus");
-    if (B == 0) return MKB_OK;
-    const int64_t need = mkb_cand_score_bwd_workspace_bytes(tb, B, M, part);
-    if (need < 0) return MKB_ERR_HIP;  // (the sort's size query failed: its message stands)
-    MKB_REQUIRE(need == 0 || (ws != nullptr && (((uintptr_t)ws) & 255) == 0 && ws_bytes >= need), "workspace null, too small or unaligned");
-    if (part == MKB_PART_TAIL) return mkb_score_bwd(tb, gr, sample, cand, B, M, MKB_MODE_TAIL, dscore, ws, stream);
-    SlotScratch S;
-    if (int rc = slot_scratch(part == MKB_PART_HEAD ? tb->n_entity : tb->n_relation, B * M, S)) return rc;
-    return dispatch_model_side(tb->model, part == MKB_PART_HEAD, [&](auto m, auto vh) {
-        return launch_slot_bwd<m(), vh()>(tb, *gr, sample, cand, B, (int)M, dscore, ws, S, (hipStream_t)stream);
-    });
 }

@@ -35,6 +35,32 @@ AUTO_POOL_MIN_SLOTS = 32768
 VALIDATE_IDS = True
 
 
+def _modulus_slot(model):
+    """The tensor in the score functions' ``modulus`` slot: ``gamma`` when the model has none (autograd.Function needs a tensor
+    there; the kernels never read it)."""
+    modulus = getattr(model, "modulus", None)
+    return model.gamma if modulus is None else modulus
+
+
+def _backward_buffers(model, saved, entity_ids, relation_ids):
+    """What the backward of a score function adds its table gradients into: ``(Grads, g_mod, what autograd gets back)``.
+    One dense zero-filled buffer per table (``_gradshare.take``), returned to autograd -- except that a table stepped by a
+    row-lazy optimizer takes a short candidate list's rows straight into ``.grad`` (``_gradshare.direct``; autograd gets
+    ``None``).  ``entity_ids`` / ``relation_ids``: callables giving the rows the backward writes, ``None`` = always the dense
+    buffer.  ``g_mod``: pRotatE's modulus gradient, else ``None``."""
+    ent, rel, modulus, sample, cand = saved
+
+    def buffer(param, table, ids):  # -> (buffer, whether autograd gets it back)
+        g = _gradshare.direct(param, table, ids) if ids is not None and _few(cand) else None
+        return _gradshare.take(param, table) if g is None else (g, False)
+
+    g_ent, fresh_e = buffer(model.entity_embedding, ent, entity_ids)
+    g_rel, fresh_r = buffer(model.relation_embedding, rel, relation_ids)
+    g_mod = torch.zeros_like(modulus) if model.name == "pRotatE" else None
+    gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
+    return gr, g_mod, ((g_ent if fresh_e else None), (g_rel if fresh_r else None), g_mod, None, None, None, None)
+
+
 class _ScoreFn(torch.autograd.Function):
     """score = model.forward(...) on device; backward = dense d loss / d tables."""
 
@@ -58,22 +84,14 @@ class _ScoreFn(torch.autograd.Function):
         B = sample.shape[0]
         K = 1 if cand is None else cand.shape[1]
         dscore = _hip.contiguous(dscore, torch.float32)
-        # (one dense buffer per table and backward pass: the positive and the negative score functions of a step share it)
-        # (a row-lazy optimizer's table takes its rows straight into .grad: _gradshare.direct)
-        g_ent = _gradshare.direct(model.entity_embedding, ent, lambda: _read_entity_ids(sample, cand)) if _few(cand) else None
-        fresh_e = False
-        if g_ent is None:
-            g_ent, fresh_e = _gradshare.take(model.entity_embedding, ent)
-        g_rel, fresh_r = _gradshare.take(model.relation_embedding, rel)
-        g_mod = torch.zeros_like(modulus) if model.name == "pRotatE" else None
+        gr, g_mod, out = _backward_buffers(model, ctx.saved_tensors, lambda: _read_entity_ids(sample, cand), None)
         tb = model._tables(ent, rel, modulus)
-        gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
         with _hip.on_device(ent.device):
             n_ws = _hip.lib().mkb_score_bwd_workspace_bytes(tb, B, K, ctx.mode)  # the glue owns every buffer (mkb_hip.h)
             ws = _hip.aligned_bytes(n_ws, ent.device) if n_ws > 0 else None
             _hip.check(_hip.lib().mkb_score_bwd(tb, gr, _hip.ptr(sample), _hip.ptr(cand), B, K, ctx.mode,
                                                 _hip.ptr(dscore), _hip.ptr(ws), _hip.stream_ptr()), "mkb_score_bwd")
-        return (g_ent if fresh_e else None), (g_rel if fresh_r else None), g_mod, None, None, None, None
+        return out
 
 
 PARTS = {"head": _hip.PART_HEAD, "relation": _hip.PART_RELATION, "tail": _hip.PART_TAIL}  # mkb_part_t = the column of a triple
@@ -114,25 +132,15 @@ class _CandScoreFn(torch.autograd.Function):
         model, part = ctx.model, ctx.part
         B, M = cand.shape
         dscore = _hip.contiguous(dscore, torch.float32)
-        # (a row-lazy optimizer's table takes its rows straight into .grad: _gradshare.direct; as in _ScoreFn.backward)
-        g_ent = g_rel = None
-        if _few(cand):
-            g_ent = _gradshare.direct(model.entity_embedding, ent, lambda: _part_rows(sample, cand, part)[0])
-            g_rel = _gradshare.direct(model.relation_embedding, rel, lambda: _part_rows(sample, cand, part)[1])
-        fresh_e = fresh_r = False
-        if g_ent is None:
-            g_ent, fresh_e = _gradshare.take(model.entity_embedding, ent)
-        if g_rel is None:
-            g_rel, fresh_r = _gradshare.take(model.relation_embedding, rel)
-        g_mod = torch.zeros_like(modulus) if model.name == "pRotatE" else None
+        gr, g_mod, out = _backward_buffers(model, ctx.saved_tensors, lambda: _part_rows(sample, cand, part)[0],
+                                           lambda: _part_rows(sample, cand, part)[1])
         tb = model._tables(ent, rel, modulus)
-        gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
         with _hip.on_device(ent.device):
             n_ws = _hip.lib().mkb_cand_score_bwd_workspace_bytes(tb, B, M, part)  # the glue owns every buffer (mkb_hip.h)
             ws = _hip.aligned_bytes(n_ws, ent.device) if n_ws > 0 else None
             _hip.check(_hip.lib().mkb_cand_score_bwd(tb, gr, _hip.ptr(sample), _hip.ptr(cand), B, M, part, _hip.ptr(dscore),
                                                      _hip.ptr(ws), max(n_ws, 0), _hip.stream_ptr()), "mkb_cand_score_bwd")
-        return (g_ent if fresh_e else None), (g_rel if fresh_r else None), g_mod, None, None, None, None
+        return out
 
 
 # candidate lists up to this many ids are made current row by row in front of a forward pass (and their gradient rows recorded
@@ -305,10 +313,7 @@ class BaseModel(Base):
             cand = _hip.contiguous(negative_sample, torch.int64)
         if lazy:
             self._make_current(sample, _read_entity_ids(sample, cand) if _few(cand) else None)
-        modulus = getattr(self, "modulus", None)
-        if modulus is None:  # autograd.Function needs a tensor slot; never read by the kernels
-            modulus = self.gamma
-        score = _ScoreFn.apply(self.entity_embedding, self.relation_embedding, modulus, self, sample, cand, mode_id)
+        score = _ScoreFn.apply(self.entity_embedding, self.relation_embedding, _modulus_slot(self), self, sample, cand, mode_id)
         return score.view(shape)
 
     def score_candidates(self, sample, candidates, part):
@@ -331,11 +336,8 @@ class BaseModel(Base):
         if _links.owner(self.entity_embedding) is not None or _links.owner(self.relation_embedding) is not None:
             ent_ids, rel_ids = _part_rows(sample, cand, col) if _few(cand) else (None, None)
             self._make_current(sample, ent_ids, rel_ids)
-        modulus = getattr(self, "modulus", None)
-        if modulus is None:  # autograd.Function needs a tensor slot; never read by the kernels
-            modulus = self.gamma
         try:
-            return _CandScoreFn.apply(self.entity_embedding, self.relation_embedding, modulus, self, sample, cand, col)
+            return _CandScoreFn.apply(self.entity_embedding, self.relation_embedding, _modulus_slot(self), self, sample, cand, col)
         except _Unsupported:  # rows too long for the kernel's LDS staging: the general kernels on the substituted block
             block = sample.unsqueeze(1).repeat(1, cand.shape[1], 1)
             block[:, :, col] = cand

@@ -120,6 +120,29 @@ def test_random_problem_vs_oracle(name, mode, shape):
     np.testing.assert_allclose(gr, c["g_rel"], rtol=1e-4, atol=tol)
 
 
+@pytest.mark.parametrize("name", MODELS)
+@pytest.mark.parametrize("mode", MODES[1:])
+def test_two_pass_backward_at_chunk_edges(name, mode):
+    """``mkb_score_bwd``'s two-pass backward in both modes with more than 256 units per row (TransE / RotatE 257, ComplEx 130
+    complex units, DistMult / pRotatE 513) and 63, 64 and 65 pairs -- the edges of the dx pass's 64-pair chunks -- against autograd
+    of the float64 oracle on the substituted block: the shapes and bounds of ``test_gpu_cand_scores``'s backward test, whose tail
+    part meets them through the same kernels in tail mode."""
+    import test_gpu_cand_scores as C
+
+    part = mode.split("-")[0]
+    model = C._tables(name, C.N_BWD, C.R_BWD, C.BWD_HIDDEN[name], seed=7 + MODELS.index(name))
+    rs = np.random.RandomState(31 * MODELS.index(name) + len(mode))
+    g = torch.Generator().manual_seed(5)
+    for B, K in C.PAIR_SHAPES[:3]:
+        for pattern in ("random", "one"):
+            sample, cand = C._problem(rs, C.N_BWD, C.R_BWD, B, K, part, pattern)
+            dscore = C._seed(B, K, g)
+            ref = C._reference_grads(model, C._block(sample, cand, part), dscore)
+            model.zero_grad(set_to_none=True)
+            (model(sample.cuda(), cand.cuda(), mode) * dscore.cuda()).sum().backward()
+            C._check_against(model, C._grads(model), ref)
+
+
 def test_cpu_tensors_are_rejected():
     from mkb_amd import models
 
