@@ -9,6 +9,11 @@
 // fp32-input matrix instruction v_mfma_f32_32x32x2_f32 runs at the fp32 vector rate with bitwise fmaf-chain
 // numerics, which is what the 1e-4 parity budget wants.
 //
+// This header holds the kernels and, at its end, the launchers.  What is launched -- kernel family, tiles, K split, grid, LDS,
+// where C goes, the pending tail, the floats written into the partial buffer -- is decided in ONE place, plan_gemm
+// (gemm_plan.h: plain host code); the launchers take a GemmPlan and decide nothing, and they read no environment: the callers
+// read the three MKB_GEMM_* switches once per ABI call (gemm_switches_from_env) and pass them to the planner as a value.
+//
 // One kernel, 256 lanes = 4 waves, 64 x 64 output tile (one 32 x 32 MFMA tile per wave), K stepped in chunks of
 // 32 through LDS.  Operand layouts are template flags; tiles are always read from global memory with the lanes
 // along the CONTIGUOUS index (coalesced 128-B segments) and stored in LDS as [m][k] / [n][k] with a +1 pad so the
@@ -19,13 +24,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace mkb {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-enum { GEMM_STORE = 0, GEMM_STORE_AFFINE = 1, GEMM_ATOMIC_ROWS = 2 };
-constexpr bool kGemmBf16x3Default = true;  // MKB_GEMM_BF16X3=0: the fp32-input matrix instruction instead (gemm128_f32_mfma_kernel)
 
 struct GemmArgs {
     const float *A, *B;
@@ -346,7 +349,6 @@ __global__ __launch_bounds__(256) void gemm128_f32_mfma_kernel(GemmArgs G) {
 // (1024 x 512 x 2000 and its two transposes; fp32 kernel -> this one): score product 26.2 -> 19.7 us, dQ 21.5 -> 20.7,
 // dX 28.8 -> 23.6: these products are short (8-16 chunks per workgroup), what is left is their prologues and epilogues.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int kBfPitch = 80;  // bytes between rows of a bf16 plane
 
 // two values -> one word per plane (element k in the low half, k + 1 in the high half): v_cvt_pk_bf16_f32 rounds to nearest and
 // packs in one instruction; x - hi and (x - hi) - mid are exact in fp32.  11 VALU operations per pair.
@@ -648,180 +650,99 @@ __global__ __launch_bounds__(256) void splitk_scatter_kernel(const float *__rest
     splitk_scatter_block(part, out, c_idx, M, N, ldc, nz, (int)blockIdx.x, depth, n_depth, s_red);
 }
 
-// These products are small (1-2 GFLOP) and short in one dimension: fill the chip by halving the tile height and / or
-// splitting K (ksplit > 1: STORE epilogues go through `partials` [ksplit, M, ldc] and a fixed-order reduction;
-// the atomic epilogue just accumulates).
-// tail: non-null = the caller folds a split-K reduction / scatter into its next launch (GemmTail, common.h): it is described
-// there instead of being launched (kind 0 when the product needed none).
-template <bool A_MK, bool B_NK, int EPI>
-// slices_cap > 0 (STORE epilogue): the caller's consumer adds up to slices_cap partial products itself -- C is [slices][M][ldc];
-// a K split then writes its partials straight there (no partial buffer, no reduction launch) and *slices_used says how many.
-// max_ks: the largest K split the plan may choose (1 = never split: a caller whose `partials` is only the permission to take
-// the 128-row tiles and holds no room for [ks][M][ldc] partial products -- the ranking route).
-static int launch_gemm(GemmArgs G, hipStream_t st, float *partials = nullptr, GemmTail *tail = nullptr, int want_wg = 0,
-                       int slices_cap = 0, int *slices_used = nullptr, int max_ks = 8) {
+// ---------------------------------------------------------------------------------------------------- host side
+// Every decision of a product -- kernel family, tiles, K split, grid, LDS, where C goes, the tail -- is plan_gemm's
+// (gemm_plan.h); the launchers below launch from a GemmPlan and decide nothing.
+
+// The three switches of the products, read by the ABI entry points (once per call: the tests flip them within one process)
+static GemmSwitches gemm_switches_from_env() {
+    const char *bx = getenv("MKB_GEMM_BF16X3");
+    return GemmSwitches{getenv("MKB_GEMM_NO128") != nullptr, getenv("MKB_GEMM_NO_PAIR") != nullptr, !bx || bx[0] == '1'};
+}
+
+// the sizes of a planned product; the caller adds the pointers
+static GemmArgs gemm_args(const GemmPlan &P) {
+    GemmArgs G{};
+    G.M = P.s.M; G.N = P.s.N; G.K = P.s.K; G.lda = P.s.lda; G.ldb = P.s.ldb; G.ldc = P.s.ldc; G.b_rows = P.s.b_rows;
+    G.ksplit = P.ks;
+    return G;
+}
+
+// what the kernel is given: the K split, and the partial buffer in place of C where the plan sends the product there
+static GemmArgs gemm_kernel_args(const GemmPlan &P, GemmArgs G, float *partials) {
+    G.ksplit = P.ks;
+    if (P.dest == GemmDest::Partials) G.C = partials;
+    if (P.tail == GemmTailKind::Scatter) G.ldc = G.N;
+    return G;
+}
+
+// the pending tail of a product: described in *tail where the plan hands it on, launched otherwise
+static int gemm_finish(const GemmPlan &P, const GemmArgs &G, hipStream_t st, float *partials, GemmTail *tail) {
     if (tail) tail->kind = 0;
-    const bool to_slices = slices_cap > 0 && EPI == GEMM_STORE && slices_used;
-    if (slices_used) *slices_used = 1;
-    {   // 128 x 128 / 128 x 64 tiles (4 / 2 accumulators per wave) when the operands allow 16-byte loads
-        const bool off = getenv("MKB_GEMM_NO128") != nullptr;  // read per call, as in launch_gemm_bwd_pair
-        const bool al = (((uintptr_t)G.A | (uintptr_t)G.B) & 15) == 0 && G.lda % 4 == 0 && G.ldb % 4 == 0 && G.M % 4 == 0 &&
-                        G.N % 4 == 0 && G.K % 4 == 0;
-        const int tiles128 = ((G.M + 127) / 128) * ((G.N + 127) / 128);
-        if (!off && al && tiles128 >= 24 && (EPI == GEMM_ATOMIC_ROWS || partials)) {
-            // fill ~256 CUs: prefer the narrower tile (no K split, no reduction launch) to splitting K
-            const bool narrow = tiles128 < 200;
-            const int tiles = narrow ? ((G.M + 127) / 128) * ((G.N + 63) / 64) : tiles128;
-            int ks = 1;
-            // workgroups wanted: ~1 per CU by default; the score product asks for 2 (want_wg = 500: a lone 4-wave workgroup leaves
-            // each SIMD's matrix pipe idle during its staging; measured 37 -> 29 us, the split-K sum rides the loss rows anyway)
-            const int min_wg = want_wg ? want_wg : 200;
-            while (tiles * ks < min_wg && ks < max_ks && G.K / (ks * 2) >= 96 && (!to_slices || ks * 2 <= slices_cap)) ks *= 2;
-            G.ksplit = ks;
-            if (to_slices) *slices_used = ks;
-            float *final_c = G.C;
-            const int tn = narrow ? 64 : 128;
-            const size_t lds = (size_t)2 * (128 + tn) * 33 * 4 + (size_t)(((G.K + ks - 1) / ks + 31) / 32 * 32) * 4;  // two stages + row ids
-            dim3 grid((unsigned)((G.M + 127) / 128), (unsigned)((G.N + tn - 1) / tn), (unsigned)ks);
-            // (two stages of a 128 x 128 tile pair are 66 KB: more than the 64 KB a kernel gets without asking)
-            // the three-way bf16 split on the bf16 matrix pipe (gemm128_bf16x3_mfma_kernel) unless MKB_GEMM_BF16X3=0; read per call
-            const char *bx = getenv("MKB_GEMM_BF16X3");
-            // (its buffer loads address an operand with 32-bit byte offsets: every row it can touch must lie within 4 GB of the base)
-            const int64_t a_span = (A_MK ? (int64_t)G.M * G.lda : (int64_t)G.K * G.lda) * 4;
-            const int64_t b_rows = G.b_idx ? G.b_rows : (B_NK ? (int64_t)G.N : (int64_t)G.K);
-            // (offsets are added as SIGNED 32-bit integers in the staging: operands of 2 GB and more take the fp32 kernel)
-            const bool fits32 = a_span < ((int64_t)1 << 31) && b_rows > 0 && b_rows * G.ldb * 4 < ((int64_t)1 << 31);
-            const bool bf16x3 = fits32 && (bx ? bx[0] == '1' : kGemmBf16x3Default);
-            const size_t lds_bf = (size_t)3 * (128 + tn) * kBfPitch + (size_t)(((G.K + ks - 1) / ks + 31) / 32 * 32) * 4;
-            auto launch128 = [&](auto epi_c, auto tn_c, const GemmArgs &GA) -> int {
-                constexpr int E = decltype(epi_c)::value, TNv = decltype(tn_c)::value;
-                static LdsOptIn grant[2];  // (per instantiation of this generic lambda and kernel form)
-                if constexpr (E != GEMM_ATOMIC_ROWS) {  // (the scattered product goes through split-K partials: STORE; the direct
-                                                        // atomic epilogue -- a caller without a partial buffer -- keeps the fp32 kernel)
-                    if (bf16x3) {
-                        auto *fn = &gemm128_bf16x3_mfma_kernel<A_MK, B_NK, E, TNv>;
-                        if (int rc = grant[1].ensure(reinterpret_cast<const void *>(fn), lds_bf)) return rc;
-                        hipLaunchKernelGGL(fn, grid, dim3(256), lds_bf, st, GA);
-                        return MKB_OK;
-                    }
-                }
-                auto *fn = &gemm128_f32_mfma_kernel<A_MK, B_NK, E, TNv>;
-                if (int rc = grant[0].ensure(reinterpret_cast<const void *>(fn), lds)) return rc;
-                hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, GA);
-                return MKB_OK;
-            };
-            typedef std::integral_constant<int, 64> tn64_t;
-            typedef std::integral_constant<int, 128> tn128_t;
-            if (EPI == GEMM_ATOMIC_ROWS && partials) {  // partial products [ks, M, N], then one scattered add per element
-                GemmArgs P2 = G;
-                P2.C = partials; P2.ldc = G.N;
-                typedef std::integral_constant<int, GEMM_STORE> store_t;
-                if (int rc = narrow ? launch128(store_t{}, tn64_t{}, P2) : launch128(store_t{}, tn128_t{}, P2)) return rc;
-                const int *dp = G.depth_mode == 3 ? G.depth : nullptr;
-                if (tail) *tail = GemmTail{2, partials, final_c, G.c_idx, G.M, G.N, ks, G.ldc, 0, 0.f, 1.f, dp, G.n_depth};
-                else hipLaunchKernelGGL(splitk_scatter_kernel<0>, dim3((unsigned)G.M), dim3(256), 0, st, partials, final_c, G.c_idx, G.M,
-                                        G.N, G.ldc, ks, dp, G.n_depth);
-                MKB_LAUNCH_CHECK();
-                return MKB_OK;
-            }
-            if (ks > 1 && EPI != GEMM_ATOMIC_ROWS && !to_slices) G.C = partials;
-            typedef std::integral_constant<int, EPI> epi_t;
-            if (int rc = narrow ? launch128(epi_t{}, tn64_t{}, G) : launch128(epi_t{}, tn128_t{}, G)) return rc;
-            if (ks > 1 && EPI != GEMM_ATOMIC_ROWS && !to_slices) {
-                const int64_t n = (int64_t)G.M * G.ldc;
-                const float c0 = EPI == GEMM_STORE_AFFINE ? G.c0 : 0.f, c1 = EPI == GEMM_STORE_AFFINE ? G.c1 : 1.f;
-                if (tail) *tail = GemmTail{1, partials, final_c, nullptr, G.M, G.N, ks, G.ldc, n, c0, c1, nullptr, 0};
-                else hipLaunchKernelGGL(splitk_reduce_kernel<0>, dim3(512), dim3(256), 0, st, partials, final_c, n, ks, c0, c1);
-            }
-            MKB_LAUNCH_CHECK();
-            return MKB_OK;
-        }
-    }
-    const int tiles64 = ((G.M + 63) / 64) * ((G.N + 63) / 64);
-    const bool half = tiles64 < 256;
-    const int tiles = half ? ((G.M + 31) / 32) * ((G.N + 63) / 64) : tiles64;
-    int ks = 1;
-    if (EPI == GEMM_ATOMIC_ROWS || partials || to_slices) {
-        while (tiles * ks < 768 && ks < max_ks && G.K / (ks * 2) >= 128 && (!to_slices || ks * 2 <= slices_cap)) ks *= 2;
-    }
-    G.ksplit = ks;
-    if (to_slices) *slices_used = ks;
-    float *final_c = G.C;
-    if (ks > 1 && EPI != GEMM_ATOMIC_ROWS && !to_slices) G.C = partials;
-    dim3 grid((unsigned)((G.M + (half ? 31 : 63)) / (half ? 32 : 64)), (unsigned)((G.N + 63) / 64), (unsigned)ks);
-    if (half) hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_MK, B_NK, EPI, 32>), grid, dim3(128), 0, st, G);
-    else hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_MK, B_NK, EPI, 64>), grid, dim3(256), 0, st, G);
-    if (ks > 1 && EPI != GEMM_ATOMIC_ROWS && !to_slices) {
+    if (P.tail == GemmTailKind::Scatter) {
+        const int *dp = G.depth_mode == 3 ? G.depth : nullptr;
+        if (P.tail_handed) *tail = GemmTail{2, partials, G.C, G.c_idx, G.M, G.N, P.ks, G.ldc, 0, 0.f, 1.f, dp, G.n_depth};
+        else hipLaunchKernelGGL(splitk_scatter_kernel<0>, dim3((unsigned)G.M), dim3(256), 0, st, partials, G.C, G.c_idx, G.M, G.N, G.ldc,
+                                P.ks, dp, G.n_depth);
+    } else if (P.tail == GemmTailKind::Reduce) {
         const int64_t n = (int64_t)G.M * G.ldc;
-        const float c0 = EPI == GEMM_STORE_AFFINE ? G.c0 : 0.f, c1 = EPI == GEMM_STORE_AFFINE ? G.c1 : 1.f;
-        hipLaunchKernelGGL(splitk_reduce_kernel<0>, dim3(512), dim3(256), 0, st, partials, final_c, n, ks, c0, c1);
+        const bool affine = P.s.epi == GEMM_STORE_AFFINE;
+        const float c0 = affine ? G.c0 : 0.f, c1 = affine ? G.c1 : 1.f;
+        if (P.tail_handed) *tail = GemmTail{1, partials, G.C, nullptr, G.M, G.N, P.ks, G.ldc, n, c0, c1, nullptr, 0};
+        else hipLaunchKernelGGL(splitk_reduce_kernel<0>, dim3(512), dim3(256), 0, st, partials, G.C, n, P.ks, c0, c1);
     }
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
 
-// The backward pair of the bilinear models as ONE launch (gemm128_bf16x3_pair_kernel): dQ = G . X (A k-contiguous, B gathered rows,
-// STORE into up to `slices_cap` dQ slices) and the scattered dX = G^T . Q (through split-K partials, its tail -- one atomic per
-// element -- described in *x_tail or launched).  Plans each product exactly as launch_gemm would (tile width, K split); *done =
-// false when either does not qualify for the 128-row bf16 tiles (the caller then launches them one by one).
-static int launch_gemm_bwd_pair(GemmArgs GQ, int slices_cap, int *slices_used, GemmArgs GX, float *partials, GemmTail *x_tail,
-                                hipStream_t st, bool *done) {
-    *done = false;
-    const bool off = getenv("MKB_GEMM_NO128") != nullptr || getenv("MKB_GEMM_NO_PAIR") != nullptr;  // (read per call: the tests flip them within one process)
-    const char *bx = getenv("MKB_GEMM_BF16X3");
-    if (off || !(bx ? bx[0] == '1' : kGemmBf16x3Default) || !partials || !slices_used || slices_cap < 1) return MKB_OK;
-    struct Plan { bool ok, narrow; int ks, tn, mx, ny; size_t lds; };
-    auto plan = [&](const GemmArgs &G, bool a_mk, bool b_nk, int cap) {
-        Plan P{false, false, 1, 128, 0, 0, 0};
-        const bool al = (((uintptr_t)G.A | (uintptr_t)G.B) & 15) == 0 && G.lda % 4 == 0 && G.ldb % 4 == 0 && G.M % 4 == 0 && G.N % 4 == 0 &&
-                        G.K % 4 == 0;
-        const int tiles128 = ((G.M + 127) / 128) * ((G.N + 127) / 128);
-        const int64_t a_span = (a_mk ? (int64_t)G.M * G.lda : (int64_t)G.K * G.lda) * 4;
-        const int64_t b_rows = G.b_idx ? G.b_rows : (b_nk ? (int64_t)G.N : (int64_t)G.K);
-        const bool fits32 = a_span < ((int64_t)1 << 31) && b_rows > 0 && b_rows * G.ldb * 4 < ((int64_t)1 << 31);
-        if (!al || tiles128 < 24 || !fits32) return P;
-        P.narrow = tiles128 < 200;
-        P.tn = P.narrow ? 64 : 128;
-        const int tiles = P.narrow ? ((G.M + 127) / 128) * ((G.N + 63) / 64) : tiles128;
-        // (short rows -- DistMult's 1000 floats -- leave few tiles: split K further there: 26.5 -> 23.4 us for its pair; the
-        // 2000-float rows of ComplEx lose with more splits, 42 -> 49 us: their partials are what the extra workgroups move)
-        const int min_wg = G.N <= 1024 ? 400 : 200;
-        while (tiles * P.ks < min_wg && P.ks < 8 && G.K / (P.ks * 2) >= 96 && (cap <= 0 || P.ks * 2 <= cap)) P.ks *= 2;
-        P.mx = (G.M + 127) / 128; P.ny = (G.N + P.tn - 1) / P.tn;
-        P.lds = (size_t)3 * (128 + P.tn) * kBfPitch + (size_t)(((G.K + P.ks - 1) / P.ks + 31) / 32 * 32) * 4;
-        P.ok = true;
-        return P;
+// One planned product.  partials: the partial buffer (>= P.part_floats floats); tail: where a handed-on tail is described
+// (needed when the plan was made with fold_tail).  A plan with slices leaves P.slices() partial products in C.
+template <bool A_MK, bool B_NK, int EPI>
+static int launch_gemm(const GemmPlan &P, const GemmArgs &G, hipStream_t st, float *partials = nullptr, GemmTail *tail = nullptr) {
+    const GemmArgs K = gemm_kernel_args(P, G, partials);
+    const dim3 grid(P.mx, P.ny, (unsigned)P.ks);
+    if (P.kernel == GemmKernel::F32Tile64) {
+        if (P.tm == 32) hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_MK, B_NK, EPI, 32>), grid, dim3(P.wg), 0, st, K);
+        else hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_MK, B_NK, EPI, 64>), grid, dim3(P.wg), 0, st, K);
+        return gemm_finish(P, G, st, partials, tail);
+    }
+    constexpr int E = EPI == GEMM_ATOMIC_ROWS ? GEMM_STORE : EPI;  // (the scattered product goes through partials: STORE)
+    auto go = [&](auto tn_c) -> int {
+        constexpr int TN = decltype(tn_c)::value;
+        static LdsOptIn grant[2];  // (per instantiation of this generic lambda and kernel form)
+        const bool bf = P.kernel == GemmKernel::Bf16x3Tile128;
+        auto *fn = bf ? &gemm128_bf16x3_mfma_kernel<A_MK, B_NK, E, TN> : &gemm128_f32_mfma_kernel<A_MK, B_NK, E, TN>;
+        if (int rc = grant[bf].ensure(reinterpret_cast<const void *>(fn), P.lds)) return rc;
+        hipLaunchKernelGGL(fn, grid, dim3(P.wg), P.lds, st, K);
+        return MKB_OK;
     };
-    const Plan pq = plan(GQ, true, false, slices_cap), px = plan(GX, false, false, 0);
-    if (!pq.ok || !px.ok) return MKB_OK;
-    GQ.ksplit = pq.ks;
-    *slices_used = pq.ks;
-    GemmArgs X2 = GX;  // partial products [ks, M, N], then one scattered add per element (the tail)
-    X2.C = partials; X2.ldc = GX.N; X2.ksplit = px.ks;
-    const GemmPairGrid grid{pq.mx, pq.ny, pq.ks, px.mx, px.ny, px.ks};
-    const size_t lds = pq.lds > px.lds ? pq.lds : px.lds;
-    const unsigned blocks = (unsigned)(pq.mx * pq.ny * pq.ks + px.mx * px.ny * px.ks);
+    if (int rc = P.tn == 64 ? go(std::integral_constant<int, 64>{}) : go(std::integral_constant<int, 128>{})) return rc;
+    return gemm_finish(P, G, st, partials, tail);
+}
+
+// The backward pair of the bilinear models as ONE launch (gemm128_bf16x3_pair_kernel): dQ = G . X (A k-contiguous, B gathered
+// rows, STORE into PQ.slices() dQ slices) and the scattered dX = G^T . Q (through split-K partials, then its tail).  Both plans
+// are of the 128-row bf16x3 tiles (the caller checked).
+static int launch_gemm_bwd_pair(const GemmPlan &PQ, const GemmArgs &GQ, const GemmPlan &PX, const GemmArgs &GX, float *partials,
+                                GemmTail *x_tail, hipStream_t st) {
+    const GemmArgs KQ = gemm_kernel_args(PQ, GQ, nullptr), KX = gemm_kernel_args(PX, GX, partials);
+    const GemmPairGrid grid{(int)PQ.mx, (int)PQ.ny, PQ.ks, (int)PX.mx, (int)PX.ny, PX.ks};
+    const size_t lds = PQ.lds > PX.lds ? PQ.lds : PX.lds;
     auto go = [&](auto tq, auto tx) -> int {
         constexpr int TQ = decltype(tq)::value, TX = decltype(tx)::value;
         auto *fn = &gemm128_bf16x3_pair_kernel<true, false, GEMM_STORE, TQ, false, false, GEMM_STORE, TX>;
         static LdsOptIn grant;  // (per instantiation of this generic lambda)
         if (int rc = grant.ensure(reinterpret_cast<const void *>(fn), lds)) return rc;
-        hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, st, GQ, X2, grid);
+        hipLaunchKernelGGL(fn, dim3(PQ.blocks() + PX.blocks()), dim3(256), lds, st, KQ, KX, grid);
         return MKB_OK;
     };
     typedef std::integral_constant<int, 64> t64;
     typedef std::integral_constant<int, 128> t128;
     int rc;
-    if (pq.narrow) rc = px.narrow ? go(t64{}, t64{}) : go(t64{}, t128{});
-    else rc = px.narrow ? go(t128{}, t64{}) : go(t128{}, t128{});
+    if (PQ.tn == 64) rc = PX.tn == 64 ? go(t64{}, t64{}) : go(t64{}, t128{});
+    else rc = PX.tn == 64 ? go(t128{}, t64{}) : go(t128{}, t128{});
     if (rc) return rc;
-    const int *dp = GX.depth_mode == 3 ? GX.depth : nullptr;
-    if (x_tail) *x_tail = GemmTail{2, partials, GX.C, GX.c_idx, GX.M, GX.N, px.ks, GX.ldc, 0, 0.f, 1.f, dp, GX.n_depth};
-    else hipLaunchKernelGGL(splitk_scatter_kernel<0>, dim3((unsigned)GX.M), dim3(256), 0, st, partials, GX.C, GX.c_idx, GX.M, GX.N, GX.ldc,
-                            px.ks, dp, GX.n_depth);
-    MKB_LAUNCH_CHECK();
-    *done = true;
-    return MKB_OK;
+    return gemm_finish(PX, GX, st, partials, x_tail);
 }
 
 }  // namespace mkb

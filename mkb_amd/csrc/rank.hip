@@ -10,7 +10,8 @@
 //           forward (8 rows per 1024-lane workgroup, swap/DPP wave reduction, LDS cross-wave combine per 16
 //           candidates) but the candidates are simply consecutive table rows, split into slices over grid.y.
 //           RotatE / TransE: the pooled forward's outer-product register tile instead; ComplEx / DistMult: one matrix-core
-//           product (run_rank).
+//           product (run_rank), planned by plan_gemm (gemm_plan.h) with this route's limits -- no partial buffer, no K split --
+//           and the three MKB_GEMM_* switches, which run_rank reads there, once per call.
 // Kernel 2  rank    : one wave per query: count scores above the target's, then walk the query's true set
 //           (a contiguous range of the sorted key array) and take back the ones that were counted.
 #include "common.h"
@@ -497,13 +498,14 @@ static int run_rank(const mkb_tables_t *tb, const int64_t *sample, int64_t B, fl
         if (ids && B % 4 == 0 && tb->entity_dim % 4 == 0 && tb->entity_dim >= 16 && B >= 32 &&
             (((uintptr_t)tb->ent | (uintptr_t)Q | (uintptr_t)S) & 15) == 0 && Npad < (1 << 30)) {
             hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, st, ids, Npad, tb->n_entity);
-            GemmArgs G{};
-            G.A = Q; G.B = tb->ent; G.C = S; G.b_idx = ids; G.b_rows = tb->n_entity;
-            G.M = (int)B; G.N = (int)Npad; G.K = (int)tb->entity_dim; G.ksplit = 1;
-            G.lda = tb->entity_dim; G.ldb = tb->entity_dim; G.ldc = Npad; G.c0 = c0; G.c1 = c1;
-            // max_ks = 1: the workspace holds ONE [B, Npad] score block -- a K split would write its partial products past it
-            // (over the id list this very product gathers through).  `partials` = S only admits the 128-row tiles.
-            if (int rc = launch_gemm<true, true, GEMM_STORE_AFFINE>(G, st, /*partials=*/S, nullptr, 0, 0, nullptr, /*max_ks=*/1)) return rc;
+            // The workspace holds ONE [B, Npad] score block and no partial buffer: max_ks = 1 -- a K split would write its partial
+            // products past S (over the id list this very product gathers through).
+            const GemmShape shape{(int)B, (int)Npad, (int)tb->entity_dim, tb->entity_dim, tb->entity_dim, Npad, true, true,
+                                  GEMM_STORE_AFFINE, true, tb->n_entity};
+            const GemmPlan plan = plan_gemm(shape, GemmLimits{false, 0, 0, /*max_ks=*/1, false}, gemm_switches_from_env());
+            GemmArgs G = gemm_args(plan);
+            G.A = Q; G.B = tb->ent; G.C = S; G.b_idx = ids; G.c0 = c0; G.c1 = c1;
+            if (int rc = launch_gemm<true, true, GEMM_STORE_AFFINE>(plan, G, st)) return rc;
             finish(0.f, 1.f, Npad);
             MKB_LAUNCH_CHECK();
             return MKB_OK;

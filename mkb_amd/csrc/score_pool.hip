@@ -276,7 +276,8 @@ static int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v
 // read once per ABI call (the tests switch them within one process)
 static PoolSwitches switches_from_env() {
     const char *m = getenv("MKB_POOL_NO_MFMA"), *d = getenv("MKB_POOL_DENSE");
-    return PoolSwitches{m && m[0] == '1', !d ? PoolSwitches::kDenseDefault : (d[0] == '1' ? PoolSwitches::kDenseOn : PoolSwitches::kDenseOff)};
+    return PoolSwitches{m && m[0] == '1', !d ? PoolSwitches::kDenseDefault : (d[0] == '1' ? PoolSwitches::kDenseOn : PoolSwitches::kDenseOff),
+                        gemm_switches_from_env()};
 }
 
 // What the plan's decisions know about a table row
@@ -328,8 +329,41 @@ static bool wants_matrix(const mkb_tables_t *tb, const PoolSwitches &sw) {
     return !sw.no_mfma && (tb->model == MKB_COMPLEX || tb->model == MKB_DISTMULT) && tb->entity_dim >= 16;
 }
 
+// The three products of the matrix route: S [B, P] = Q . ent[pool]^T, dQ [B, De] = G [B, P] . ent[pool] and the scattered
+// dX [P, De] = G^T . Q.  Q, G and the partial buffer are workspace segments (256-byte aligned); the table is the caller's.
+static void plan_matrix(const mkb_tables_t *tb, int64_t B, int64_t P, const RowShape &R, const PoolSwitches &sw, PoolFolds folds,
+                        PoolPlan &L) {
+    const int64_t De = tb->entity_dim;
+    const GemmShape s_shape{(int)B, (int)P, (int)De, De, De, P, true, true, GEMM_STORE_AFFINE, R.al16, tb->n_entity};
+    const GemmShape q_shape{(int)B, (int)De, (int)P, P, De, De, true, false, GEMM_STORE, R.al16, tb->n_entity};
+    const GemmShape x_shape{(int)P, (int)De, (int)B, P, De, De, false, false, GEMM_ATOMIC_ROWS, true, B};
+    // (a product whose tail rides the next launch asks for 2 workgroups per CU, want_wg = 500: the tail costs no launch)
+    L.fwd = FwdRoute::Matrix;
+    L.gemm = plan_gemm(s_shape, GemmLimits{true, 0, folds.s ? 500 : 0, 8, folds.s}, sw.gemm);
+    L.bwd = BwdRoute::Matrix;
+    // Both backward products in ONE launch where both take the 128-row bf16x3 tiles.  (Short rows -- DistMult's 1000 floats --
+    // leave few tiles: split K further there: 26.5 -> 23.4 us for its pair; the 2000-float rows of ComplEx lose with more
+    // splits, 42 -> 49 us: their partials are what the extra workgroups move.)
+    const int pair_wg = De <= 1024 ? 400 : 200;
+    BwdMatrix M{plan_gemm(q_shape, GemmLimits{true, kMfmaDqSlices, pair_wg, 8, false}, sw.gemm),
+                plan_gemm(x_shape, GemmLimits{true, 0, pair_wg, 8, folds.x}, sw.gemm), true};
+    M.pair = !sw.gemm.no_pair && M.dq.kernel == GemmKernel::Bf16x3Tile128 && M.dx.kernel == GemmKernel::Bf16x3Tile128;
+    if (!M.pair) {
+        // a K split of dQ leaves its partials in the dQ slices: the row backward sums them (it does so for the VALU route's
+        // position blocks anyway) instead of a reduction launch in between (DistMult: 6.5 us)
+        M.dq = plan_gemm(q_shape, GemmLimits{true, kMfmaDqSlices, 0, 8, false}, sw.gemm);
+        M.dx = plan_gemm(x_shape, GemmLimits{true, 0, folds.x ? 500 : 0, 8, folds.x}, sw.gemm);
+    }
+    L.products = M;
+    L.dq_parts = M.dq.slices();
+    // room for the partials of whichever product runs, under every switch setting and whatever the call folds: callers cache
+    // a workspace per table shape (mkb_pool_step_workspace_bytes), and the two halves of a step must carve the same layout.
+    // (dQ is given the buffer too and counts with its bound, though with slices its K split lands in the dQ buffer: for
+    // B >= P the room is then what it always was, 8 * B * max(P, De) floats; for B < P it grows to dX's 8 * P * De.)
+    L.gemm_part = std::max({L.gemm.part_bound, M.dq.part_bound, M.dx.part_bound});
+}
+
 static void plan_forward(const mkb_tables_t *tb, int64_t B, int64_t P, const RowShape &R, const PoolSwitches &sw, PoolPlan &L) {
-    if (wants_matrix(tb, sw)) { L.fwd = FwdRoute::Matrix; return; }
     // 4 units per lane when the row allows it (measured 91 -> 77 us at the headline shape: the per-position wave
     // reduction is amortised over twice the pair evaluations); the backward kernels gain nothing from it
     const bool wide = R.k4 && R.NU > 512 && R.NU <= 1024;
@@ -406,7 +440,6 @@ static int plan_dense_lanes(const mkb_tables_t *tb, int64_t P, const Bwd1Layout 
 // grid holds ~4096 waves (16 per CU); each block costs one dQ partial buffer.  More blocks than dQ buffers: the two-pass
 // kernel; a handful of workgroups: the wave kernel.
 static bool plan_backward(const mkb_tables_t *tb, int64_t B, int64_t P, const RowShape &R, const PoolSwitches &sw, PoolPlan &L) {
-    if (wants_matrix(tb, sw)) { L.bwd = BwdRoute::Matrix; L.dq_parts = kMfmaDqSlices; return true; }
     Bwd1Layout Y{};
     // units per lane: 2 (1 for odd rows); real-valued models with long rows take 4 -- the same 4 floats per lane and
     // position as RotatE's two complex dims, half the per-position bookkeeping of 2
@@ -439,13 +472,14 @@ static bool plan_backward(const mkb_tables_t *tb, int64_t B, int64_t P, const Ro
 
 // Kernel configuration for a table shape: units per lane (vector width of the loads), waves per workgroup, the routes, and
 // how many workgroups share a row tile / position tile so that the grid fills 256 CUs with 16-32 waves each.
-static bool plan_pool(const mkb_tables_t *tb, int64_t B, int64_t P, const PoolSwitches &sw, PoolPlan &L) {
+static bool plan_pool(const mkb_tables_t *tb, int64_t B, int64_t P, const PoolSwitches &sw, PoolFolds folds, PoolPlan &L) {
     L = PoolPlan{};
     L.rel_elems = tb->n_relation * tb->relation_dim;
     L.rel_copies = plan_rel_copies(tb, B);
     L.n_entity = tb->n_entity;
     RowShape R;
     if (!plan_row_shape(tb, B, P, R, L)) return false;
+    if (wants_matrix(tb, sw)) { plan_matrix(tb, B, P, R, sw, folds, L); return true; }
     plan_forward(tb, B, P, R, sw, L);
     return plan_backward(tb, B, P, R, sw, L);
 }
@@ -459,13 +493,13 @@ static Workspace carve(void *ws, int64_t B, int64_t P, int64_t De, const PoolPla
     auto take = [&](size_t n) { void *r = p ? p + off : nullptr; off += align256(n); return (float *)r; };
     const bool sp = L.single_pass();
     w.Q = take((size_t)B * De * 4);
-    w.dQ = take((size_t)L.dq_parts * B * De * 4);
+    w.dQ = take((size_t)(L.matrix() ? kMfmaDqSlices : L.dq_parts) * B * De * 4);  // (Matrix: the cap its dQ plan was given)
     // gradient seeds: plain [B, P], or the tile-blocked layout of the single-pass backward
     const size_t g_plain = (size_t)B * P, g_blocked = sp ? L.single.seed_elems(B) : 0;
     w.G = take((g_plain > g_blocked ? g_plain : g_blocked) * 4);
     w.dpos = take((size_t)B * 4);
     w.scratch = take((size_t)(B + 1) * 4);
-    w.gemm_part = take(L.matrix() ? (size_t)8 * B * (P > De ? P : De) * 4 : 0);  // split-K partials of the MFMA path
+    w.gemm_part = take(L.matrix() ? L.gemm_part * 4 : 0);  // split-K partials of the matrix route, sized by its plans
     w.dXp = take(sp ? L.single.dxp_elems() * 4 : 0);
     w.xused = (unsigned long long *)take(sp ? L.single.xused_words() * 8 : 0);
     w.rel_rep = take(L.rel_copies > 1 ? (size_t)L.rel_copies * L.rel_elems * 4 : 0);
@@ -549,11 +583,10 @@ static int pooled_fwd(const mkb_tables_t *tb, bool head, const int64_t *sample, 
     if (s_tail) s_tail->kind = 0;
     ProfScope ps(MKB_PROF_POOL_FWD, st);
     if (L.fwd == FwdRoute::Matrix) {  // S = Q . ent[pool]^T on the matrix cores, over the pool positions the row tile uses (cnt masks later)
-        GemmArgs g{};
-        g.A = w.Q; g.lda = tb->entity_dim; g.B = tb->ent; g.ldb = tb->entity_dim; g.b_idx = pool; g.b_rows = tb->n_entity;
-        g.C = S; g.ldc = P; g.M = (int)B; g.N = (int)P; g.K = (int)tb->entity_dim; g.c0 = 0.f; g.c1 = 1.f;
+        GemmArgs g = gemm_args(L.gemm);
+        g.A = w.Q; g.B = tb->ent; g.b_idx = pool; g.C = S; g.c0 = 0.f; g.c1 = 1.f;
         g.depth = w.depth; g.depth_mode = 1; g.n_depth = (int)B;
-        return launch_gemm<true, true, GEMM_STORE_AFFINE>(g, st, w.gemm_part, s_tail, s_tail ? 500 : 0);
+        return launch_gemm<true, true, GEMM_STORE_AFFINE>(L.gemm, g, st, w.gemm_part, s_tail);
     }
     PoolArgs A = make_args(tb, pool, cnt, B, P, w, L, /*bwd=*/false);  // (the kernel also zero-fills the entries no row uses)
     A.S = S;
@@ -565,42 +598,34 @@ static int pooled_fwd(const mkb_tables_t *tb, bool head, const int64_t *sample, 
     return launch_tiles(tb, head, kPoolFwd, L, A, st);
 }
 
-// the two products of the matrix route; dq_parts (out): how many [B, De] partial products the dQ buffer holds
-static int matrix_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *pool, int64_t B, int64_t P, const Workspace &w,
-                      hipStream_t st, GemmTail *x_tail, int *dq_parts) {
+// the two products of the matrix route, as the plan has them: one launch or two
+static int matrix_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *pool, int64_t B, const Workspace &w,
+                      const BwdMatrix &M, hipStream_t st, GemmTail *x_tail) {
     // dQ [B, De] = G [B, P] . ent[pool]   (w.depth was written by this call's row_fwd / query_build)
-    GemmArgs gq{};
-    gq.A = w.G; gq.lda = P; gq.B = tb->ent; gq.ldb = tb->entity_dim; gq.b_idx = pool; gq.b_rows = tb->n_entity;
-    gq.C = w.dQ; gq.ldc = tb->entity_dim; gq.M = (int)B; gq.N = (int)tb->entity_dim; gq.K = (int)P;
+    GemmArgs gq = gemm_args(M.dq);
+    gq.A = w.G; gq.B = tb->ent; gq.b_idx = pool; gq.C = w.dQ;
     gq.depth = w.depth; gq.depth_mode = 2; gq.n_depth = (int)B;  // (G is exactly 0 beyond a row's depth)
     // g_ent[pool[p]] += (G^T [P, B] . Q [B, De])[p]
-    GemmArgs gx{};
-    gx.A = w.G; gx.lda = P; gx.B = w.Q; gx.ldb = tb->entity_dim; gx.b_idx = nullptr;
-    gx.C = gr->g_ent; gx.ldc = tb->entity_dim; gx.c_idx = pool; gx.M = (int)P; gx.N = (int)tb->entity_dim; gx.K = (int)B;
+    GemmArgs gx = gemm_args(M.dx);
+    gx.A = w.G; gx.B = w.Q; gx.C = gr->g_ent; gx.c_idx = pool;
     gx.depth = w.depth; gx.depth_mode = 3; gx.n_depth = (int)B;
-    bool paired = false;
-    {   // both products in ONE launch where they qualify (profiled as the POOL_BWD_Q class)
+    if (M.pair) {  // (profiled as the POOL_BWD_Q class)
         ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-        if (int rc = launch_gemm_bwd_pair(gq, kMfmaDqSlices, dq_parts, gx, w.gemm_part, x_tail, st, &paired)) return rc;
+        return launch_gemm_bwd_pair(M.dq, gq, M.dx, gx, w.gemm_part, x_tail, st);
     }
-    if (paired) return MKB_OK;
     {
         ProfScope ps(MKB_PROF_POOL_BWD_Q, st);
-        // a K split of this product leaves its partials in the dQ slices: the row backward sums them (it does so for the
-        // VALU route's position blocks anyway) instead of a reduction launch in between (DistMult: 6.5 us)
-        if (int rc = launch_gemm<true, false, GEMM_STORE>(gq, st, w.gemm_part, nullptr, 0, kMfmaDqSlices, dq_parts)) return rc;
+        if (int rc = launch_gemm<true, false, GEMM_STORE>(M.dq, gq, st, w.gemm_part)) return rc;
     }
     ProfScope ps(MKB_PROF_POOL_BWD_X, st);
-    return launch_gemm<false, false, GEMM_ATOMIC_ROWS>(gx, st, w.gemm_part, x_tail, x_tail ? 500 : 0);
+    return launch_gemm<false, false, GEMM_ATOMIC_ROWS>(M.dx, gx, st, w.gemm_part, x_tail);
 }
 
-// dq_parts (out): how many [B, De] partial products the dQ buffer holds (the consumer -- row / query backward -- adds them up)
+// leaves L.dq_parts [B, De] partial products in the dQ buffer (the consumer -- row / query backward -- adds them up)
 static int pooled_bwd(const mkb_tables_t *tb, bool head, const mkb_grads_t *gr, const int64_t *pool, const uint16_t *cnt, int64_t B,
-                      int64_t P, const Workspace &w, const PoolPlan &L, hipStream_t st, DxReduce *dx_out, GemmTail *x_tail,
-                      int *dq_parts) {
-    *dq_parts = L.dq_parts;
+                      int64_t P, const Workspace &w, const PoolPlan &L, hipStream_t st, DxReduce *dx_out, GemmTail *x_tail) {
     if (x_tail) x_tail->kind = 0;
-    if (L.matrix()) return matrix_bwd(tb, gr, pool, B, P, w, st, x_tail, dq_parts);
+    if (L.matrix()) return matrix_bwd(tb, gr, pool, B, w, L.products, st, x_tail);
     PoolArgs A = make_args(tb, pool, cnt, B, P, w, L, /*bwd=*/true);
     A.g_modulus = gr->g_modulus;
     A.g_ent = gr->g_ent;
@@ -610,14 +635,14 @@ static int pooled_bwd(const mkb_tables_t *tb, bool head, const mkb_grads_t *gr, 
 }
 
 static int check_pool_call(const mkb_tables_t *tb, const int64_t *sample, const int64_t *pool, const uint16_t *cnt, int64_t B,
-                           int64_t K, int mode, const void *ws, PoolPlan &L) {
+                           int64_t K, int mode, const void *ws, PoolFolds folds, PoolPlan &L) {
     if (int rc = validate_tables(tb)) return rc;
     MKB_REQUIRE(sample && pool && cnt && ws, "null pointer");
     MKB_REQUIRE(B > 0 && K > 0 && B <= INT32_MAX, "bad B / K");
     MKB_REQUIRE(tb->n_entity <= INT32_MAX, "n_entity too large");
     MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "the pooled path needs head-batch or tail-batch");
     MKB_REQUIRE((((uintptr_t)ws) & 255) == 0, "workspace must be 256-byte aligned");
-    if (2 * K > kMaxP || !plan_pool(tb, B, 2 * K, switches_from_env(), L))
+    if (2 * K > kMaxP || !plan_pool(tb, B, 2 * K, switches_from_env(), folds, L))
         return set_error(MKB_ERR_UNSUPPORTED, "shape not covered by the pooled kernels (size <= 1024, rows <= 4096 units, "
                                               "even dims above 256 units); use the general path");
     return MKB_OK;
@@ -629,17 +654,19 @@ using namespace mkb;
 
 extern "C" int mkb_pool_supported(const mkb_tables_t *tb, int64_t B, int64_t K) {
     PoolPlan L;
-    return tb && B > 0 && K > 0 && 2 * K <= kMaxP && tb->n_entity <= INT32_MAX && plan_pool(tb, B, 2 * K, switches_from_env(), L);
+    return tb && B > 0 && K > 0 && 2 * K <= kMaxP && tb->n_entity <= INT32_MAX && plan_pool(tb, B, 2 * K, switches_from_env(), PoolFolds{}, L);
 }
 
 extern "C" int64_t mkb_pool_step_workspace_bytes(const mkb_tables_t *tb, int64_t B, int64_t K) {
     if (!tb || B <= 0 || K <= 0) return 0;
     PoolPlan L;
-    if (!plan_pool(tb, B, 2 * K, switches_from_env(), L)) return 0;  // (the shape must be supported as the environment stands)
+    if (!plan_pool(tb, B, 2 * K, switches_from_env(), PoolFolds{}, L)) return 0;  // (the shape must be supported as the environment stands)
     int64_t best = 0;
+    // (the matrix route's layout is the same under every setting of the three GEMM switches and whatever the call folds: its
+    // buffers are sized by the bounds of its plans, PoolPlan::gemm_part and kMfmaDqSlices)
     for (bool no_mfma : {false, true})
         for (PoolSwitches::Dense dense : {PoolSwitches::kDenseOff, PoolSwitches::kDenseOn})
-            if (plan_pool(tb, B, 2 * K, PoolSwitches{no_mfma, dense}, L))
+            if (plan_pool(tb, B, 2 * K, PoolSwitches{no_mfma, dense, GemmSwitches{}}, PoolFolds{}, L))
                 best = std::max(best, (int64_t)carve(nullptr, B, 2 * K, tb->entity_dim, L).bytes);
     return best;
 }
@@ -647,7 +674,7 @@ extern "C" int64_t mkb_pool_step_workspace_bytes(const mkb_tables_t *tb, int64_t
 extern "C" int mkb_pool_score_fwd(const mkb_tables_t *tb, const int64_t *sample, const int64_t *pool, const uint16_t *cnt,
                                   int64_t B, int64_t K, int mode, float *pool_score, void *ws, void *stream) {
     PoolPlan L;
-    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
+    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, PoolFolds{}, L)) return rc;
     MKB_REQUIRE(pool_score != nullptr, "pool_score is null");
     const Workspace w = carve(ws, B, 2 * K, tb->entity_dim, L);
     hipStream_t st = (hipStream_t)stream;
@@ -659,7 +686,7 @@ extern "C" int mkb_pool_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr,
                                   const uint16_t *cnt, int64_t B, int64_t K, int mode, const float *dpool_score, void *ws,
                                   void *stream) {
     PoolPlan L;
-    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
+    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, PoolFolds{}, L)) return rc;
     MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && dpool_score, "null pointer");
     MKB_REQUIRE(tb->model != MKB_PROTATE || gr->g_modulus, "pRotatE needs g_modulus");
     const int64_t P = 2 * K;
@@ -673,11 +700,10 @@ extern "C" int mkb_pool_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr,
     hipLaunchKernelGGL(masked_copy_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, dpool_score, cnt, w.G,
                        B * P, n_pad, P, L.seeds());
     MKB_LAUNCH_CHECK();
-    int dq_parts = 0;
-    if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, nullptr, nullptr, &dq_parts)) return rc;
+    if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, nullptr, nullptr)) return rc;
     // chain dQ into the fixed operands' gradient rows
     RowArgs ra{tb->ent, tb->rel, sample, w.dQ, gr->g_ent, gr->g_rel, tb->entity_dim, tb->relation_dim, tb->hidden_dim,
-               (int)B, dq_parts, tb->phase_div};
+               (int)B, L.dq_parts, tb->phase_div};
     return launch_query_bwd(tb, head, ra, st);
 }
 
@@ -688,7 +714,8 @@ extern "C" int mkb_pool_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr,
 static int pool_step_fwd(const mkb_tables_t *tb, const int64_t *sample, const int64_t *pool, const uint16_t *cnt, int64_t B,
                          int64_t K, int mode, float *pos_score, float *pool_score, void *ws, void *stream, GemmTail *s_tail) {
     PoolPlan L;
-    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
+    if (s_tail && 2 * K > 64 * 16) s_tail = nullptr;  // (the loss rows reduce the scores of pools of <= 1024 positions)
+    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, PoolFolds{s_tail != nullptr, true}, L)) return rc;
     MKB_REQUIRE(pos_score && pool_score, "null pointer");
     const int64_t P = 2 * K;
     const Workspace w = carve(ws, B, P, tb->entity_dim, L);
@@ -705,7 +732,7 @@ static int pool_step_fwd(const mkb_tables_t *tb, const int64_t *sample, const in
         if (int rc = launch_row_fwd(tb, head, ra, st)) return rc;
     }
     // negative pass over the shared pool (pipeline.py:230-232)
-    return pooled_fwd(tb, head, sample, pool, cnt, B, P, pool_score, w, L, st, (s_tail && P <= 64 * 16) ? s_tail : nullptr, ra.occ);
+    return pooled_fwd(tb, head, sample, pool, cnt, B, P, pool_score, w, L, st, s_tail, ra.occ);
 }
 
 // s_tail: scores still in split-K partials (from pool_step_fwd); fold: the scattered product's tail rides the row backward
@@ -714,7 +741,7 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
                          const float *weight_sum, const float *pos_score, float *pool_score, float *loss, void *ws,
                          void *stream, const GemmTail *s_tail) {
     PoolPlan L;
-    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, L)) return rc;
+    if (int rc = check_pool_call(tb, sample, pool, cnt, B, K, mode, ws, PoolFolds{s_tail != nullptr, true}, L)) return rc;
     MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && weight && pos_score && pool_score && loss, "null pointer");
     MKB_REQUIRE(tb->model != MKB_PROTATE || gr->g_modulus, "pRotatE needs g_modulus");
     const int64_t P = 2 * K;
@@ -736,7 +763,7 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
     ra.loss_scal = weight_sum ? weight_sum : w.scratch;
     ra.loss_out = loss;
     // backward (pipeline.py:236): pooled negatives, then the positive pair and both query chains in one row kernel
-    if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, L.single_pass() ? &ra.dx : nullptr, &ra.sc, &ra.nslices)) return rc;
+    if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, L.single_pass() ? &ra.dx : nullptr, &ra.sc)) return rc;
     ra.dx.occ = ra.occ;  // (the dx reduction riding this launch writes pool rows: exclusive ones without atomics)
     ra.grads_clear = gr->rows_clear ? 1 : 0;
     ra.dx.clear = ra.grads_clear;

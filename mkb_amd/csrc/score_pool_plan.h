@@ -1,6 +1,8 @@
 // Launch plan of the pooled scoring path: which kernel runs for a table shape, with which grid, over which workspace
-// layout.  score_pool.hip fills a PoolPlan (plan_pool) and carves the workspace from it; score_pool_launch.h launches from it.
+// layout.  score_pool.hip fills a PoolPlan (plan_pool) and carves the workspace from it; score_pool_launch.h launches the VALU
+// routes from it, gemm_mfma.h the matrix route's three products (their GemmPlans, gemm_plan.h, are part of the plan).
 #pragma once
+#include "gemm_plan.h"
 #include "score_pool_kernels.h"
 
 namespace mkb {
@@ -11,7 +13,13 @@ struct PoolSwitches {
     enum Dense { kDenseDefault, kDenseOff, kDenseOn };
     bool no_mfma;  // MKB_POOL_NO_MFMA=1: the bilinear models keep the VALU kernels (the tests' independent route)
     Dense dense;   // MKB_POOL_DENSE: the dense pass of the single-pass backward (default: on where the model has the form)
+    GemmSwitches gemm;  // MKB_GEMM_NO128 / MKB_GEMM_NO_PAIR / MKB_GEMM_BF16X3: the matrix route's products (gemm_plan.h)
 };
+
+// Which tails of the matrix route's products the call folds into its next launch: the split-K sum of the scores into the loss
+// rows (mkb_pool_step), the scattered add of dX into the row backward (mkb_pool_step and mkb_pool_step_bwd).  A folding product
+// asks for twice the workgroups, so its K split -- not the workspace layout -- depends on these.
+struct PoolFolds { bool s, x; };
 
 enum class FwdRoute {
     Matrix,   // S = Q . ent[pool]^T on the matrix cores (gemm_mfma.h; ComplEx / DistMult)
@@ -87,6 +95,7 @@ struct FwdRows { int kpt, nw, slices; };             // units per lane (it amort
 struct FwdTile { int kpt, kd, ks, fringe_slices; };  // dense prefix [0, kd) in ks dim splits, the fringe's position slices (score_pool_tile.h)
 struct BwdWave { int kpt, chunks, slices; };         // units per lane, dim chunks, position slices
 struct BwdTwoPass { int q_slices, x_slices; };       // dQ slices of the dq pass, row slices of the dx pass
+struct BwdMatrix { GemmPlan dq, dx; bool pair; };    // dQ = G . ent[pool] into <= kMfmaDqSlices slices, dX = G^T . Q scattered; pair: ONE launch
 
 struct PoolPlan {
     // row kernels
@@ -97,13 +106,17 @@ struct PoolPlan {
 
     FwdRoute fwd;
     union {
-        FwdRows rows;  // RowTile
-        FwdTile tile;  // Tile
+        GemmPlan gemm;  // Matrix
+        FwdRows rows;   // RowTile
+        FwdTile tile;   // Tile
     };
 
     BwdRoute bwd;
-    int dq_parts;  // [B, De] partial buffers of dQ the row / query backward sums (Matrix: room for the product's K split)
+    int dq_parts;  // [B, De] partial buffers of dQ the row / query backward sums (Matrix: the slices of the dQ plan)
+    // Matrix: floats of split-K partials the workspace holds -- the most any product of the route writes, whatever the call folds
+    size_t gemm_part;
     union {
+        BwdMatrix products;  // Matrix
         Bwd1Layout single;  // SinglePass (dq_parts = its position blocks)
         BwdWave wave;       // Wave (dq_parts = its position slices)
         BwdTwoPass two;     // TwoPass (dq_parts = its dQ slices)

@@ -83,6 +83,27 @@ def test_matrix_route_equals_the_valu_route_on_every_row(name, flag):
         np.testing.assert_allclose(r1, r0, rtol=0, atol=3e-6 * np.abs(r0).max())
 
 
+@pytest.mark.parametrize("name,hidden,B,K,no_pair", [
+    ("ComplEx", 500, 8, 256, False),      # 8 batch rows: dX takes the 128-row tiles unsplit, 512 x 1000 floats of partials
+    ("ComplEx", 500, 384, 512, False),    # the pair launch with dX split four ways: 4 x 1024 x 1000 floats of partials
+    ("ComplEx", 1000, 256, 1024, True),   # two launches, dX split two ways: 2 x 2048 x 2000 floats of partials
+])
+def test_matrix_route_with_fewer_rows_than_pool_positions_equals_the_valu_route(name, hidden, B, K, no_pair, monkeypatch):
+    """B < 2 K: the scattered product dX = G^T . Q has more rows (pool positions) than the batch, and its split-K partials
+    [ks, 2 K, De] are more than the 8 * B * max(2 K, De) floats the partial buffer used to be: it is sized from the products' plans
+    (PoolPlan::gemm_part; tools/gemm_plan_room_check.cpp asserts the room on the host).  Against the VALU kernels, which are
+    independent code and have no partial buffer, with the tolerances of test_matrix_route_equals_the_valu_route_on_every_row."""
+    for mode in ("head-batch", "tail-batch"):
+        if no_pair:
+            monkeypatch.setenv("MKB_GEMM_NO_PAIR", "1")
+        l1, e1, r1 = _grads(name, hidden, B, K, "1", mode)
+        monkeypatch.delenv("MKB_GEMM_NO_PAIR", raising=False)
+        l0, e0, r0 = _grads(name, hidden, B, K, "1", mode, no_mfma=True)
+        assert abs(l1 - l0) <= 1e-6 * max(1.0, abs(l0))
+        np.testing.assert_allclose(e1, e0, rtol=0, atol=3e-6 * np.abs(e0).max())
+        np.testing.assert_allclose(r1, r0, rtol=0, atol=3e-6 * np.abs(r0).max())
+
+
 def test_training_with_either_matrix_form_reaches_the_same_model():
     """40 fused steps of ComplEx hidden 1000 (FB15k-237, K 256, B 1024) with the row-lazy optimizer, once with each form of the
     tile kernel: the same loss trajectory and the same tables (Adam divides a gradient by its own running magnitude, so the
