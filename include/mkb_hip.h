@@ -544,6 +544,30 @@ int64_t mkb_cand_score_bwd_workspace_bytes(const mkb_tables_t *tb, int64_t B, in
 int mkb_cand_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const int64_t *cand, int64_t B,
                        int64_t M, int part, const float *dscore, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- embedding regularisers: Lp (p = 2, 3) / N3 on the rows of a batch's positive triples ----------------------------
+ * No reference counterpart (a torch expression on gathered rows in user code); mkb_amd/csrc/reg_rows.hip.  New symbols under
+ * ABI 8: the version is not bumped (symbols are only added).
+ *   reg = sum_i (w_i / W) [lambda_ent (f(E[h_i]) + f(E[t_i])) + lambda_rel f(R[r_i])] over sample [B, 3]; weight [B] or null
+ *   (all ones), W = sum of weight (B when null), or weight_sum[0] when given (the rows are a shard, as for the loss calls).
+ *   f(x) = sum_k |x_k|^p; for a table whose rows the model reads as [re | im] halves (ComplEx: both tables, RotatE: the entity
+ *   table) f(x) = sum_{k < hidden_dim} (re_k^2 + im_k^2)^(p / 2), the N3 of complex models; for p = 2 the two are the same sum.
+ *   pRotatE's modulus takes no part.  The gradient of a real entry is p |x|^(p - 1) sign(x), of a pair p m^(p - 2) (re, im) with
+ *   m = sqrt(re^2 + im^2): exactly 0 at m = 0.
+ *   value [1] out (null: gradient only) = reg; gr (null: value only): scale[0] (device; null = 1) times the gradient of reg is
+ *   ADDED to g_ent / g_rel (g_modulus and rows_clear are not used).  A table whose lambda is 0 is neither read nor written (its gradient buffer may be null).
+ *   The occurrences of a row collapse into one coefficient: the 3 B occurrences are radix-sorted by row, each distinct row is
+ *   read once and its gradient row written by a single workgroup with plain stores; fixed-order sums, no float atomics: two runs
+ *   give the same bits in the value and in both gradient tables.  An id outside its table counts as the nearest row.
+ *   ws: the workspace function's byte count, 256-byte aligned, caller-owned; nothing is allocated in a call.
+ *   B == 0 is a valid call that launches no kernel and writes value = 0 (ws may be null).  p other than 2 or 3, a negative or
+ *   non-finite lambda, null tb or sample, value and gr both null, B < 0, B >= 2^30 (the single int32 sort: 3 B and n_entity +
+ *   n_relation must stay below 2^31), a short or misaligned workspace, an unknown model -> MKB_ERR_INVALID before any launch.
+ *   The workspace function returns 0 for B <= 0, null tables or a B that the call refuses. */
+int64_t mkb_reg_rows_workspace_bytes(const mkb_tables_t *tb, int64_t B);
+int mkb_reg_rows(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int p,
+                 float lambda_ent, float lambda_rel, const float *weight_sum, const float *scale, float *value, void *ws,
+                 int64_t ws_bytes, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

@@ -10,6 +10,7 @@ Same public names as the reference for the path it replaces::
 * ``compose.Pipeline``                                 same training loop; fused step when it can
 * ``evaluation.Evaluation``                            filtered ranking on device
 * ``datasets``                                         host-side batch producer (same torch DataLoader order)
+* ``regularizers.{Lp,N3,L2}``                           Lp / N3 penalty on the batch's rows; keeps row-lazy Adam
 * ``distillation.{Distillation,KdmkbModel}`` + ``losses.KlDivergence``   second consumer of the scoring kernels
 * ``table_rows`` / ``parallel``                        multi-GPU partitionings (row-sharded table, dims, batch rows)
 
@@ -19,6 +20,6 @@ library raises at first use.
 """
 __version__ = "0.1.0"
 
-from . import compose, datasets, distillation, evaluation, fused, losses, models, optim, sampling, table_rows, utils  # noqa: F401
+from . import compose, datasets, distillation, evaluation, fused, losses, models, optim, regularizers, sampling, table_rows, utils  # noqa: F401
 
-__all__ = ["compose", "datasets", "distillation", "evaluation", "fused", "losses", "models", "optim", "sampling", "table_rows", "utils"]
+__all__ = ["compose", "datasets", "distillation", "evaluation", "fused", "losses", "models", "optim", "regularizers", "sampling", "table_rows", "utils"]

@@ -159,6 +159,9 @@ _SIGNATURES = {
     "mkb_cand_score_bwd_workspace_bytes": (c_int64, [POINTER(Tables), c_int64, c_int64, c_int]),
     "mkb_cand_score_bwd": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
                                    c_int64, c_void_p]),
+    "mkb_reg_rows_workspace_bytes": (c_int64, [POINTER(Tables), c_int64]),
+    "mkb_reg_rows": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

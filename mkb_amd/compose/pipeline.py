@@ -92,6 +92,9 @@ class Pipeline:
         # the device) instead of the dataset's two host DataLoaders.  Same batch format, alternation and coverage; the
         # shuffle ORDER is a seeded device randperm, not the reference's CPU RandomSampler order, hence not the default.
         self.device_batches = False
+        # Opt-in: a ``mkb_amd.regularizers.Lp`` (``N3``, ``L2``) on the positive triples of every batch.  The fused steps take it
+        # as one more library call; the explicit sequence adds ``regularizer(model, sample, weight)`` to the loss.
+        self.regularizer = None
 
     # ------------------------------------------------------------------ one epoch of steps (pipeline.py:206-244)
     def _fused_step_for(self, model, dataset, sampling, optimizer, loss):
@@ -110,8 +113,8 @@ class Pipeline:
             #                              the touched rows may wait for the next catch-up launch (mkb_amd/optim.py)
             self._borrowed.append("defer_step")
         if type(loss) in _POOLED_LOSSES:
-            return PooledLossStep(model, loss)
-        return FusedTrainStep(model, loss.alpha)
+            return PooledLossStep(model, loss, regularizer=self.regularizer)
+        return FusedTrainStep(model, loss.alpha, regularizer=self.regularizer)
 
     def _give_back(self, optimizer):
         """Deferral is scoped to learn(): a pending step lives in the table's gradient rows, and the user's own code after
@@ -150,6 +153,8 @@ class Pipeline:
                 positive_score = model(sample)
                 negatives = sampling.generate(sample=sample, mode=mode).to(self.device)
                 error = loss(positive_score, model(sample=sample, negative_sample=negatives, mode=mode), weight)
+                if self.regularizer is not None:
+                    error = error + self.regularizer(model, sample, weight)
                 error.backward()
             optimizer.step()
             optimizer.zero_grad()

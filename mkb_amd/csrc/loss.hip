@@ -19,13 +19,6 @@
 
 namespace mkb {
 
-// scal[0] = W
-__global__ __launch_bounds__(256) void weight_sum_kernel(const float *__restrict__ w, int B, float *__restrict__ scal) {
-    __shared__ float red[4];
-    const float acc = weight_sum_block(w, B, red);
-    if (threadIdx.x == 0) scal[0] = acc;
-}
-
 // one wave per row; rowpart[i] = w_i * (ps_i + ns_i).
 // Columns are handled 64 at a time (column group t: lane l owns column l + 64 t).  Rows of up to kStageCols columns are read
 // from global memory ONCE and staged in LDS -- scores in s_v, multiplicities (then softmax numerators) in s_e, both

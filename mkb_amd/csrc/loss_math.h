@@ -49,6 +49,14 @@ __device__ __forceinline__ float weight_sum_block(const float *__restrict__ w, i
     return block_sum_256(acc, red);
 }
 
+// scal[0] = W by one 256-lane workgroup: the launch in front of a kernel whose workgroups are too many to re-reduce W each
+// (ns_loss.hip, reg_rows.hip)
+static __global__ __launch_bounds__(256) void weight_sum_kernel(const float *__restrict__ w, int B, float *__restrict__ scal) {
+    __shared__ float red[4];
+    const float acc = weight_sum_block(w, B, red);
+    if (threadIdx.x == 0) scal[0] = acc;
+}
+
 // exp / log on the hardware transcendental unit (v_exp_f32 / v_log_f32, ~1 ulp of the base-2 function): the arguments
 // here are scores of magnitude <= ~20, so exp's relative error stays ~1e-6 and log1p's absolute error ~1e-7 -- two
 // orders below the 1e-4 / 1e-5 parity tolerances -- at a tenth of the instructions of the correctly rounded libm forms.

@@ -25,12 +25,6 @@ namespace mkb {
 constexpr int kNsStageCols = 1024;
 constexpr int kNsRows = 4;  // rows (waves) per workgroup
 
-__global__ __launch_bounds__(256) void ns_weight_sum_kernel(const float *__restrict__ w, int B, float *__restrict__ scal) {
-    __shared__ float red[4];
-    const float acc = weight_sum_block(w, B, red);
-    if (threadIdx.x == 0) scal[0] = acc;
-}
-
 template <int KIND>
 __global__ __launch_bounds__(256) void ns_loss_rows_kernel(const float *__restrict__ pos, const float *__restrict__ neg,
                                                            const float *__restrict__ w, const uint16_t *__restrict__ cnt, int B,
@@ -170,7 +164,7 @@ extern "C" int mkb_ns_loss(int kind, const float *pos, const float *neg, const f
     const float *scal_in = weight_sum;  // W of the whole (sharded) batch when the caller supplies it
     ProfScope ps(MKB_PROF_LOSS, st);
     if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one extra launch
-        hipLaunchKernelGGL(ns_weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
+        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
         scal_in = scal;
     }
     switch (kind) {

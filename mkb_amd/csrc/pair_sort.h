@@ -19,4 +19,20 @@ int pair_sort_plan(int64_t n_table, int64_t n_pairs, PairSortPlan &plan);
 int pair_sort_launch(const int64_t *cand, int64_t n_pairs, int64_t n_table, void *scratch, const PairSortPlan &plan, hipStream_t st,
                      const int **sorted_cand, const int **sorted_pair);
 
+// The same sort over a key list made of up to kPairKeySegs segments laid end to end (reg_rows.hip: the heads, the tails and the
+// relations of a batch in one sort): pair first + j of a segment has the key base + table_row(ids[j * stride], n_table).  The
+// plan is pair_sort_plan(the largest key + 1, the segments' total n); the sort is stable, so equal keys keep their pair order.
+constexpr int kPairKeySegs = 3;
+struct PairKeySeg {
+    const int64_t *ids;
+    int64_t stride, n, n_table;
+    int base;
+};
+struct PairKeySegs {
+    PairKeySeg seg[kPairKeySegs];
+    int n_segs;
+};
+int pair_sort_launch_segs(const PairKeySegs &segs, void *scratch, const PairSortPlan &plan, hipStream_t st, const int **sorted_key,
+                          const int **sorted_pair);
+
 }  // namespace mkb

@@ -28,9 +28,15 @@ def _workspace(model, B, K, slot=0):
     tests/test_gpu_rows_loopback.py; a user training two models side by side) must not share it -- until round 6 they did."""
     dev = model.entity_embedding.device
     key = (dev, _hip.stream_ptr(dev).value, model.name, model.entity_dim, model.n_entity, model.n_relation, B, K, slot)  # (the size depends on the last six)
+    return cached_workspace(key, dev, lambda: _hip.lib().mkb_pool_step_workspace_bytes(model._tables(), B, K))
+
+
+def cached_workspace(key, dev, size):
+    """The cache behind ``_workspace``, for any library call whose scratch depends on ``key`` alone (``key[:2]``: device and
+    stream; ``size() -> bytes``, asked once per key): the pooled kernels' and the regulariser's (``mkb_amd.regularizers``)."""
     ws = _workspaces.get(key)
     if ws is None:
-        n = _hip.lib().mkb_pool_step_workspace_bytes(model._tables(), B, K)
+        n = size()
         guard = _GUARD_BYTES if _guard_on() else 0
         buf = _hip.aligned_bytes(n + guard, dev)
         ws = buf[:n]
@@ -139,10 +145,16 @@ def sampled_step(step, sample, weight, sampler, mode, **kwargs):
 class FusedTrainStep:
     """``loss = step(sample, weight, negative_sample, mode)``: fills ``param.grad`` (dense, accumulated) and returns
     the loss as a 0-dim device tensor.  ``positive_score`` [B,1] and ``negative_score`` [B,size] of the last call
-    stay available for inspection."""
+    stay available for inspection.
 
-    def __init__(self, model, alpha):
-        self.model, self.alpha = model, float(alpha)
+    ``regularizer``: a ``mkb_amd.regularizers.Lp`` (``N3``, ``L2``) whose term on the batch's positive triples joins the step:
+    one more library call (``mkb_reg_rows``, value and gradient in one launch sequence) behind ``mkb_pool_step`` -- which may
+    STORE the batch's gradient rows (``rows_clear``), so the regulariser adds onto them afterwards.  Its rows are the batch's heads
+    and tails, which the row-lazy protocol has already made current and marked.  The loss returned is loss + regulariser;
+    ``regularization`` keeps the term alone."""
+
+    def __init__(self, model, alpha, regularizer=None):
+        self.model, self.alpha, self.regularizer, self.regularization = model, float(alpha), regularizer, None
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
         return sampled_step(self, sample, weight, sampler, mode, weight_sum=weight_sum)
@@ -175,11 +187,19 @@ class FusedTrainStep:
                                                 _hip.ptr(pos), _hip.ptr(S),
                                                 _hip.ptr(loss), _hip.ptr(ws), _hip.stream_ptr()), "mkb_pool_step")
         self.positive_score, self._S, self._info = pos, S, info
-        return loss.reshape(())
+        return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)
 
     @property
     def negative_score(self):
         return self._S.gather(1, self._info.pos.long())
+
+
+def _with_regularizer(step, loss, sample, weight, weight_sum, gr):
+    """loss + the step's regulariser term, whose gradient is added to the buffers ``gr`` the step has just written."""
+    if step.regularizer is None:
+        return loss
+    step.regularization = step.regularizer.launch(step.model, sample, weight, weight_sum, grads=gr)
+    return loss + step.regularization
 
 
 class PooledLossStep:
@@ -190,12 +210,13 @@ class PooledLossStep:
     Five library calls, no autograd: positive scores (``mkb_score_fwd``), pool scores (``mkb_pool_score_fwd``), ``mkb_ns_loss``
     over the ``[B, 2 size]`` pool block with the sampler's multiplicities, then ``mkb_pool_score_bwd`` on its seeds and the
     positive pair's ``mkb_score_bwd``.  Against the explicit autograd sequence this drops the gather of the ``[B, size]`` view,
-    the scatter of its gradient back onto pool positions and the dense zero-filled buffers autograd adds into ``.grad``."""
+    the scatter of its gradient back onto pool positions and the dense zero-filled buffers autograd adds into ``.grad``.
+    ``regularizer``: as for ``FusedTrainStep`` (a sixth call, ``mkb_reg_rows``, behind the two backward calls)."""
 
-    def __init__(self, model, loss):
+    def __init__(self, model, loss, regularizer=None):
         if getattr(loss, "kind", None) not in (_hip.LOSS_MARGIN, _hip.LOSS_PAIR_LOGISTIC, _hip.LOSS_SOFTMAX):
             raise TypeError("PooledLossStep takes losses.MarginRanking, losses.PairwiseLogistic or losses.CrossEntropy")
-        self.model, self.loss = model, loss
+        self.model, self.loss, self.regularizer, self.regularization = model, loss, regularizer, None
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
         return sampled_step(self, sample, weight, sampler, mode, weight_sum=weight_sum)
@@ -245,7 +266,7 @@ class PooledLossStep:
         if gr.g_modulus:
             m.modulus.grad += mod_parts[0] + mod_parts[1]
         self.positive_score, self._S, self._info = pos, S, info
-        return loss.reshape(())
+        return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)
 
     @property
     def negative_score(self):

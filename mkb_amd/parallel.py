@@ -221,8 +221,11 @@ class DimShardedStep:
     all-reduce of one part's scores runs on RCCL's stream while the other part's forward / backward kernels run:
     [fwd 0][fwd 1 | all-reduce 0][bwd 0 | all-reduce 1][bwd 1].  The loss normaliser W is the whole batch's."""
 
-    def __init__(self, local_model, alpha, group=None, micro_batches=None):
+    def __init__(self, local_model, alpha, group=None, micro_batches=None, regularizer=None):
         from . import _hip, fused
+
+        if regularizer is not None:  # (a row's penalty needs all of its dimensions when the halves are paired)
+            raise NotImplementedError("DimShardedStep does not take a regularizer")
 
         self._hip, self._fused = _hip, fused
         self.model, self.alpha, self.group = local_model, float(alpha), group

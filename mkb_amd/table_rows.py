@@ -467,7 +467,9 @@ class TableRowShardedStep:
     position p."""
 
     def __init__(self, table, relation, alpha, model_cls=None, hidden_dim=None, gamma=None, group=None, compute=None,
-                 modulus=None, comm=None):
+                 modulus=None, comm=None, regularizer=None):
+        if regularizer is not None:  # (the step runs on a compact table: the occurrences would have to be re-addressed)
+            raise NotImplementedError("TableRowShardedStep does not take a regularizer")
         self.table, self.relation, self.alpha, self.group = table, relation, float(alpha), group
         self.world, self.ops = table.world, table.ops
         self.compute = compute

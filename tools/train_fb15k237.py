@@ -2,11 +2,12 @@
 FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamma=9, Adam.
 
     python tools/train_fb15k237.py [--epochs 200] [--lr 5e-5] [--eval-every 50] [--model RotatE]
-                                   [--loss adversarial|margin|pairwise|softmax]
+                                   [--loss adversarial|margin|pairwise|softmax] [--reg none|l2|n3] [--reg-weight 1e-3]
 
 --loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
 --alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
-PooledLossStep.
+PooledLossStep.  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
+handed to the step.
 
 Uses the public mkb_amd API only (models / sampling / losses / compose.Pipeline-equivalent loop / evaluation) plus
 the device batch producer.  Prints one JSON line per evaluation."""
@@ -18,7 +19,7 @@ import time
 import torch
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
-from mkb_amd import datasets, evaluation, losses, models, optim, sampling  # noqa: E402
+from mkb_amd import datasets, evaluation, losses, models, optim, regularizers, sampling  # noqa: E402
 from mkb_amd.fused import FusedTrainStep, PooledLossStep  # noqa: E402
 
 
@@ -36,6 +37,8 @@ def main():
     ap.add_argument("--dataset", default="Fb15k237")
     ap.add_argument("--loss", default="adversarial", choices=["adversarial", "margin", "pairwise", "softmax"])
     ap.add_argument("--temperature", type=float, default=1.0, help="--loss softmax")
+    ap.add_argument("--reg", default="none", choices=["none", "l2", "n3"])
+    ap.add_argument("--reg-weight", type=float, default=1e-3, help="--reg l2 / n3")
     ap.add_argument("--no-defer", action="store_true", help="apply the optimizer step at once (one more launch per step)")
     args = ap.parse_args()
 
@@ -48,12 +51,14 @@ def main():
                                         relations=ds.relations, seed=42)
     opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=sampler,
                      defer_step=not args.no_defer)  # gradients are cleared through opt.zero_grad() only: the step may wait
+    reg = {"none": lambda: None, "l2": lambda: regularizers.L2(args.reg_weight), "n3": lambda: regularizers.N3(args.reg_weight)}[args.reg]()
     if args.loss == "adversarial":
-        step = FusedTrainStep(model, args.alpha)
+        step = FusedTrainStep(model, args.alpha, regularizer=reg)
     else:
         step = PooledLossStep(model, {"margin": lambda: losses.MarginRanking(margin=args.gamma, alpha=args.alpha),
                                       "pairwise": lambda: losses.PairwiseLogistic(margin=0.0, alpha=args.alpha),
-                                      "softmax": lambda: losses.CrossEntropy(temperature=args.temperature)}[args.loss]())
+                                      "softmax": lambda: losses.CrossEntropy(temperature=args.temperature)}[args.loss](),
+                              regularizer=reg)
     ev = evaluation.Evaluation(true_triples=ds.true_triples, entities=ds.entities, relations=ds.relations,
                                batch_size=1024, device="cuda", num_workers=0)
     n_steps, t_train = 0, 0.0
