@@ -269,6 +269,28 @@ int mkb_adam_rows_advance_generate(float *param, float *grad, float *exp_avg, fl
                                    int mode, int64_t *neg, int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched,
                                    void *stream);
 
+/* ---- row-sparse Adagrad (mkb_amd/csrc/adagrad.hip) ----------------------------------------------------------------------
+ * == torch.optim.Adagrad(lr, lr_decay, eps, weight_decay = 0).step() + zero_grad(), one launch per optimizer step:
+ *   sum += g * g ; p -= clr * g / (sqrt(sum) + eps) ; g = 0        clr = lr / (1 + (step - 1) * lr_decay), computed by the caller
+ * An element whose g is 0 keeps its p and sum exactly, so stepping only the rows a batch wrote is dense Adagrad bit for bit:
+ * nothing is deferred, replayed or flushed.  State of a table param [n_rows, D]: sum [n_rows, D] and `last` [n_rows] int32
+ * (zero-initialised) = the last step that visited a row; step is 1-based and strictly increasing per table.
+ *   ids != null, the listed form: the rows ids[0 .. n_ids) take the step (duplicates allowed: one workgroup claims a row through
+ *     `last`; negative entries and entries >= n_rows are skipped).  n_ids == 0: no row.
+ *   ids == null && n_ids == 0, the all-rows form: every row of the table (a step whose written rows are not known).
+ *   param == null, the dense-only form: no table; n_dense > 0.
+ *   dense_host [n_dense <= 8]: small dense tensors (any alignment, any n) that take the same step, with the same clr, and have
+ *     their gradients cleared by extra workgroups of the launch.
+ *   draw_ahead: null, or a sampler whose NEXT pool draw runs as one more workgroup of this launch (as for mkb_adam_step_multi).
+ */
+typedef struct {
+    float *param, *grad, *sum; /* a small dense tensor (the relation table, pRotatE's modulus); any alignment */
+    int64_t n;                 /* elements */
+} mkb_adagrad_dense_t;
+int mkb_adagrad_step(float *param, float *grad, float *sum, int32_t *last, int64_t n_rows, int64_t D, const int64_t *ids,
+                     int64_t n_ids, int64_t step, float clr, float eps, const mkb_adagrad_dense_t *dense_host, int n_dense,
+                     mkb_sampler_t *draw_ahead, void *stream);
+
 /* ---- row-sharded entity table (several GPUs; the reference is single-process: no counterpart to cite) ----------------
  * Rank g of `world` owns the entity rows e with e % world == g, at shard index e / world (table, dense gradient and Adam
  * state alike).  mkb_amd/table_rows.py moves rows between owners and users with these three calls and torch.distributed
@@ -574,7 +596,7 @@ int mkb_reg_rows(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *s
  * each, which a sampled measurement keeps out of most steps).  mkb_profile_read synchronises, returns the number of bracketed launches and
  * their summed duration in milliseconds, and resets the counters.  kernel: 0 = pooled backward (the dq and dx passes
  * in one launch; for ComplEx / DistMult the dQ GEMM),
- * 1 = pooled forward, 2 = Adam, 3 = sampler (draw + filter), 4 = adversarial loss, 5 = general forward,
+ * 1 = pooled forward, 2 = the optimizer launches (every mkb_adam_* call and mkb_adagrad_step), 3 = sampler (draw + filter), 4 = adversarial loss, 5 = general forward,
  * 6 = general backward, 7 = pooled backward dx pass when it is launched alone (the GEMM route).  At most 8192 launches are kept between reads.
  */
 #define MKB_PROF_POOL_BWD_Q 0

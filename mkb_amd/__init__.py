@@ -11,6 +11,7 @@ Same public names as the reference for the path it replaces::
 * ``evaluation.Evaluation``                            filtered ranking on device
 * ``datasets``                                         host-side batch producer (same torch DataLoader order)
 * ``regularizers.{Lp,N3,L2}``                           Lp / N3 penalty on the batch's rows; keeps row-lazy Adam
+* ``optim.{Adam,Adagrad}``                              row-lazy Adam / row-sparse Adagrad, bit for bit the dense optimizers
 * ``distillation.{Distillation,KdmkbModel}`` + ``losses.KlDivergence``   second consumer of the scoring kernels
 * ``table_rows`` / ``parallel``                        multi-GPU partitionings (row-sharded table, dims, batch rows)
 

@@ -45,6 +45,10 @@ class AdamDense(Structure):  # mkb_adam_dense_t: a small dense tensor stepped in
                 ("n", c_int64), ("step", c_int64)]
 
 
+class AdagradDense(Structure):  # mkb_adagrad_dense_t: a small dense tensor stepped inside mkb_adagrad_step's launch
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("sum", c_void_p), ("n", c_int64)]
+
+
 class RowSeg(Structure):  # mkb_row_seg_t: rows of a table shard listed by shard index (world == 0) or global entity id
     _fields_ = [("ids", c_void_p), ("n", c_int64), ("rows", c_void_p), ("world", c_int32), ("rank", c_int32),
                 ("local_ids", c_void_p)]
@@ -105,6 +109,8 @@ _SIGNATURES = {
     "mkb_adam_rows_advance": (c_int, _ROWS_TABLE + [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64] + _ROWS_STEP
                               + [c_void_p, c_void_p]),
     "mkb_adam_rows_advance_generate": (c_int, _ROWS_TABLE + [c_int, c_int, c_void_p, c_int64] + _ROWS_STEP + _SAMPLER_TAIL),
+    "mkb_adagrad_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_float,
+                                 c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "mkb_rows_route": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
     "mkb_rows_gather": (c_int, [c_void_p, c_int64, c_int64, POINTER(RowSeg), c_int, c_void_p, c_int64, c_void_p, c_void_p,

@@ -130,11 +130,13 @@ def grad_buffers(model):
 def sampled_step(step, sample, weight, sampler, mode, **kwargs):
     """``step.sampled(...)``: ``step(sample, weight, sampler.generate(sample, mode), mode, **kwargs)`` with the sampler folded
     into the optimizer's catch-up launch when the entity table of ``step.model`` steps row-lazily (``mkb_amd.optim.Adam(lazy_rows=
-    True)``): no sampler launch, identical negatives.  The negatives of the call stay available as ``step.negative_sample``."""
+    True)``): no sampler launch, identical negatives.  An optimizer whose rows are always current (``rows_always_current``:
+    ``mkb_amd.optim.Adagrad``) has no catch-up to fold the sampler into; its own step launch has drawn the pool already, and the
+    plain ``generate`` only filters.  The negatives of the call stay available as ``step.negative_sample``."""
     ent = step.model.entity_embedding
     lazy = _links.owner(ent)
     sample = _hip.contiguous(sample, torch.int64)
-    if lazy is not None and sampler.size <= 512 and sample.is_cuda:
+    if lazy is not None and not getattr(lazy, "rows_always_current", False) and sampler.size <= 512 and sample.is_cuda:
         neg = sampler.generate_with_catch_up(sample, mode, lazy, ent)
     else:
         neg = sampler.generate(sample=sample, mode=mode)

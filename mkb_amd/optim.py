@@ -24,12 +24,25 @@ relation table) ride the next catch-up launch instead, so with ``defer_step`` th
 ``flush()``.  Contract: clear gradients through ``optimizer.zero_grad()`` only (``model.zero_grad()`` /
 ``p.grad.zero_()`` would erase a step that has not been applied yet), and let every step that reads a row-lazy table keep to
 "the protocol" below (the step classes and ``model(...)`` do): rows current before the forward pass, then their gradient, then the report.
+
+``mkb_amd.optim.Adagrad`` -- ``torch.optim.Adagrad`` (``weight_decay=0``) stepped ROW-SPARSELY, one ``mkb_adagrad_step`` launch per
+step with ``zero_grad()`` fused into it (mkb_amd/csrc/adagrad.hip).  A zero gradient moves neither Adagrad's accumulator nor the
+parameter, so stepping only the rows a batch wrote is dense Adagrad bit for bit: the rows of its tables are ALWAYS current, and
+the protocol's catch-up, flush and replay are no launches at all.
 """
 import torch
 
 from . import _hip, _links
 
-__all__ = ["Adam"]
+__all__ = ["Adam", "Adagrad"]
+
+
+def _draw_ahead_handle(sampler, device):
+    """The device handle of the sampler an optimizer carries the next draw of, or None: no sampler, none on ``device``, or one that
+    has not generated yet (the sampler creates its device state on its first ``generate()``)."""
+    if sampler is None or getattr(sampler, "_handle", None) is None or sampler._device != device:
+        return None
+    return sampler._handle
 
 
 class Adam:
@@ -230,10 +243,7 @@ class Adam:
         return None, None
 
     def _sampler_handle(self, device):
-        s = self.draw_ahead
-        if s is None or getattr(s, "_handle", None) is None or s._device != device:
-            return None  # (the sampler creates its device state on its first generate())
-        return s._handle
+        return _draw_ahead_handle(self.draw_ahead, device)
 
     def step(self):
         self.step_count += 1
@@ -369,4 +379,207 @@ class Adam:
             if "last" in st:  # row-lazy: nothing is pending, the replay constants of earlier steps are not needed again
                 st["last"].fill_(st["n"])
         self._pending_dense = None
+        self._zeroed = False
+
+
+class Adagrad:
+    """``torch.optim.Adagrad(params, lr, lr_decay, 0, initial_accumulator_value, eps)`` with the big tables (two dimensions, 4,096
+    rows or more: the rule of ``Adam(lazy_rows=True)``) stepped row-sparsely and everything else as dense riders of the same
+    launch: ``step()`` is one ``mkb_adagrad_step`` per device, gradient clearing included.
+
+    It speaks the protocol of the steps that read a row-lazily stepped table (``_links.owner(p)``) on the fact that its
+    rows are always current: making rows current launches nothing, the marks say which rows ``step()`` visits.  A step into which
+    autograd wrote as well (which rows is unknown) visits every row of that table, once: nothing is pending that could be lost, so
+    the next step is row-sparse again.  The same holds for a table with a gradient whose rows nobody reported: a writer that does
+    not report (the fused steps report entity rows only, so a relation table of 4,096 rows or more) cannot be told from no writer,
+    and the all-rows form only reads where the gradient is zero.  Like torch's, a parameter's step count advances with every
+    ``step()`` that finds a gradient on it.
+
+    ``draw_ahead``: a ``mkb_amd.sampling.NegativeSampling`` whose NEXT pool draw rides the step's launch (``compose.Pipeline``
+    lends its sampler for the length of ``learn()``); the negatives are the same, bit for bit."""
+
+    lazy_rows = True            # (compose.Pipeline lends such an optimizer its sampler; there is no defer_step to borrow)
+    rows_always_current = True  # fused.sampled_step: nothing to fold into the sampler's launch, plain generate() it is
+    direct_grads = True         # the backward functions of model(...) add their rows straight into .grad (_gradshare.direct)
+
+    def __init__(self, params, lr=1e-2, lr_decay=0.0, weight_decay=0.0, initial_accumulator_value=0.0, eps=1e-10, draw_ahead=None):
+        for name, value in (("learning rate", lr), ("lr_decay value", lr_decay), ("weight_decay value", weight_decay),
+                            ("initial_accumulator_value value", initial_accumulator_value), ("epsilon value", eps)):
+            if not 0.0 <= value:
+                raise ValueError(f"Invalid {name}: {value}")
+        if weight_decay != 0:
+            raise ValueError("mkb_amd.optim.Adagrad steps only the rows a batch wrote; a weight decay moves every row every step. "
+                             "The row-sparse way to get it is mkb_amd.regularizers.L2 on the batch's rows")
+        self.params = [p for p in params]
+        self.lr, self.lr_decay, self.eps = lr, lr_decay, eps
+        self.weight_decay, self.initial_accumulator_value = weight_decay, initial_accumulator_value
+        self.draw_ahead = draw_ahead
+        self.state = {}
+        self.step_count = 0
+        self._zeroed = False
+        for p in self.params:
+            if p.dim() == 2 and p.shape[0] >= 4096:
+                _links.attach(p, self)
+            st = self._state(p)
+            if "last" in st and p.grad is None and p.is_cuda:
+                p.grad = st["clean"] = torch.zeros_like(p)  # (where the row gradients land; all-zero between steps)
+
+    # ------------------------------------------------------------------ state
+    def _state(self, p):
+        # sum / n: torch's state_sum / step.  Row-sparse tables also: last [rows] int32 = the last step that visited a row (the
+        # kernel's ownership stamp), fwd_n = the step count at the last before_forward, clean = the .grad TENSOR known to be
+        # all-zero between steps (held, so that its address cannot come back as another tensor's)
+        st = self.state.get(p)
+        if st is None:
+            st = self.state[p] = {"sum": torch.full_like(p, self.initial_accumulator_value), "n": 0}
+            if _links.owner(p) is self:
+                st["last"] = torch.zeros(p.shape[0], dtype=torch.int32, device=p.device)
+        return st
+
+    def _link(self, p):
+        rec = _links.record(p)
+        return rec if rec is not None and rec.owner is self else None
+
+    # ------------------------------------------------------------------ the protocol (DESIGN.md): rows are always current
+    def ensure_current(self, p, ids):
+        pass
+
+    def catch_up(self, p, ids, upto=None):
+        pass
+
+    def flush(self, p=None):
+        pass
+
+    def before_forward(self, p, ids):
+        st = self._state(p)
+        st["fwd_n"] = st["n"]  # (rows_written(after_forward=True) at this step count marks its rows as current)
+
+    def begin_step_on(self, p, ids):
+        """In front of a fused step that adds to the rows ``ids`` of ``p.grad``: they are marked as written.  -> ``mkb_grads_t.
+        rows_clear``: EVERY row of ``p.grad`` is zero, the kernels may store.  That is known when the tensor is the one this
+        optimizer created or last cleared in full, every step since cleared the rows it was told about (each did), and nothing has
+        been marked and autograd has written nothing since the last step.  Read BEFORE the mark."""
+        st, rec = self._state(p), _links.record(p)
+        clean, g = st.get("clean"), p.grad
+        clear = bool(clean is not None and g is not None and clean.data_ptr() == g.data_ptr() and rec.touched is None and not rec.wrote)
+        rec.mark(ids)  # accumulates when several steps share one optimizer.step()
+        return clear
+
+    def rows_written(self, p, ids, after_forward=False, replace=False):
+        """Report the rows a backward pass wrote into ``p.grad`` (``_links.Link.mark``); ``after_forward``: behind autograd's back
+        (``_gradshare.direct``)."""
+        rec = _links.record(p)
+        st = self._state(p) if after_forward else None
+        rec.mark(ids, replace, after_forward and st.get("fwd_n") == st["n"])
+        if after_forward:
+            rec.rebase(p)
+
+    def catch_up_with_sampler(self, *args, **kwargs):
+        raise NotImplementedError("mkb_amd.optim.Adagrad steps single-device tables only and has no catch-up for the sampler's launch "
+                                  "to carry: use sampler.generate (fused.sampled_step does)")
+
+    def catch_up_sharded(self, *args, **kwargs):
+        raise NotImplementedError("mkb_amd.optim.Adagrad steps single-device tables only: row-sharded (mkb_amd.table_rows) and "
+                                  "data-parallel (mkb_amd.parallel) tables need mkb_amd.optim.Adam(lazy_rows=True)")
+
+    # ------------------------------------------------------------------ torch.optim-like API
+    def step(self):
+        self.step_count += 1
+        work = {}  # (device, clr) -> (tables, dense tensors): one launch carries one table, up to 8 dense tensors and ONE rate
+        for p in self.params:
+            g = p.grad
+            if g is None:
+                continue
+            _hip.require_device(p)
+            st = self._state(p)
+            if g.dtype != torch.float32 or p.dtype != torch.float32 or not p.is_contiguous():
+                raise TypeError("mkb_amd.optim.Adagrad steps contiguous float32 parameters")
+            if st["sum"].device != p.device:  # the model moved after the optimizer was built: the state follows it
+                st.update({k: v.to(p.device) for k, v in st.items() if k in ("sum", "last")})
+            if not g.is_contiguous():
+                g = p.grad = g.contiguous()
+                st.pop("clean", None)
+            ids, rec = None, self._link(p)
+            if rec is not None:
+                wrote, ids = rec.wrote, rec.take_touched()
+                if wrote or ids is None or ids.numel() == 0:
+                    # autograd accumulated into .grad in this step as well, or nobody reported a row: a writer that keeps no protocol
+                    # for this table (the fused steps report the ENTITY rows only; a relation table of 4,096 rows takes their
+                    # gradient unreported) cannot be told from no writer.  Which rows is unknown -> every row, this once: the
+                    # all-rows form reads the gradient and writes only where it is not zero.  (optim.Adam steps such a table densely.)
+                    ids = None
+                else:
+                    ids = _hip.contiguous(ids, torch.int64)
+            st["n"] += 1
+            clr = self.lr / (1.0 + (st["n"] - 1) * self.lr_decay)
+            tables, dense = work.setdefault((p.device, clr), ([], []))
+            (tables if rec is not None else dense).append((p, g, st, ids))
+        lib = _hip.lib()
+        for (dev, clr), (tables, dense) in work.items():
+            sampler = _draw_ahead_handle(self.draw_ahead, dev)  # (its next pool is drawn by one more workgroup of the first launch it meets)
+            with _hip.on_device(dev):
+                while tables or dense:
+                    group, dense = dense[:8], dense[8:]
+                    arr = None
+                    if group:
+                        arr = (_hip.AdagradDense * len(group))(*[_hip.AdagradDense(q.data_ptr(), h.data_ptr(), s["sum"].data_ptr(), q.numel())
+                                                                 for q, h, s, _ in group])
+                    if tables:
+                        p, g, st, ids = tables.pop(0)
+                        table = (_hip.ptr(p.data), _hip.ptr(g), _hip.ptr(st["sum"]), _hip.ptr(st["last"]), p.shape[0], p.shape[1],
+                                 _hip.ptr(ids), 0 if ids is None else ids.numel(), st["n"])
+                        if ids is None:
+                            st["clean"] = g  # every row was cleared
+                    else:
+                        table = (None, None, None, None, 0, 0, None, 0, group[0][2]["n"])
+                    _hip.check(lib.mkb_adagrad_step(*table, clr, self.eps, arr, len(group), sampler, _hip.stream_ptr()), "mkb_adagrad_step")
+        self._zeroed = True
+
+    def zero_grad(self, set_to_none=False):
+        """Gradients were already cleared inside ``step`` (fused); they stay allocated so the next backward accumulates in place."""
+        if self._zeroed and not set_to_none:
+            self._zeroed = False
+            return
+        for p in self.params:
+            rec, st = self._link(p), self._state(p)
+            if rec is not None:
+                rec.take_touched()  # the rows that were marked are cleared with everything else
+                st.pop("clean", None)
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.zero_()
+                    if rec is not None:
+                        st["clean"] = p.grad
+        self._zeroed = False
+
+    # ------------------------------------------------------------------ checkpointing (torch.optim-style)
+    def state_dict(self):
+        """Like ``torch.optim.Adagrad.state_dict()``: per-parameter ``step`` / ``sum`` (a clone) keyed by the parameter's position,
+        and one param group with the hyper-parameters.  Nothing is ever pending, so nothing is flushed."""
+        state = {i: {"step": torch.tensor(float(self.state[p]["n"])), "sum": self.state[p]["sum"].clone()}  # (torch keeps `step` as a tensor)
+                 for i, p in enumerate(self.params)}
+        return {"state": state, "param_groups": [{"lr": self.lr, "lr_decay": self.lr_decay, "eps": self.eps, "weight_decay": self.weight_decay,
+                                                  "initial_accumulator_value": self.initial_accumulator_value,
+                                                  "params": list(range(len(self.params)))}]}
+
+    def load_state_dict(self, sd):
+        """Restore ``state_dict()`` onto an optimizer built over the same parameters (the caller restores their tables)."""
+        g = sd["param_groups"][0]
+        self.lr, self.lr_decay, self.eps = g["lr"], g["lr_decay"], g["eps"]
+        self.initial_accumulator_value = g.get("initial_accumulator_value", self.initial_accumulator_value)
+        for i, p in enumerate(self.params):
+            saved = sd["state"].get(i, sd["state"].get(str(i)))
+            st = self._state(p)
+            if saved is None:
+                st["sum"].fill_(self.initial_accumulator_value)
+                st["n"] = 0
+            else:
+                st["sum"].copy_(saved["sum"])
+                st["n"] = int(saved["step"])
+            st.pop("fwd_n", None)
+            if "last" in st:
+                st["last"].fill_(st["n"])  # every stamp is below the next step: no row of it looks claimed
+        self.step_count = max([self.state[p]["n"] for p in self.params], default=0)  # (torch's layout has no optimizer-wide count)
         self._zeroed = False

@@ -3,11 +3,13 @@ FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamm
 
     python tools/train_fb15k237.py [--epochs 200] [--lr 5e-5] [--eval-every 50] [--model RotatE]
                                    [--loss adversarial|margin|pairwise|softmax] [--reg none|l2|n3] [--reg-weight 1e-3]
+                                   [--optimizer adam|adagrad]
 
 --loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
 --alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
 PooledLossStep.  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
-handed to the step.
+handed to the step.  --optimizer: adam (the default: row-lazy optim.Adam) or adagrad (row-sparse optim.Adagrad; the literature's
+ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.
 
 Uses the public mkb_amd API only (models / sampling / losses / compose.Pipeline-equivalent loop / evaluation) plus
 the device batch producer.  Prints one JSON line per evaluation."""
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0, help="--loss softmax")
     ap.add_argument("--reg", default="none", choices=["none", "l2", "n3"])
     ap.add_argument("--reg-weight", type=float, default=1e-3, help="--reg l2 / n3")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "adagrad"], help="optim.Adam(lazy_rows=True) or optim.Adagrad at --lr")
     ap.add_argument("--no-defer", action="store_true", help="apply the optimizer step at once (one more launch per step)")
     args = ap.parse_args()
 
@@ -49,8 +52,11 @@ def main():
                                         gamma=args.gamma).cuda()
     sampler = sampling.NegativeSampling(size=args.size, train_triples=ds.train, entities=ds.entities,
                                         relations=ds.relations, seed=42)
-    opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=sampler,
-                     defer_step=not args.no_defer)  # gradients are cleared through opt.zero_grad() only: the step may wait
+    if args.optimizer == "adagrad":  # row-sparse: nothing is deferred, --no-defer has nothing to switch off
+        opt = optim.Adagrad([p for p in model.parameters() if p.requires_grad], lr=args.lr, draw_ahead=sampler)
+    else:
+        opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=sampler,
+                         defer_step=not args.no_defer)  # gradients are cleared through opt.zero_grad() only: the step may wait
     reg = {"none": lambda: None, "l2": lambda: regularizers.L2(args.reg_weight), "n3": lambda: regularizers.N3(args.reg_weight)}[args.reg]()
     if args.loss == "adversarial":
         step = FusedTrainStep(model, args.alpha, regularizer=reg)
