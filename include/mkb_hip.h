@@ -590,6 +590,40 @@ int mkb_reg_rows(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *s
                  float lambda_ent, float lambda_rel, const float *weight_sum, const float *scale, float *value, void *ws,
                  int64_t ws_bytes, void *stream);
 
+/* ---- 1vsAll: softmax cross entropy over ALL entities, ComplEx and DistMult ---------------------------------------------
+ * No reference counterpart (the reference trains against sampled negatives only); mkb_amd/csrc/score_all.hip.  New symbols under
+ * ABI 8: the version is not bumped (symbols are only added).
+ *   row_i = log sum_{e < n_entity} exp(s_i(e) / T) - s_i(target_i) / T,   loss = sum_i w_i row_i / W
+ *   over sample [B, 3] in MKB_MODE_TAIL (s_i(e) = score of (h_i, r_i, e), target t_i) or MKB_MODE_HEAD ((e, r_i, t_i), target h_i);
+ *   weight [B] or null (all ones), W = sum of weight (B when null), or weight_sum[0] when given (the rows are a shard, as for
+ *   mkb_ns_loss).  No filtering of other known answers.  Only the two models whose all-entity block is one matrix product:
+ *   TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED (their sampled softmax is mkb_ns_loss with MKB_LOSS_SOFTMAX).
+ *   mkb_all_score_fwd: scores [B, n_entity] out = the all-entity block of the evaluation, the bits mkb_rank_scores hands out (the
+ *   same routes, chosen in the same place).
+ *   mkb_all_softmax: one pass per row over a block S [B, ld] of which the first N columns count, target[i * target_stride] the
+ *   row's target column.  Writes loss [1] and pos [B] (the target's score, read before anything is overwritten) and OVERWRITES S
+ *   with dS_ij = (w_i / (W T)) (p_ij - [j = target_i]); columns N .. ld - 1 take no part in the sums and are written as exactly 0.
+ *   Stable logsumexp, fixed-order reductions, no float atomics.  scratch: 1 + B floats (device).  A target outside [0, N) counts as
+ *   the nearest column: the glue flags it with mkb_check_ids.
+ *   mkb_all_score_bwd: accumulates d loss / d tables given dscore [B, ld] (columns past n_entity are not read) into gr->g_ent and
+ *   gr->g_rel (never zeroed; g_modulus and rows_clear are not used): dE += dscore^T . Q with every entity row written by exactly one
+ *   tile (a K split is reduced in fixed order and the finished product added once), dQ = dscore . E chained into the query's entity
+ *   row and relation row with one writer per distinct row.  No float atomics: two runs give the same bits.
+ *   mkb_all_step: forward, softmax and backward in one call, the score block staying in the workspace; pos [B] out.
+ *   ws: mkb_all_step_workspace_bytes(tb, B) bytes (the same for the three calls that take it), 256-byte aligned, caller-owned;
+ *   nothing is allocated in a call.  A null pointer, a mode other than head-/tail-batch, B < 1, T <= 0 or not finite, ld < N,
+ *   B * ld (or B * (n_entity + 3)) > 2^31 - 1, a short or misaligned workspace, an unknown model -> MKB_ERR_INVALID before any
+ *   launch.  The workspace function returns 0 for B <= 0, null tables, another model or a B that the calls refuse. */
+int64_t mkb_all_step_workspace_bytes(const mkb_tables_t *tb, int64_t B);
+int mkb_all_score_fwd(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, float *scores, void *ws, int64_t ws_bytes,
+                      void *stream);
+int mkb_all_softmax(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t target_stride, const float *weight,
+                    const float *weight_sum, float T, float *loss, float *pos, float *scratch, void *stream);
+int mkb_all_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode, const float *dscore,
+                      int64_t ld, void *ws, int64_t ws_bytes, void *stream);
+int mkb_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
+                 float temperature, const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

@@ -168,6 +168,14 @@ _SIGNATURES = {
     "mkb_reg_rows_workspace_bytes": (c_int64, [POINTER(Tables), c_int64]),
     "mkb_reg_rows": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_all_step_workspace_bytes": (c_int64, [POINTER(Tables), c_int64]),
+    "mkb_all_score_fwd": (c_int, [POINTER(Tables), c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_all_softmax": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "mkb_all_score_bwd": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_void_p]),
+    "mkb_all_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,8 +13,8 @@ README, or ``mkb_amd.optim.Adam``).
 import torch
 
 from ..datasets.device import DeviceBatches
-from ..fused import FusedTrainStep, PooledLossStep, pooled_supported
-from ..losses import Adversarial, CrossEntropy, MarginRanking, PairwiseLogistic
+from ..fused import FusedTrainStep, OneVsAllStep, PooledLossStep, pooled_supported
+from ..losses import Adversarial, CrossEntropy, MarginRanking, OneVsAll, PairwiseLogistic
 from ..models.base import BaseModel
 from ..sampling import NegativeSampling
 from ..utils import Bar, RollingMean
@@ -99,7 +99,11 @@ class Pipeline:
     # ------------------------------------------------------------------ one epoch of steps (pipeline.py:206-244)
     def _fused_step_for(self, model, dataset, sampling, optimizer, loss):
         """``FusedTrainStep`` (``Adversarial``) or ``PooledLossStep`` (``MarginRanking`` / ``PairwiseLogistic`` / ``CrossEntropy``)
-        when model, sampler and loss are the mkb_amd ones on a ROCm device, else None."""
+        when model, sampler and loss are the mkb_amd ones on a ROCm device, else None.  ``losses.OneVsAll`` always takes
+        ``OneVsAllStep``: it has no explicit sequence (no negatives are drawn: ``sampling`` is not used)."""
+        if isinstance(loss, OneVsAll):
+            self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
+            return OneVsAllStep(model, loss.temperature, regularizer=self.regularizer)
         if not (self.fuse and isinstance(model, BaseModel) and isinstance(sampling, NegativeSampling)
                 and type(loss) in (Adversarial,) + _POOLED_LOSSES and model.entity_embedding.is_cuda
                 and pooled_supported(model, dataset.batch_size, sampling.size)):

@@ -5,6 +5,8 @@
 //     S  [B, P]  = Q [B, De] . Xp[P, De]^T          Xp = ent[pool]   (gathered through the row index, never copied)
 //     dQ [B, De] = G [B, P]  . Xp[P, De]
 //     dXp[P, De] = G^T[P, B] . Q [B, De]            accumulated into g_ent[pool[p]] (atomics: pool ids may repeat)
+// ... and of the 1vsAll step (score_all.hip), whose pool is every entity in order, once: there dX = G^T . Q writes each entity row
+// from exactly one tile and accumulates with plain loads and stores (GEMM_ACCUM), no row index and no atomics.
 // G is zero where a row does not use a position, so no masking is needed.  gfx950 has no TF32/xf32; the exact
 // fp32-input matrix instruction v_mfma_f32_32x32x2_f32 runs at the fp32 vector rate with bitwise fmaf-chain
 // numerics, which is what the 1e-4 parity budget wants.
@@ -161,6 +163,7 @@ __global__ __launch_bounds__(TM * 4) void gemm_f32_mfma_kernel(GemmArgs G) {
             float *Cz = G.C + (int64_t)blockIdx.z * G.M * G.ldc;  // partial buffer of this K split (z = 0: C itself)
             if constexpr (EPI == GEMM_STORE) Cz[(int64_t)m * G.ldc + n] = v;
             else if constexpr (EPI == GEMM_STORE_AFFINE) Cz[(int64_t)m * G.ldc + n] = (gridDim.z > 1) ? v : G.c0 + G.c1 * v;
+            else if constexpr (EPI == GEMM_ACCUM) Cz[(int64_t)m * G.ldc + n] = (gridDim.z > 1) ? v : Cz[(int64_t)m * G.ldc + n] + v;
             else if (v != 0.f) atomicAdd(G.C + G.c_idx[m] * G.ldc + n, v);
         }
     }
@@ -325,6 +328,7 @@ __global__ __launch_bounds__(256) void gemm128_f32_mfma_kernel(GemmArgs G) {
                     const float v = acc[a][b][reg];
                     if constexpr (EPI == GEMM_STORE) Cz[(int64_t)m * G.ldc + n] = v;
                     else if constexpr (EPI == GEMM_STORE_AFFINE) Cz[(int64_t)m * G.ldc + n] = (gridDim.z > 1) ? v : G.c0 + G.c1 * v;
+                    else if constexpr (EPI == GEMM_ACCUM) Cz[(int64_t)m * G.ldc + n] = (gridDim.z > 1) ? v : Cz[(int64_t)m * G.ldc + n] + v;
                     else if (v != 0.f) atomicAdd(G.C + G.c_idx[m] * G.ldc + n, v);
                 }
             }
@@ -569,6 +573,7 @@ __device__ __forceinline__ void gemm128_bf16x3_body(const GemmArgs &G, const int
                     const float v = acc[a][b][reg];
                     if constexpr (EPI == GEMM_STORE) Cz[(int64_t)m * G.ldc + n] = v;
                     else if constexpr (EPI == GEMM_STORE_AFFINE) Cz[(int64_t)m * G.ldc + n] = (nz > 1) ? v : G.c0 + G.c1 * v;
+                    else if constexpr (EPI == GEMM_ACCUM) Cz[(int64_t)m * G.ldc + n] = (nz > 1) ? v : Cz[(int64_t)m * G.ldc + n] + v;
                     else if (v != 0.f) atomicAdd(G.C + G.c_idx[m] * G.ldc + n, v);
                 }
             }
@@ -601,8 +606,9 @@ __global__ __launch_bounds__(256) void gemm128_bf16x3_pair_kernel(GemmArgs G1, G
     }
 }
 
-// out[i] = c0 + c1 * sum_z part[z][i]   (fixed order: deterministic)
-template <int UNUSED = 0>  // (a template so that the header can be included by several translation units)
+// out[i] = c0 + c1 * sum_z part[z][i]   (fixed order: deterministic); ADD (the GEMM_ACCUM epilogue): out[i] += sum_z part[z][i] --
+// the finished product is added once
+template <int ADD = 0>  // (a template also so that the header can be included by several translation units)
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restrict__ part, float *__restrict__ out, int64_t n,
                                                             int nz, float c0, float c1) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -614,7 +620,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
 #pragma unroll
             for (int k = 0; k < 8; ++k) s += z0 + k < nz ? v[k] : 0.f;
         }
-        out[i] = c0 + c1 * s;
+        if constexpr (ADD) out[i] += s;
+        else out[i] = c0 + c1 * s;
     }
 }
 
@@ -688,7 +695,10 @@ static int gemm_finish(const GemmPlan &P, const GemmArgs &G, hipStream_t st, flo
         const int64_t n = (int64_t)G.M * G.ldc;
         const bool affine = P.s.epi == GEMM_STORE_AFFINE;
         const float c0 = affine ? G.c0 : 0.f, c1 = affine ? G.c1 : 1.f;
-        if (P.tail_handed) *tail = GemmTail{1, partials, G.C, nullptr, G.M, G.N, P.ks, G.ldc, n, c0, c1, nullptr, 0};
+        if (P.s.epi == GEMM_ACCUM) {  // (no caller folds this tail: GemmTail's kinds store)
+            if (P.tail_handed) return set_error(MKB_ERR_INVALID, "the accumulating product's tail cannot be handed on");
+            hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3(512), dim3(256), 0, st, partials, G.C, n, P.ks, 0.f, 1.f);
+        } else if (P.tail_handed) *tail = GemmTail{1, partials, G.C, nullptr, G.M, G.N, P.ks, G.ldc, n, c0, c1, nullptr, 0};
         else hipLaunchKernelGGL(splitk_reduce_kernel<0>, dim3(512), dim3(256), 0, st, partials, G.C, n, P.ks, c0, c1);
     }
     MKB_LAUNCH_CHECK();

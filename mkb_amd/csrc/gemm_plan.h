@@ -8,8 +8,11 @@
 
 namespace mkb {
 
-enum { GEMM_STORE = 0, GEMM_STORE_AFFINE = 1, GEMM_ATOMIC_ROWS = 2 };
+// GEMM_ACCUM: C += A . B, every element of C written by exactly one tile (a K split goes through the partial buffer and a
+// fixed-order reduction that adds the finished product once): the dense entity gradient of the 1vsAll step (score_all.hip)
+enum { GEMM_STORE = 0, GEMM_STORE_AFFINE = 1, GEMM_ATOMIC_ROWS = 2, GEMM_ACCUM = 3 };
 constexpr int kBfPitch = 80;  // bytes between rows of a bf16 plane (the staging of the bf16x3 kernels)
+constexpr size_t kGemmLdsMax = 160 * 1024;  // LDS of a CU: a plan that asks for more cannot launch
 
 // The per-call switches of the products (DESIGN.md "Run-time switches"), read once per ABI call by the caller
 struct GemmSwitches {
@@ -76,9 +79,19 @@ inline GemmPlan plan_gemm(const GemmShape &s, const GemmLimits &lim, const GemmS
     };
     auto chunk_ids = [&](int ks) { return (size_t)(((s.K + ks - 1) / ks + 31) / 32 * 32) * 4; };  // row ids of a K range
     // 128 x 128 / 128 x 64 tiles (4 / 2 accumulators per wave) when the operands allow 16-byte loads
-    const bool al = s.aligned16 && s.lda % 4 == 0 && s.ldb % 4 == 0 && s.M % 4 == 0 && s.N % 4 == 0 && s.K % 4 == 0;
+    // The bf16x3 kernel's buffer loads address an operand with SIGNED 32-bit byte offsets: every row it can touch must lie
+    // within 2 GB of the base; larger operands take the fp32 kernel
+    const int64_t a_span = (s.a_mk ? (int64_t)s.M * s.lda : (int64_t)s.K * s.lda) * 4;
+    const bool fits32 = a_span < ((int64_t)1 << 31) && s.b_rows > 0 && s.b_rows * s.ldb * 4 < ((int64_t)1 << 31);
+    const bool bf = sw.bf16x3 && fits32;
+    // M % 4: the fp32 tiles load an m-contiguous A four rows at a time.  The bf16x3 kernel loads it one value per lane and every
+    // kernel stores C element by element, so the accumulating product -- M is the entity count, whatever that is -- keeps the
+    // 128-row tiles there
+    const bool m_ok = s.M % 4 == 0 || (s.epi == GEMM_ACCUM && !s.a_mk && bf);
+    const bool al = s.aligned16 && s.lda % 4 == 0 && s.ldb % 4 == 0 && m_ok && s.N % 4 == 0 && s.K % 4 == 0;
     const int m128 = (s.M + 127) / 128, tiles128 = m128 * ((s.N + 127) / 128);
-    if (!sw.no128 && al && tiles128 >= 24 && (lim.partials || lim.max_ks <= 1)) {
+    bool big = !sw.no128 && al && tiles128 >= 24 && (lim.partials || lim.max_ks <= 1);
+    if (big) {
         // fill ~256 CUs: prefer the narrower tile (no K split, no reduction launch) to splitting K
         p.tn = tiles128 < 200 ? 64 : 128;
         p.tm = 128;
@@ -87,17 +100,20 @@ inline GemmPlan plan_gemm(const GemmShape &s, const GemmLimits &lim, const GemmS
         // workgroups wanted: ~1 per CU by default; the products whose tail rides the next launch ask for 2 (want_wg = 500: a lone
         // 4-wave workgroup leaves each SIMD's matrix pipe idle during its staging; measured 37 -> 29 us)
         p.ks = split((int)(p.mx * p.ny), lim.want_wg ? lim.want_wg : 200, 96);
-        // The bf16x3 kernel's buffer loads address an operand with SIGNED 32-bit byte offsets: every row it can touch must lie
-        // within 2 GB of the base; larger operands take the fp32 kernel
-        const int64_t a_span = (s.a_mk ? (int64_t)s.M * s.lda : (int64_t)s.K * s.lda) * 4;
-        const bool fits32 = a_span < ((int64_t)1 << 31) && s.b_rows > 0 && s.b_rows * s.ldb * 4 < ((int64_t)1 << 31);
-        p.kernel = sw.bf16x3 && fits32 ? GemmKernel::Bf16x3Tile128 : GemmKernel::F32Tile128;
+        p.kernel = bf ? GemmKernel::Bf16x3Tile128 : GemmKernel::F32Tile128;
         // (two stages of a 128 x 128 fp32 tile pair are 66 KB: more than the 64 KB a kernel gets without asking)
         p.lds = (p.kernel == GemmKernel::Bf16x3Tile128 ? (size_t)3 * (128 + p.tn) * kBfPitch : (size_t)2 * (128 + p.tn) * 33 * 4) + chunk_ids(p.ks);
         // the scattered product always goes through partials [ks][M][N] and ONE atomic per element
         p.tail = atomic ? GemmTailKind::Scatter : (p.ks > 1 && !to_slices ? GemmTailKind::Reduce : GemmTailKind::None);
         p.tail_handed = lim.fold_tail && p.tail != GemmTailKind::None;
-    } else {
+        // the row ids of a K range are staged whole: a K of hundreds of thousands (every entity of a large graph) does not fit
+        if (p.lds > kGemmLdsMax) {
+            big = false;
+            p.lds = 0;
+            p.tail_handed = false;
+        }
+    }
+    if (!big) {
         const int n64 = (s.N + 63) / 64, tiles64 = ((s.M + 63) / 64) * n64;
         p.tm = tiles64 < 256 ? 32 : 64;  // few tiles: two waves per workgroup, twice the workgroups
         p.tn = 64;

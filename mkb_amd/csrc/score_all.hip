@@ -1,0 +1,364 @@
+// 1vsAll softmax training for ComplEx / DistMult (include/mkb_hip.h, "1vsAll"): every entity is scored for each (h, r, ?) -- or
+// (?, r, t) -- and the cross entropy is taken over the whole row,
+//     row_i = log sum_{e < N} exp(s_i(e) / T) - s_i(target_i) / T,     loss = sum_i w_i row_i / W.
+//
+//   forward   the all-entity block of the evaluation (run_rank, rank_all.h): ONE matrix-core product S = Q . E^T, or the
+//             lane-owns-dims kernel for the shapes that product does not take.  The route is chosen there, not here.
+//   softmax   all_softmax_kernel: one 256-lane workgroup per row, three passes (maximum, partition sum, seeds); rows of up to
+//             kAllStageCols columns are read once and kept in LDS, longer ones are re-read from global memory.  S is overwritten in
+//             place with dS_ij = (w_i / (W T)) (p_ij - [j = target_i]); the columns N .. ld - 1 that the forward's padding fills
+//             with the last entity's score take no part in the sums and their dS is written as exactly 0.
+//   backward  dQ [B, De] = dS . E and dE [N, De] += dS^T . Q, both planned by plan_gemm (shapes and limits: all_plan.h) and launched
+//             through launch_gemm; dE uses the accumulating epilogue (GEMM_ACCUM: every entity row is written by exactly one tile,
+//             a K split is reduced in fixed order and the finished product added once).  Then dQ is chained into the query's
+//             entity row and relation row (query_side.h): the 2 B occurrences are radix-sorted by row (pair_sort.h) and each
+//             distinct row has a single writer that walks its occurrences in batch order and adds the sum onto the gradient row
+//             (a query entity's row: together with its row of dE, in one rounded addition -- all_stash_kernel).
+// No float atomics anywhere: loss and both gradient tables have the same bits run to run, and gradient buffers that held
+// something end as that + the step's result, bit for bit.
+#include "common.h"
+#include "loss_math.h"
+#include "pair_sort.h"
+#include "rank_all.h"
+#include "score_row.h"  // table_row
+
+#include <algorithm>
+#include <math.h>
+
+namespace mkb {
+
+constexpr int kAllStageCols = 4096;  // 16 KB of LDS per row
+
+// max over the workgroup's 256 lanes; every lane gets it.  red: 4 floats of LDS.
+__device__ __forceinline__ float block_max_256(float v, float *red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// scal: W on the device, or null: every workgroup reduces it from w alike (or takes B) and workgroup 0 publishes it in scal_out
+__global__ __launch_bounds__(256) void all_softmax_kernel(float *__restrict__ S, int B, int64_t N, int64_t ld,
+                                                          const int64_t *__restrict__ target, int64_t tstride,
+                                                          const float *__restrict__ w, const float *__restrict__ scal,
+                                                          float *__restrict__ scal_out, float inv_T, float *__restrict__ pos,
+                                                          float *__restrict__ rowpart) {
+    __shared__ float red[4];
+    extern __shared__ float s_row[];
+    const int tid = threadIdx.x;
+    const int64_t i = blockIdx.x;
+    float *row = S + i * ld;
+    const bool staged = N <= kAllStageCols;
+    const int64_t t = table_row(target[i * tstride], N);  // (an id outside the table: the glue flags it, mkb_check_ids)
+    const float p_i = row[t];  // before anything is overwritten: every lane reads it here, the barriers below come first
+    const float wi = w ? w[i] : 1.f;
+
+    float m = -INFINITY;
+    for (int64_t j = tid; j < N; j += 256) {
+        const float v = row[j];
+        m = fmaxf(m, v);
+        if (staged) s_row[j] = v;
+    }
+    const float W = scal ? scal[0] : (w ? weight_sum_block(w, B, red) : (float)B);
+    if (!scal && blockIdx.x == 0 && tid == 0) scal_out[0] = W;
+    m = block_max_256(m, red);
+
+    // every exponent relative to the row maximum in score units: the row is (m - pos) / T + log Z with Z >= 1
+    float z = 0.f;
+    for (int64_t j = tid; j < N; j += 256) {
+        const float e = expf(((staged ? s_row[j] : row[j]) - m) * inv_T);
+        z += e;
+        if (staged) s_row[j] = e;
+    }
+    z = block_sum_256(z, red);  // lane-strided partial sums, then the fixed tree
+    const float inv = 1.f / z, coef = wi * inv_T / W;
+    for (int64_t j = tid; j < N; j += 256) {
+        const float e = staged ? s_row[j] : expf((row[j] - m) * inv_T);
+        row[j] = coef * (e * inv - (j == t ? 1.f : 0.f));
+    }
+    for (int64_t j = N + tid; j < ld; j += 256) row[j] = 0.f;  // the forward's pad columns
+    if (tid == 0) {
+        pos[i] = p_i;
+        rowpart[i] = wi * ((m - p_i) * inv_T + logf(z));
+    }
+}
+
+// loss = sum_i rowpart[i] / W by one 256-lane workgroup: strided partial sums, then the fixed tree of block_sum_256
+__global__ __launch_bounds__(256) void all_loss_finish_kernel(const float *__restrict__ rowpart, int B, const float *__restrict__ scal,
+                                                              float *__restrict__ loss) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) acc += rowpart[i];
+    const float total = block_sum_256(acc, red);
+    if (threadIdx.x == 0) loss[0] = total / scal[0];
+}
+
+// scratch: [0] = W, [1 .. B] = the rows' terms
+static void all_softmax_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride, const float *weight,
+                               const float *weight_sum, float T, float *loss, float *pos, float *scratch, hipStream_t st) {
+    float *scal = scratch, *rowpart = scratch + 1;
+    const float *scal_in = weight_sum;
+    if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one launch in front
+        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
+        scal_in = scal;
+    }
+    const size_t lds = N <= kAllStageCols ? (size_t)N * sizeof(float) : 0;
+    hipLaunchKernelGGL(all_softmax_kernel, dim3((unsigned)B), dim3(256), lds, st, S, (int)B, N, ld, target, tstride, weight, scal_in, scal,
+                       1.f / T, pos, rowpart);
+    hipLaunchKernelGGL(all_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B, weight_sum ? weight_sum : scal, loss);
+}
+
+// ---- query chain: dQ -> the query's entity row (h; t for head-batch) and relation row, one writer per distinct row
+struct ChainArgs {
+    const float *ent, *rel;  // (the table fields query_row reads)
+    int64_t De, Dr;
+    int d;
+    float kd;
+    const int64_t *sample;
+    const float *dQ;
+    float *g_ent, *g_rel;
+    const int *keys, *vals;  // the sorted occurrences: row keys (relations: n_entity + r) and occurrence indices (relations: B + i)
+    int n, B, n_entity;
+    float *stash;  // [B, De]: what the gradient rows of the batch's query entities held before the step, by sorted position
+};
+
+// The gradient row of a query's entity takes two terms, its row of the product dE and the chain's.  Adding them one after the other
+// onto what the row already holds would round twice; so the row's content is set aside and the row cleared here, the product adds
+// onto zero (exact), and the chain kernel writes stash + (product + chain): the finished result is added once, as for every
+// other row.  One workgroup per sorted position of the entity keys (they sort in front of the relation keys: positions 0 .. B - 1).
+__global__ __launch_bounds__(256) void all_stash_kernel(ChainArgs A) {
+    const int pos = blockIdx.x;
+    const int key = A.keys[pos];
+    if (pos > 0 && A.keys[pos - 1] == key) return;
+    float *g = A.g_ent + (int64_t)key * A.De, *x = A.stash + (int64_t)pos * A.De;
+    for (int64_t u = threadIdx.x; u < A.De; u += 256) {
+        x[u] = g[u];
+        g[u] = 0.f;
+    }
+}
+
+template <int MODEL, bool HEAD>
+__global__ __launch_bounds__(256) void all_chain_kernel(ChainArgs A) {
+    constexpr bool CQ = ModelTraits<MODEL>::cplx_query;
+    const int pos = blockIdx.x;
+    const int key = A.keys[pos];
+    if (pos > 0 && A.keys[pos - 1] == key) return;  // (uniform) only the position that opens a run of equal keys owns the row
+    const bool is_rel = key >= A.n_entity;
+    float *g = is_rel ? A.g_rel + (int64_t)(key - A.n_entity) * A.Dr : A.g_ent + (int64_t)key * A.De;
+    const bool has_im = CQ && (!is_rel || MODEL == MKB_COMPLEX);
+    const int U = CQ ? A.d : (int)A.De;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        float a_re = 0.f, a_im = 0.f;
+        for (int j = pos; j < A.n && A.keys[j] == key; ++j) {  // the run in batch order (the sort is stable)
+            const int64_t i = A.vals[j] % A.B;
+            const QueryRow R = query_row<MODEL>(A, A.sample, i);
+            const float *dq = A.dQ + i * A.De;
+            const float dq0 = dq[u], dq1 = CQ ? dq[A.d + u] : 0.f;
+            Cplx de, dr;
+            query_unit_bwd<MODEL, HEAD>(R, u, dq0, dq1, de, dr);
+            a_re += is_rel ? dr.re : de.re;
+            a_im += is_rel ? dr.im : de.im;
+        }
+        if (is_rel) {
+            g[u] += a_re;
+            if (has_im) g[A.d + u] += a_im;
+        } else {  // (see all_stash_kernel)
+            const float *x = A.stash + (int64_t)pos * A.De;
+            g[u] = x[u] + (g[u] + a_re);
+            if (has_im) g[A.d + u] = x[A.d + u] + (g[A.d + u] + a_im);
+        }
+    }
+}
+
+// ---- workspace: Q [B, De], the score block [B, Npad] (which becomes dS), the id list [Npad], dQ [B, De], the partial buffer of the
+// two backward products (used one after the other), the stash [B, De] of all_stash_kernel, the sort's storage, the loss scratch [1 + B]
+struct AllPlan {
+    PairSortPlan sort;
+    size_t s_off, ids_off, dq_off, stash_off, part_off, sort_off, scr_off, total;
+};
+struct AllWs {
+    float *Q, *S;
+    int64_t *ids;
+    float *dQ, *stash, *part;
+    void *sort;
+    float *scratch;
+};
+
+static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The shapes one int32 sort, one int32 GEMM and the softmax's B * ld limit cover (B >= 1 is the caller's).  false: outside them, or
+// the sort's size query failed (*rc < 0)
+static bool all_plan(const mkb_tables_t *tb, int64_t B, AllPlan &P, int *rc) {
+    *rc = 0;
+    const int64_t N = tb->n_entity, Npad = all_npad(N), De = tb->entity_dim;
+    if (N <= 0 || tb->n_relation <= 0 || De <= 0 || Npad >= (1 << 30) || N + tb->n_relation > INT32_MAX || B > INT32_MAX / 2 ||
+        B * Npad > INT32_MAX || B * De > INT32_MAX)
+        return false;
+    if ((*rc = pair_sort_plan(N + tb->n_relation, 2 * B, P.sort))) return false;
+    const GemmSwitches sw{false, false, true};  // (part_bound does not depend on the switches)
+    const size_t part = std::max(plan_gemm(all_dq_shape(B, N, De, Npad, true, true), all_dq_limits(), sw).part_bound,
+                                 plan_gemm(all_de_shape(B, N, De, Npad, true), all_de_limits(N, De), sw).part_bound);
+    P.s_off = up256((size_t)B * De * 4);
+    P.ids_off = P.s_off + up256((size_t)B * Npad * 4);
+    P.dq_off = P.ids_off + up256((size_t)Npad * 8);
+    P.stash_off = P.dq_off + up256((size_t)B * De * 4);
+    P.part_off = P.stash_off + up256((size_t)B * De * 4);
+    P.sort_off = P.part_off + up256(part * 4);
+    P.scr_off = P.sort_off + P.sort.total;
+    P.total = P.scr_off + up256((size_t)(B + 1) * 4);
+    return true;
+}
+
+static AllWs all_carve(const AllPlan &P, void *ws) {
+    unsigned char *b = (unsigned char *)ws;
+    return AllWs{(float *)b, (float *)(b + P.s_off), (int64_t *)(b + P.ids_off), (float *)(b + P.dq_off), (float *)(b + P.stash_off),
+                 (float *)(b + P.part_off),
+                 b + P.sort_off, (float *)(b + P.scr_off)};
+}
+
+// dS [B, ld] -> g_ent, g_rel (accumulated).  w.Q holds the batch's queries.  gathered: dS is the forward's padded block, its pad
+// columns exactly 0, and w.ids the forward's id list.
+template <int MODEL, bool HEAD>
+static int all_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, const float *dS, int64_t ld,
+                   bool gathered, const AllPlan &P, const AllWs &w, hipStream_t st) {
+    const int64_t N = tb->n_entity, De = tb->entity_dim;
+    const GemmSwitches sw = gemm_switches_from_env();
+    const bool al = (((uintptr_t)dS | (uintptr_t)tb->ent | (uintptr_t)gr->g_ent) & 15) == 0;  // (Q, dQ: the 256-byte aligned workspace)
+    PairKeySegs segs{};
+    segs.seg[0] = PairKeySeg{sample + (HEAD ? 2 : 0), 3, B, N, 0};    // the query's entity
+    segs.seg[1] = PairKeySeg{sample + 1, 3, B, tb->n_relation, (int)N};  // its relation
+    segs.n_segs = 2;
+    ChainArgs A{};
+    if (int rc = pair_sort_launch_segs(segs, w.sort, P.sort, st, &A.keys, &A.vals)) return rc;
+    A.ent = tb->ent; A.rel = tb->rel; A.De = De; A.Dr = tb->relation_dim; A.d = tb->hidden_dim; A.kd = tb->phase_div;
+    A.sample = sample; A.dQ = w.dQ; A.g_ent = gr->g_ent; A.g_rel = gr->g_rel;
+    A.n = (int)(2 * B); A.B = (int)B; A.n_entity = (int)N; A.stash = w.stash;
+    hipLaunchKernelGGL(all_stash_kernel, dim3((unsigned)B), dim3(256), 0, st, A);
+    {
+        const GemmPlan plan = plan_gemm(all_dq_shape(B, N, De, ld, gathered, al), all_dq_limits(), sw);
+        GemmArgs G = gemm_args(plan);
+        G.A = dS; G.B = tb->ent; G.C = w.dQ; G.b_idx = gathered ? w.ids : nullptr;
+        if (int rc = launch_gemm<true, false, GEMM_STORE>(plan, G, st, w.part)) return rc;
+    }
+    {
+        const GemmPlan plan = plan_gemm(all_de_shape(B, N, De, ld, al), all_de_limits(N, De), sw);
+        GemmArgs G = gemm_args(plan);
+        G.A = dS; G.B = w.Q; G.C = gr->g_ent;
+        if (int rc = launch_gemm<false, false, GEMM_ACCUM>(plan, G, st, w.part)) return rc;
+    }
+    hipLaunchKernelGGL((all_chain_kernel<MODEL, HEAD>), dim3((unsigned)(2 * B)), dim3(256), 0, st, A);
+    MKB_LAUNCH_CHECK();
+    return MKB_OK;
+}
+
+// f(std::integral_constant<int, MODEL>{}, std::bool_constant<HEAD>{}) for the two models whose all-entity block is one product
+template <class F>
+static int dispatch_dot_model(int model, bool head, F &&f) {
+    auto side = [&](auto m) { return head ? f(m, std::true_type{}) : f(m, std::false_type{}); };
+    if (model == MKB_COMPLEX) return side(std::integral_constant<int, MKB_COMPLEX>{});
+    if (model == MKB_DISTMULT) return side(std::integral_constant<int, MKB_DISTMULT>{});
+    return set_error(MKB_ERR_UNSUPPORTED,
+                     "1vsAll covers ComplEx and DistMult, whose all-entity block is one matrix product; for TransE, RotatE and pRotatE "
+                     "use the sampled softmax (losses.CrossEntropy)");
+}
+
+// what every entry point that takes tables, a batch and the workspace checks, in this order
+static int all_check(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const void *ws, int64_t ws_bytes, AllPlan &P) {
+    if (int rc = validate_tables(tb)) return rc;
+    MKB_REQUIRE(sample && ws, "null pointer");
+    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "1vsAll needs head-batch or tail-batch");
+    MKB_REQUIRE(B >= 1, "B must be >= 1");
+    if (tb->model != MKB_COMPLEX && tb->model != MKB_DISTMULT) return dispatch_dot_model(tb->model, false, [](auto, auto) { return MKB_OK; });
+    MKB_REQUIRE(tb->entity_dim <= 4 * kWGr, "rows of more than 4096 units are not supported");
+    int rc;
+    if (!all_plan(tb, B, P, &rc)) {
+        if (rc) return rc;
+        MKB_REQUIRE(false, "B * (n_entity + 3) and B * entity_dim must stay below 2^31, n_entity below 2^30");
+    }
+    MKB_REQUIRE(ws_bytes >= (int64_t)P.total && (((uintptr_t)ws) & 255) == 0, "workspace too small / unaligned");
+    return MKB_OK;
+}
+
+static int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const void *target, int64_t tstride, float T, const void *loss,
+                         const void *pos, const void *scratch) {
+    MKB_REQUIRE(S && target && loss && pos && scratch, "null pointer");
+    MKB_REQUIRE(T - T == 0.f && T > 0.f, "the softmax temperature must be finite and > 0");
+    MKB_REQUIRE(B >= 1, "B must be >= 1");
+    MKB_REQUIRE(N >= 1 && ld >= N && tstride >= 1, "need N >= 1, ld >= N and target_stride >= 1");
+    MKB_REQUIRE(B <= INT32_MAX && ld <= INT32_MAX && B * ld <= INT32_MAX, "B * ld must stay below 2^31");
+    return MKB_OK;
+}
+
+}  // namespace mkb
+
+using namespace mkb;
+
+extern "C" int64_t mkb_all_step_workspace_bytes(const mkb_tables_t *tb, int64_t B) {
+    AllPlan P;
+    int rc;
+    if (!tb || B <= 0 || (tb->model != MKB_COMPLEX && tb->model != MKB_DISTMULT) || !all_plan(tb, B, P, &rc)) return 0;
+    return (int64_t)P.total;
+}
+
+extern "C" int mkb_all_score_fwd(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, float *scores, void *ws,
+                                 int64_t ws_bytes, void *stream) {
+    AllPlan P;
+    MKB_REQUIRE(scores, "null pointer");
+    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
+    const AllWs w = all_carve(P, ws);
+    hipStream_t st = (hipStream_t)stream;
+    auto finish = [&](float f0, float f1, int64_t ld) {  // the evaluation's export: the bits mkb_rank_scores hands out
+        hipLaunchKernelGGL(export_scores_kernel, dim3((unsigned)std::min<int64_t>((tb->n_entity + 255) / 256, 64), (unsigned)B), dim3(256), 0,
+                           st, w.S, scores, tb->n_entity, ld, f0, f1);
+    };
+    return dispatch_dot_model(tb->model, mode == MKB_MODE_HEAD,
+                              [&](auto m, auto h) { return run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish); });
+}
+
+extern "C" int mkb_all_softmax(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t target_stride,
+                               const float *weight, const float *weight_sum, float T, float *loss, float *pos, float *scratch,
+                               void *stream) {
+    if (int rc = softmax_check(S, B, N, ld, target, target_stride, T, loss, pos, scratch)) return rc;
+    all_softmax_launch(S, B, N, ld, target, target_stride, weight, weight_sum, T, loss, pos, scratch, (hipStream_t)stream);
+    MKB_LAUNCH_CHECK();
+    return MKB_OK;
+}
+
+extern "C" int mkb_all_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode,
+                                 const float *dscore, int64_t ld, void *ws, int64_t ws_bytes, void *stream) {
+    AllPlan P;
+    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && dscore, "null pointer");
+    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
+    MKB_REQUIRE(ld >= tb->n_entity && B * ld <= INT32_MAX, "need ld >= n_entity and B * ld below 2^31");
+    const AllWs w = all_carve(P, ws);
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_dot_model(tb->model, mode == MKB_MODE_HEAD, [&](auto m, auto h) {
+        const RowArgs ra = query_build_args(tb->ent, tb->rel, sample, w.Q, tb->entity_dim, tb->relation_dim, tb->hidden_dim, B, tb->phase_div);
+        hipLaunchKernelGGL((query_build_kernel<m(), h()>), dim3((unsigned)B), dim3(256), 0, st, ra);
+        return all_bwd<m(), h()>(tb, gr, sample, B, dscore, ld, false, P, w, st);
+    });
+}
+
+extern "C" int mkb_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
+                            int mode, float temperature, const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes,
+                            void *stream) {
+    AllPlan P;
+    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
+    MKB_REQUIRE(temperature - temperature == 0.f && temperature > 0.f, "the softmax temperature must be finite and > 0");
+    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
+    const AllWs w = all_carve(P, ws);
+    hipStream_t st = (hipStream_t)stream;
+    const bool head = mode == MKB_MODE_HEAD;
+    const int64_t N = tb->n_entity;
+    int64_t ld_S = 0;
+    auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
+        ld_S = ld;
+        all_softmax_launch(w.S, B, N, ld, sample + (head ? 0 : 2), 3, weight, weight_sum, temperature, loss, pos, w.scratch, st);
+    };
+    return dispatch_dot_model(tb->model, head, [&](auto m, auto h) {
+        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
+        return all_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, ld_S > N, P, w, st);
+    });
+}

@@ -9,6 +9,9 @@
                         bypassing autograd.  Used by ``compose.Pipeline`` when model / sampler / loss are ours.
 ``PooledLossStep``   -- the same step for ``losses.MarginRanking`` / ``PairwiseLogistic`` / ``CrossEntropy``: the separate
                         pooled entry points around ``mkb_ns_loss``, bypassing autograd.
+``OneVsAllStep``     -- the 1vsAll step of ComplEx / DistMult (``losses.OneVsAll``): every entity scored for each row, the softmax
+                        over the whole row and the dense backward in one call (``mkb_all_step``); no negatives are drawn.
+``score_all``        -- the ``[B, n_entity]`` block behind ``model.score_all``, differentiable (``mkb_all_score_fwd`` / ``_bwd``).
 """
 import torch
 
@@ -16,7 +19,7 @@ from . import _gradshare, _hip, _links
 from .losses import ns_losses
 from .sampling.negative_sampling import PoolInfo
 
-__all__ = ["FusedTrainStep", "PooledLossStep", "pooled_forward", "pooled_supported"]
+__all__ = ["FusedTrainStep", "PooledLossStep", "OneVsAllStep", "pooled_forward", "pooled_supported", "score_all"]
 
 _workspaces = {}
 
@@ -273,3 +276,105 @@ class PooledLossStep:
     @property
     def negative_score(self):
         return self._S.gather(1, self._info.pos.long())
+
+
+# ---------------------------------------------------------------------------------------------------- 1vsAll (ComplEx / DistMult)
+ONE_VS_ALL_MODELS = ("ComplEx", "DistMult")  # the models whose all-entity block is ONE matrix product
+
+
+def _all_workspace(model, B):
+    """Device scratch of the three ``mkb_all_*`` calls that take tables, cached like ``_workspace``."""
+    dev = model.entity_embedding.device
+    key = (dev, _hip.stream_ptr(dev).value, "all", model.name, model.entity_dim, model.n_entity, model.n_relation, B)
+    return cached_workspace(key, dev, lambda: _hip.lib().mkb_all_step_workspace_bytes(model._tables(), B))
+
+
+def _side(mode):
+    mode_id = _hip.mode_id(mode)
+    if mode_id == _hip.MODE_DEFAULT:
+        raise ValueError(f"1vsAll scores one side of a triple: mode must be 'head-batch' or 'tail-batch', not {mode!r}")
+    return mode_id
+
+
+class _ScoreAllFn(torch.autograd.Function):
+    """scores [B, n_entity] of every entity in the open slot of ``sample``; backward = dense d loss / d tables."""
+
+    @staticmethod
+    def forward(ctx, ent, rel, model, sample, mode):
+        B = sample.shape[0]
+        scores = torch.empty((B, model.n_entity), dtype=torch.float32, device=ent.device)
+        ws = _all_workspace(model, B)
+        with _hip.on_device(ent.device):
+            _hip.check(_hip.lib().mkb_all_score_fwd(model._tables(ent, rel), _hip.ptr(sample), B, mode, _hip.ptr(scores), _hip.ptr(ws),
+                                                    ws.numel(), _hip.stream_ptr()), "mkb_all_score_fwd")
+        ctx.model, ctx.mode = model, mode
+        ctx.save_for_backward(ent, rel, sample)
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscore):
+        ent, rel, sample = ctx.saved_tensors
+        model, B = ctx.model, sample.shape[0]
+        dscore = _hip.contiguous(dscore, torch.float32)
+        g_ent, g_rel = torch.zeros_like(ent), torch.zeros_like(rel)  # every entity row is written: dense, through autograd
+        ws = _all_workspace(model, B)
+        with _hip.on_device(ent.device):
+            _hip.check(_hip.lib().mkb_all_score_bwd(model._tables(ent, rel), _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None),
+                                                    _hip.ptr(sample), B, ctx.mode, _hip.ptr(dscore), dscore.shape[1], _hip.ptr(ws),
+                                                    ws.numel(), _hip.stream_ptr()), "mkb_all_score_bwd")
+        return g_ent, g_rel, None, None, None
+
+
+def score_all(model, sample, mode):
+    """What ``model.score_all(sample, mode)`` runs (models/base.py checks the arguments and makes row-lazy tables current)."""
+    return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, model, sample, _side(mode))
+
+
+class OneVsAllStep:
+    """``loss = step(sample, weight, mode)``: the 1vsAll softmax step of ComplEx / DistMult.  Every entity is scored for each
+    ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``) and the cross entropy is taken over the whole row, at
+    ``temperature``; fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.  ``positive_score``
+    [B, 1] of the last call stays available.  One library call (``mkb_all_step``), no autograd, no negatives, no filtering of a
+    row's other known answers.  ``weight``: [B] or None (all ones); ``weight_sum`` and ``regularizer``: as for ``FusedTrainStep``.
+
+    Optimizers: the step writes EVERY entity row.  A row-lazily stepped table (``optim.Adam(lazy_rows=True)``) is flushed first and
+    its step then takes the route "touched rows unknown -> dense"; ``optim.Adagrad`` uses its all-rows form."""
+
+    def __init__(self, model, temperature=1.0, regularizer=None):
+        if model.name not in ONE_VS_ALL_MODELS:
+            raise NotImplementedError(f"OneVsAllStep covers {' and '.join(ONE_VS_ALL_MODELS)}, whose all-entity block is one matrix "
+                                      f"product, not {model.name}: train it with the sampled softmax, losses.CrossEntropy")
+        self.temperature = ns_losses._checked("temperature", temperature, positive=True)
+        self.model, self.regularizer, self.regularization = model, regularizer, None
+
+    def sampled(self, sample, weight, sampler, mode, weight_sum=None):
+        """The other steps' entry point (``compose.Pipeline`` calls it): nothing is drawn from ``sampler``."""
+        return self(sample, weight, mode, weight_sum=weight_sum)
+
+    def __call__(self, sample, weight, mode, weight_sum=None):
+        m = self.model
+        mode_id = _side(mode)
+        if sample.dim() != 2 or sample.shape[1] != 3 or sample.shape[0] < 1:
+            raise ValueError("sample must be [B, 3] with B >= 1")
+        if weight is not None and weight.shape != (sample.shape[0],):
+            raise ValueError("weight must be [B]")
+        sample = _hip.contiguous(sample, torch.int64)
+        weight = None if weight is None else _hip.contiguous(weight, torch.float32)
+        _hip.require_device(m.entity_embedding, sample, weight)
+        B, dev = sample.shape[0], sample.device
+        for p in (m.entity_embedding, m.relation_embedding):
+            lazy = _links.owner(p)
+            if lazy is not None:  # every row is read and written: what is pending is applied, which rows were written is "unknown"
+                lazy.before_forward(p, None)
+                _links.record(p).wrote = True
+        m._launch_id_check(sample, None)
+        pos = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _all_workspace(m, B)
+        gr = grad_buffers(m)
+        with _hip.on_device(dev):
+            _hip.check(_hip.lib().mkb_all_step(m._tables(), gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, self.temperature,
+                                               _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
+                                               _hip.stream_ptr()), "mkb_all_step")
+        self.positive_score = pos
+        return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)

@@ -1,5 +1,6 @@
 from .adversarial import Adversarial
 from .kl_divergence import KlDivergence
 from .ns_losses import CrossEntropy, MarginRanking, PairwiseLogistic
+from .one_vs_all import OneVsAll
 
-__all__ = ["Adversarial", "KlDivergence", "MarginRanking", "PairwiseLogistic", "CrossEntropy"]
+__all__ = ["Adversarial", "KlDivergence", "MarginRanking", "PairwiseLogistic", "CrossEntropy", "OneVsAll"]

@@ -343,6 +343,28 @@ class BaseModel(Base):
             block[:, :, col] = cand
             return self(block)
 
+    def score_all(self, sample, mode):
+        """float32 ``[B, n_entity]``: ``out[i, e]`` is the score of ``sample[i]`` with its tail (``'tail-batch'``; its head for
+        ``'head-batch'``) replaced by entity ``e`` -- the bits ``Evaluation.ranks(..., with_scores=True)`` hands out -- and
+        differentiable with respect to both tables (the 1vsAll objective: ``losses.OneVsAll()(scores, target)``).  ComplEx and
+        DistMult, whose all-entity block is one matrix product with a dense backward; ids are handled as in ``forward``."""
+        from ..fused import ONE_VS_ALL_MODELS, score_all
+
+        if self.name not in ONE_VS_ALL_MODELS:
+            raise NotImplementedError(f"score_all is differentiable for {' and '.join(ONE_VS_ALL_MODELS)} only, not {self.name}: "
+                                      "Evaluation.ranks(..., with_scores=True) gives the same block without a backward")
+        if _hip.mode_id(mode) == _hip.MODE_DEFAULT:
+            raise ValueError(f"score_all scores one side of a triple: mode must be 'head-batch' or 'tail-batch', not {mode!r}")
+        _hip.require_device(self.entity_embedding, sample)
+        if sample.dim() != 2 or sample.shape[1] != 3 or sample.shape[0] < 1:
+            raise ValueError("sample must be [B, 3] with B >= 1")
+        sample = _hip.contiguous(sample, torch.int64)
+        if VALIDATE_IDS:
+            self._launch_id_check(sample, None)
+        if _links.owner(self.entity_embedding) is not None or _links.owner(self.relation_embedding) is not None:
+            self._make_current(sample, None)  # every entity row is read
+        return score_all(self, sample, mode)
+
     # ------------------------------------------------------------------ id validation
     def _launch_candidate_check(self, sample, cand, col):
         """``_launch_id_check`` for ``score_candidates``: the two columns of ``sample`` that are read, and the candidates against
