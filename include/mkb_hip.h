@@ -624,6 +624,35 @@ int mkb_all_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64
 int mkb_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
                  float temperature, const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- KvsAll: multi-label binary cross entropy over ALL entities, ComplEx and DistMult --------------------------------------
+ * The 1-N recipe of ConvE / TuckER and of the reference's losses.BCEWithLogitsLoss, on the 1vsAll step's products;
+ * mkb_amd/csrc/score_all.hip.  New symbols under ABI 8: the version is not bumped (symbols are only added).
+ *   y_ij = (1 - eps) [j in A_i] + eps / N,   row_i = c sum_{j < N} (softplus(s_ij) - y_ij s_ij),   c = 1 / N or 1 (sum_over_entities),
+ *   loss = sum_i w_i row_i / W,   dS_ij = (w_i c / W) (sigmoid(s_ij) - y_ij),   N = n_entity, eps = smoothing
+ *   over sample [B, 3] in MKB_MODE_TAIL (query q_i = h_i n_relation + r_i, pos the score of t_i) or MKB_MODE_HEAD (q_i = t_i
+ *   n_relation + r_i, pos the score of h_i).  A_i, the labels of row i: keys [n_keys] is the ascending int64 array of the known
+ *   triples in the mode's ordering ((h R + r) N + t for tail-batch, (t R + r) N + h for head-batch: the filter arrays of mkb_rank),
+ *   the row's labels are its keys in [q_i N, (q_i + 1) N), label column = key - q_i N.  A query without any key is legal (all of
+ *   its labels are eps / N), so are two rows with one query; the row's own target need not be a label.  weight, W, weight_sum: as
+ *   for the 1vsAll calls.  TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED.
+ *   mkb_all_bce: one pass per row over a block S [B, ld] of which the first N columns count.  Writes loss [1] and pos [B] (the
+ *   target's score, read before anything is overwritten) and OVERWRITES S with dS; columns N .. ld - 1 take no part in the sums
+ *   and are written as exactly 0.  softplus(s) = max(s, 0) + log1p(exp(-|s|)): finite for any finite score.  Fixed-order
+ *   reductions, no float atomics.  scratch: 1 + B floats (device).  An id outside its table counts as the nearest row (no label
+ *   column leaves the row): the glue flags it with mkb_check_ids.
+ *   mkb_all_kvs_step: forward, this loss and the backward of mkb_all_step in one call, the score block staying in the workspace;
+ *   pos [B] out; gradients accumulate into gr as for mkb_all_step, two runs give the same bits.
+ *   ws: mkb_all_step_workspace_bytes(tb, B) bytes, the 1vsAll step's.  A null pointer (keys may be null only with n_keys == 0),
+ *   n_keys < 0, smoothing outside [0, 1) or not finite, a mode other than head-/tail-batch, B < 1, ld < N, the size limits of the
+ *   1vsAll calls, (n_entity * n_relation + n_relation) * n_entity past 2^63 - 1, a short or misaligned workspace, an unknown
+ *   model -> MKB_ERR_INVALID before any launch. */
+int mkb_all_bce(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, int mode, int64_t n_relation, const int64_t *keys,
+                int64_t n_keys, const float *weight, const float *weight_sum, float smoothing, int sum_over_entities, float *loss,
+                float *pos, float *scratch, void *stream);
+int mkb_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
+                     const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities, const float *weight_sum, float *loss,
+                     float *pos, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

@@ -13,8 +13,8 @@ README, or ``mkb_amd.optim.Adam``).
 import torch
 
 from ..datasets.device import DeviceBatches
-from ..fused import FusedTrainStep, OneVsAllStep, PooledLossStep, pooled_supported
-from ..losses import Adversarial, CrossEntropy, MarginRanking, OneVsAll, PairwiseLogistic
+from ..fused import FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep, pooled_supported
+from ..losses import Adversarial, CrossEntropy, KvsAll, MarginRanking, OneVsAll, PairwiseLogistic
 from ..models.base import BaseModel
 from ..sampling import NegativeSampling
 from ..utils import Bar, RollingMean
@@ -100,10 +100,16 @@ class Pipeline:
     def _fused_step_for(self, model, dataset, sampling, optimizer, loss):
         """``FusedTrainStep`` (``Adversarial``) or ``PooledLossStep`` (``MarginRanking`` / ``PairwiseLogistic`` / ``CrossEntropy``)
         when model, sampler and loss are the mkb_amd ones on a ROCm device, else None.  ``losses.OneVsAll`` always takes
-        ``OneVsAllStep``: it has no explicit sequence (no negatives are drawn: ``sampling`` is not used)."""
+        ``OneVsAllStep`` and ``losses.KvsAll`` always ``KvsAllStep``: they have no explicit sequence (no negatives are drawn:
+        ``sampling`` is not used).  A ``KvsAll`` without triples of its own is labelled by the training triples of ``dataset``
+        (``DeviceBatches`` hands out the wrapped dataset's)."""
         if isinstance(loss, OneVsAll):
             self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
             return OneVsAllStep(model, loss.temperature, regularizer=self.regularizer)
+        if isinstance(loss, KvsAll):
+            self._borrowed = []
+            triples = dataset.train if loss.true_triples is None else loss.true_triples
+            return KvsAllStep(model, triples, loss.label_smoothing, loss.reduction, regularizer=self.regularizer)
         if not (self.fuse and isinstance(model, BaseModel) and isinstance(sampling, NegativeSampling)
                 and type(loss) in (Adversarial,) + _POOLED_LOSSES and model.entity_embedding.is_cuda
                 and pooled_supported(model, dataset.batch_size, sampling.size)):

@@ -16,11 +16,14 @@
 //             (a query entity's row: together with its row of dE, in one rounded addition -- all_stash_kernel).
 // No float atomics anywhere: loss and both gradient tables have the same bits run to run, and gradient buffers that held
 // something end as that + the step's result, bit for bit.
+// KvsAll (include/mkb_hip.h, "KvsAll") is the same step around another loss kernel, all_bce_kernel: the multi-label binary cross
+// entropy with label smoothing, its labels read from the sorted key arrays of the filtered ranking.
 #include "common.h"
 #include "loss_math.h"
 #include "pair_sort.h"
 #include "rank_all.h"
-#include "score_row.h"  // table_row
+#include "sampler_draw.h"  // lower_bound_dev
+#include "score_row.h"     // table_row
 
 #include <algorithm>
 #include <math.h>
@@ -107,6 +110,79 @@ static void all_softmax_launch(float *S, int64_t B, int64_t N, int64_t ld, const
     const size_t lds = N <= kAllStageCols ? (size_t)N * sizeof(float) : 0;
     hipLaunchKernelGGL(all_softmax_kernel, dim3((unsigned)B), dim3(256), lds, st, S, (int)B, N, ld, target, tstride, weight, scal_in, scal,
                        1.f / T, pos, rowpart);
+    hipLaunchKernelGGL(all_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B, weight_sum ? weight_sum : scal, loss);
+}
+
+// ---- KvsAll (include/mkb_hip.h, "KvsAll"): multi-label binary cross entropy over the whole row, labels smoothed by eps,
+//     y_ij = (1 - eps) [j in A_i] + eps / N,   row_i = c sum_{j < N} (softplus(s_ij) - y_ij s_ij),   dS_ij = (w_i c / W) (sigmoid(s_ij) - y_ij)
+// A_i: the keys of the row's query q = e R + r (e: the head; the tail for head-batch) in the sorted key array of its side
+// (utils/true_keys.py), the contiguous range [q N, (q + 1) N); label column = key - q N.  One 256-lane workgroup per row, no LDS
+// staging (every column is read once and written once): the label columns' scores are summed BEFORE anything is overwritten, one
+// dense pass writes coef (sigmoid(s) - eps / N), one sparse pass takes coef (1 - eps) off the label columns (keys are unique: one
+// writer per element).  scal / scal_out / rowpart: as for all_softmax_kernel.
+__global__ __launch_bounds__(256) void all_bce_kernel(float *__restrict__ S, int B, int64_t N, int64_t ld, const int64_t *__restrict__ sample,
+                                                      int head, int64_t R, const int64_t *__restrict__ keys, int64_t n_keys,
+                                                      const float *__restrict__ w, const float *__restrict__ scal,
+                                                      float *__restrict__ scal_out, float eps, float c, float *__restrict__ pos,
+                                                      float *__restrict__ rowpart) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const int64_t i = blockIdx.x;
+    float *row = S + i * ld;
+    const int64_t *s = sample + 3 * i;
+    // (an id outside its table counts as the nearest row, so that no label column leaves the row: the glue flags it, mkb_check_ids)
+    const int64_t q = table_row(s[head ? 2 : 0], N) * R + table_row(s[1], R), base = q * N;
+    const int64_t t = table_row(s[head ? 0 : 2], N);
+    const int64_t lo = lower_bound_dev(keys, n_keys, base), hi = lower_bound_dev(keys, n_keys, base + N);  // (uniform; empty: lo == hi)
+    const float p_i = row[t];  // before anything is overwritten: every lane reads it here, the barriers below come first
+    const float wi = w ? w[i] : 1.f;
+
+    float lab = 0.f;
+    for (int64_t k = lo + tid; k < hi; k += 256) lab += row[table_row(keys[k] - base, N)];
+    const float W = scal ? scal[0] : (w ? weight_sum_block(w, B, red) : (float)B);
+    if (!scal && blockIdx.x == 0 && tid == 0) scal_out[0] = W;
+    lab = block_sum_256(lab, red);  // lane-strided partial sums, then the fixed tree; its barriers stand between the reads above and the writes below
+
+    const float y0 = eps / (float)N, coef = wi * c / W;
+    float sp = 0.f, sv = 0.f;
+    auto seed = [&](float v) {
+        const float e = expf(-fabsf(v));  // in (0, 1]: softplus and sigmoid stay finite for any finite score
+        sp += fmaxf(v, 0.f) + log1pf(e);
+        sv += v;
+        return coef * ((v >= 0.f ? 1.f : e) / (1.f + e) - y0);
+    };
+    int64_t j = tid;
+    for (; j + 768 < N; j += 1024) {  // four strides' loads in flight at a time (a plain loop is one round trip per column)
+        float v[4];
+#pragma unroll
+        for (int z = 0; z < 4; ++z) v[z] = row[j + 256 * z];
+#pragma unroll
+        for (int z = 0; z < 4; ++z) row[j + 256 * z] = seed(v[z]);
+    }
+    for (; j < N; j += 256) row[j] = seed(row[j]);
+    for (int64_t p = N + tid; p < ld; p += 256) row[p] = 0.f;  // the forward's pad columns
+    sp = block_sum_256(sp, red);
+    sv = block_sum_256(sv, red);  // (the dense pass is behind these barriers)
+    const float off = coef * (1.f - eps);
+    for (int64_t k = lo + tid; k < hi; k += 256) row[table_row(keys[k] - base, N)] -= off;
+    if (tid == 0) {
+        pos[i] = p_i;
+        rowpart[i] = wi * c * (sp - y0 * sv - (1.f - eps) * lab);
+    }
+}
+
+// scratch: [0] = W, [1 .. B] = the rows' terms (as all_softmax_launch)
+static void all_bce_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, bool head, int64_t R, const int64_t *keys,
+                           int64_t n_keys, const float *weight, const float *weight_sum, float eps, bool sum_over_entities, float *loss,
+                           float *pos, float *scratch, hipStream_t st) {
+    float *scal = scratch, *rowpart = scratch + 1;
+    const float *scal_in = weight_sum;
+    if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one launch in front
+        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
+        scal_in = scal;
+    }
+    hipLaunchKernelGGL(all_bce_kernel, dim3((unsigned)B), dim3(256), 0, st, S, (int)B, N, ld, sample, head ? 1 : 0, R, keys, n_keys, weight,
+                       scal_in, scal, eps, sum_over_entities ? 1.f : 1.f / (float)N, pos, rowpart);
     hipLaunchKernelGGL(all_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B, weight_sum ? weight_sum : scal, loss);
 }
 
@@ -291,6 +367,18 @@ static int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const 
     return MKB_OK;
 }
 
+// what the two KvsAll entry points check of their label arguments (N, R: the table sizes the keys were built for)
+static int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n_keys, float eps) {
+    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "KvsAll needs head-batch or tail-batch");
+    MKB_REQUIRE(n_keys >= 0 && (keys || n_keys == 0), "keys may be null only with n_keys == 0, and n_keys must be >= 0");
+    MKB_REQUIRE(eps - eps == 0.f && eps >= 0.f && eps < 1.f, "the label smoothing must be finite and in [0, 1)");
+    int64_t nq, top;  // the largest value a range bound takes: ((N - 1) R + R - 1) N + N <= (N R + R) N
+    MKB_REQUIRE(N >= 1 && R >= 1 && !__builtin_mul_overflow(N, R, &nq) && !__builtin_add_overflow(nq, R, &nq) &&
+                    !__builtin_mul_overflow(nq, N, &top),
+                "(n_entity * n_relation + n_relation) * n_entity must fit a signed 64-bit key");
+    return MKB_OK;
+}
+
 }  // namespace mkb
 
 using namespace mkb;
@@ -356,6 +444,40 @@ extern "C" int mkb_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const
     auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
         ld_S = ld;
         all_softmax_launch(w.S, B, N, ld, sample + (head ? 0 : 2), 3, weight, weight_sum, temperature, loss, pos, w.scratch, st);
+    };
+    return dispatch_dot_model(tb->model, head, [&](auto m, auto h) {
+        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
+        return all_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, ld_S > N, P, w, st);
+    });
+}
+
+extern "C" int mkb_all_bce(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, int mode, int64_t n_relation,
+                           const int64_t *keys, int64_t n_keys, const float *weight, const float *weight_sum, float smoothing,
+                           int sum_over_entities, float *loss, float *pos, float *scratch, void *stream) {
+    if (int rc = softmax_check(S, B, N, ld, sample, 1, 1.f, loss, pos, scratch)) return rc;
+    if (int rc = bce_check(N, n_relation, mode, keys, n_keys, smoothing)) return rc;
+    all_bce_launch(S, B, N, ld, sample, mode == MKB_MODE_HEAD, n_relation, keys, n_keys, weight, weight_sum, smoothing,
+                   sum_over_entities != 0, loss, pos, scratch, (hipStream_t)stream);
+    MKB_LAUNCH_CHECK();
+    return MKB_OK;
+}
+
+extern "C" int mkb_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
+                                int mode, const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities,
+                                const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream) {
+    AllPlan P;
+    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
+    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
+    if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing)) return rc;
+    const AllWs w = all_carve(P, ws);
+    hipStream_t st = (hipStream_t)stream;
+    const bool head = mode == MKB_MODE_HEAD;
+    const int64_t N = tb->n_entity;
+    int64_t ld_S = 0;
+    auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
+        ld_S = ld;
+        all_bce_launch(w.S, B, N, ld, sample, head, tb->n_relation, keys, n_keys, weight, weight_sum, smoothing, sum_over_entities != 0,
+                       loss, pos, w.scratch, st);
     };
     return dispatch_dot_model(tb->model, head, [&](auto m, auto h) {
         if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;

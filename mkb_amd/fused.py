@@ -11,15 +11,18 @@
                         pooled entry points around ``mkb_ns_loss``, bypassing autograd.
 ``OneVsAllStep``     -- the 1vsAll step of ComplEx / DistMult (``losses.OneVsAll``): every entity scored for each row, the softmax
                         over the whole row and the dense backward in one call (``mkb_all_step``); no negatives are drawn.
+``KvsAllStep``       -- the KvsAll ("1-N") step of the same two models (``losses.KvsAll``): the same products around the multi-label
+                        binary cross entropy with label smoothing (``mkb_all_kvs_step``).
 ``score_all``        -- the ``[B, n_entity]`` block behind ``model.score_all``, differentiable (``mkb_all_score_fwd`` / ``_bwd``).
 """
 import torch
 
 from . import _gradshare, _hip, _links
-from .losses import ns_losses
+from .losses import kvs_all, ns_losses
 from .sampling.negative_sampling import PoolInfo
+from .utils.true_keys import true_keys
 
-__all__ = ["FusedTrainStep", "PooledLossStep", "OneVsAllStep", "pooled_forward", "pooled_supported", "score_all"]
+__all__ = ["FusedTrainStep", "PooledLossStep", "OneVsAllStep", "KvsAllStep", "pooled_forward", "pooled_supported", "score_all"]
 
 _workspaces = {}
 
@@ -330,21 +333,15 @@ def score_all(model, sample, mode):
     return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, model, sample, _side(mode))
 
 
-class OneVsAllStep:
-    """``loss = step(sample, weight, mode)``: the 1vsAll softmax step of ComplEx / DistMult.  Every entity is scored for each
-    ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``) and the cross entropy is taken over the whole row, at
-    ``temperature``; fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.  ``positive_score``
-    [B, 1] of the last call stays available.  One library call (``mkb_all_step``), no autograd, no negatives, no filtering of a
-    row's other known answers.  ``weight``: [B] or None (all ones); ``weight_sum`` and ``regularizer``: as for ``FusedTrainStep``.
+class _AllEntityStep:
+    """What the steps over the whole entity row share (``OneVsAllStep``, ``KvsAllStep``): the argument checks, the optimizer
+    protocol of a step that writes EVERY entity row, the id check, the outputs, the workspace and the regulariser hook.  A subclass
+    launches its one library call in ``_launch``."""
 
-    Optimizers: the step writes EVERY entity row.  A row-lazily stepped table (``optim.Adam(lazy_rows=True)``) is flushed first and
-    its step then takes the route "touched rows unknown -> dense"; ``optim.Adagrad`` uses its all-rows form."""
-
-    def __init__(self, model, temperature=1.0, regularizer=None):
+    def __init__(self, model, regularizer=None):
         if model.name not in ONE_VS_ALL_MODELS:
-            raise NotImplementedError(f"OneVsAllStep covers {' and '.join(ONE_VS_ALL_MODELS)}, whose all-entity block is one matrix "
-                                      f"product, not {model.name}: train it with the sampled softmax, losses.CrossEntropy")
-        self.temperature = ns_losses._checked("temperature", temperature, positive=True)
+            raise NotImplementedError(f"{type(self).__name__} covers {' and '.join(ONE_VS_ALL_MODELS)}, whose all-entity block is one "
+                                      f"matrix product, not {model.name}: train it with the sampled softmax, losses.CrossEntropy")
         self.model, self.regularizer, self.regularization = model, regularizer, None
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
@@ -373,8 +370,51 @@ class OneVsAllStep:
         ws = _all_workspace(m, B)
         gr = grad_buffers(m)
         with _hip.on_device(dev):
-            _hip.check(_hip.lib().mkb_all_step(m._tables(), gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, self.temperature,
-                                               _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
-                                               _hip.stream_ptr()), "mkb_all_step")
+            self._launch(m._tables(), gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws)
         self.positive_score = pos
         return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)
+
+
+class OneVsAllStep(_AllEntityStep):
+    """``loss = step(sample, weight, mode)``: the 1vsAll softmax step of ComplEx / DistMult.  Every entity is scored for each
+    ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``) and the cross entropy is taken over the whole row, at
+    ``temperature``; fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.  ``positive_score``
+    [B, 1] of the last call stays available.  One library call (``mkb_all_step``), no autograd, no negatives, no filtering of a
+    row's other known answers.  ``weight``: [B] or None (all ones); ``weight_sum`` and ``regularizer``: as for ``FusedTrainStep``.
+
+    Optimizers: the step writes EVERY entity row.  A row-lazily stepped table (``optim.Adam(lazy_rows=True)``) is flushed first and
+    its step then takes the route "touched rows unknown -> dense"; ``optim.Adagrad`` uses its all-rows form."""
+
+    def __init__(self, model, temperature=1.0, regularizer=None):
+        super().__init__(model, regularizer)
+        self.temperature = ns_losses._checked("temperature", temperature, positive=True)
+
+    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
+        _hip.check(_hip.lib().mkb_all_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, self.temperature,
+                                           _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
+                                           _hip.stream_ptr()), "mkb_all_step")
+
+
+class KvsAllStep(_AllEntityStep):
+    """``loss = step(sample, weight, mode)``: the KvsAll ("1-N") step of ComplEx / DistMult.  Every entity is scored for each
+    ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``) and the binary cross entropy is taken over the whole row
+    against the multi-hot labels of ALL the query's known answers in ``true_triples``, smoothed by ``label_smoothing``
+    (``losses.KvsAll`` has the formula); fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.
+    ``positive_score`` [B, 1] of the last call stays available.  One library call (``mkb_all_kvs_step``): the labels are read from
+    the sorted key arrays of the filtered ranking (``utils.true_keys``, built once), no [B, n_entity] label matrix exists.
+    Arguments of the call, optimizers and ``regularizer``: as for ``OneVsAllStep``."""
+
+    def __init__(self, model, true_triples, label_smoothing=0.0, reduction="mean", regularizer=None):
+        super().__init__(model, regularizer)
+        self.label_smoothing, self.reduction = kvs_all.checked_settings(label_smoothing, reduction)
+        if true_triples is None:
+            raise ValueError("KvsAllStep needs true_triples: the known triples its labels come from")
+        self.true_triples = true_triples
+
+    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
+        m = self.model
+        keys = true_keys(self.true_triples, sample.device, m.n_entity, m.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
+        _hip.check(_hip.lib().mkb_all_kvs_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, _hip.ptr(keys), keys.numel(),
+                                               self.label_smoothing, int(self.reduction == "sum"), _hip.ptr(weight_sum),
+                                               _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
+                   "mkb_all_kvs_step")

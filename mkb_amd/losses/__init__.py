@@ -1,6 +1,7 @@
 from .adversarial import Adversarial
 from .kl_divergence import KlDivergence
+from .kvs_all import KvsAll
 from .ns_losses import CrossEntropy, MarginRanking, PairwiseLogistic
 from .one_vs_all import OneVsAll
 
-__all__ = ["Adversarial", "KlDivergence", "MarginRanking", "PairwiseLogistic", "CrossEntropy", "OneVsAll"]
+__all__ = ["Adversarial", "KlDivergence", "MarginRanking", "PairwiseLogistic", "CrossEntropy", "OneVsAll", "KvsAll"]

@@ -2,13 +2,14 @@
 FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamma=9, Adam.
 
     python tools/train_fb15k237.py [--epochs 200] [--lr 5e-5] [--eval-every 50] [--model RotatE]
-                                   [--loss adversarial|margin|pairwise|softmax|onevsall] [--reg none|l2|n3] [--reg-weight 1e-3]
+                                   [--loss adversarial|margin|pairwise|softmax|onevsall|kvsall] [--reg none|l2|n3] [--reg-weight 1e-3]
                                    [--optimizer adam|adagrad]
 
 --loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
 --alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
 PooledLossStep, or onevsall (OneVsAll(--temperature) through OneVsAllStep: ComplEx / DistMult, every entity scored for each row, no
-negatives drawn; --size is then not used).  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
+negatives drawn; --size is then not used), or kvsall (KvsAllStep: the same two models, binary cross entropy against the multi-hot
+labels of every known answer in the training triples, --label-smoothing, --reduction mean|sum over the entities).  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
 handed to the step.  --optimizer: adam (the default: row-lazy optim.Adam) or adagrad (row-sparse optim.Adagrad; the literature's
 ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.
 
@@ -23,7 +24,7 @@ import torch
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from mkb_amd import datasets, evaluation, losses, models, optim, regularizers, sampling  # noqa: E402
-from mkb_amd.fused import FusedTrainStep, OneVsAllStep, PooledLossStep  # noqa: E402
+from mkb_amd.fused import FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep  # noqa: E402
 
 
 def main():
@@ -38,8 +39,10 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--dataset", default="Fb15k237")
-    ap.add_argument("--loss", default="adversarial", choices=["adversarial", "margin", "pairwise", "softmax", "onevsall"])
+    ap.add_argument("--loss", default="adversarial", choices=["adversarial", "margin", "pairwise", "softmax", "onevsall", "kvsall"])
     ap.add_argument("--temperature", type=float, default=1.0, help="--loss softmax / onevsall")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="--loss kvsall")
+    ap.add_argument("--reduction", default="mean", choices=["mean", "sum"], help="--loss kvsall: over the entities of a row")
     ap.add_argument("--reg", default="none", choices=["none", "l2", "n3"])
     ap.add_argument("--reg-weight", type=float, default=1e-3, help="--reg l2 / n3")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "adagrad"], help="optim.Adam(lazy_rows=True) or optim.Adagrad at --lr")
@@ -63,6 +66,8 @@ def main():
         step = FusedTrainStep(model, args.alpha, regularizer=reg)
     elif args.loss == "onevsall":
         step = OneVsAllStep(model, temperature=args.temperature, regularizer=reg)
+    elif args.loss == "kvsall":
+        step = KvsAllStep(model, ds.train, label_smoothing=args.label_smoothing, reduction=args.reduction, regularizer=reg)
     else:
         step = PooledLossStep(model, {"margin": lambda: losses.MarginRanking(margin=args.gamma, alpha=args.alpha),
                                       "pairwise": lambda: losses.PairwiseLogistic(margin=0.0, alpha=args.alpha),
@@ -90,7 +95,7 @@ def main():
             torch.cuda.synchronize()
             print(json.dumps({"epoch": epoch + 1, "steps": n_steps, "loss": float(loss.item()),
                               "train_seconds": round(t_train, 2),
-                              "triples_per_s": round(n_steps * args.batch * ((len(ds.entities) if args.loss == "onevsall" else args.size) + 1)
+                              "triples_per_s": round(n_steps * args.batch * ((len(ds.entities) if args.loss in ("onevsall", "kvsall") else args.size) + 1)
                                                      / t_train),
                               "eval_seconds": round(time.perf_counter() - t1, 2), "valid": valid, "test": test}), flush=True)
 
