@@ -30,6 +30,13 @@ def mode_id(mode):
     return MODE_HEAD if mode == "head-batch" else MODE_TAIL if mode == "tail-batch" else MODE_DEFAULT
 
 
+def side_id(mode, what):
+    """``mode_id`` where only the two batch strings are legal; ``what``: the caller's half of the message ("1vsAll scores")."""
+    if mode_id(mode) == MODE_DEFAULT:
+        raise ValueError(f"{what} one side of a triple: mode must be 'head-batch' or 'tail-batch', not {mode!r}")
+    return mode_id(mode)
+
+
 class Tables(Structure):
     _fields_ = [("model", c_int32), ("hidden_dim", c_int32), ("n_entity", c_int64), ("n_relation", c_int64),
                 ("entity_dim", c_int64), ("relation_dim", c_int64), ("ent", c_void_p), ("rel", c_void_p),

@@ -14,8 +14,9 @@
 // small terms, and every other entry carries the small factor t_ik.
 // One wave per row (the distributions of distillation/distillation.py:486-558 hold a few entities / relations, m is small);
 // correctly rounded expf / logf: this loss is compared with torch's CPU result at 1e-6.  Row partials are summed in a fixed
-// order by a second single-workgroup launch: bit-reproducible.
+// order by a second single-workgroup launch, the row losses' finish (loss_math.h) with c = 1 / (n m) and no W: bit-reproducible.
 #include "common.h"
+#include "loss_math.h"
 #include "model_math.h"
 
 // No fused multiply-add in this file: the row maximum is taken over the rounded logits s * (1 / T), and `s * inv_T - max` as one
@@ -78,16 +79,6 @@ __global__ __launch_bounds__(256) void kl_rows_kernel(const float *__restrict__ 
     if (lane == 0) rowpart[i] = kl;
 }
 
-__global__ __launch_bounds__(256) void kl_finish_kernel(const float *__restrict__ rowpart, int n, float scale, float *__restrict__ loss) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc += rowpart[i];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = (red[0] + red[1] + red[2] + red[3]) * scale;
-}
-
 }  // namespace mkb
 
 using namespace mkb;
@@ -101,7 +92,7 @@ extern "C" int mkb_kl_divergence(const float *student, const float *teacher, int
     ProfScope ps(MKB_PROF_LOSS, st);
     hipLaunchKernelGGL(kl_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, student, teacher, (int)n, (int)m, 1.f / T,
                        dstudent, dteacher, scratch);
-    hipLaunchKernelGGL(kl_finish_kernel, dim3(1), dim3(256), 0, st, scratch, (int)n, 1.f / ((float)n * (float)m), loss);
+    hipLaunchKernelGGL(row_loss_finish_kernel, dim3(1), dim3(256), 0, st, scratch, (int)n, 1.f / ((float)n * (float)m), nullptr, loss);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }

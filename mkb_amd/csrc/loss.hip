@@ -7,11 +7,11 @@
 // Optional column multiplicities cnt[i,j] (pooled path: column = pool position used cnt times by row i):
 //   softmax and the sums run over columns weighted by cnt; dneg_ij is the summed gradient of its copies.
 //
-// One launch up to 8192 rows: every workgroup (one wave per row, 4 rows) first reduces W itself with the fixed tree
-//   of loss_math.h (B / 256 loads per lane from L2; bit-identical in every workgroup), then row max / partition sum / weighted
-//   log-sigmoid sum with wave64 shuffle reductions, writes dpos, dneg and the per-row partial.  A second single-
-//   workgroup kernel sums the partials in a fixed order -- or, inside mkb_pool_step, the last workgroup of the row
-//   backward kernel does (adversarial_finish_block), so the fused step spends ONE launch on the loss.
+// The row-loss protocol of loss_math.h (RowLoss: W, the scratch, the launch in front of many rows, the finish): every workgroup
+//   (one wave per row, 4 rows) first takes W from it -- its weights requested ahead of the row's own loads --, then row max /
+//   partition sum / weighted log-sigmoid sum with wave64 shuffle reductions, writes dpos, dneg and the per-row partial.  The
+//   shared single-workgroup finish sums the partials in a fixed order (c = -0.5) -- or, inside mkb_pool_step, the last
+//   workgroup of the row backward kernel does (row_loss_finish_block), so the fused step spends ONE launch on the loss.
 //   No float atomics: the loss is bit-reproducible run to run.
 #include "common.h"
 #include "loss_math.h"
@@ -140,8 +140,7 @@ __global__ __launch_bounds__(TILE ? 512 : 256) void adversarial_rows_kernel(cons
     }
     // scal == nullptr: W is reduced here, by every workgroup alike (its loads and barriers run under the row's loads, which
     // were issued above); workgroup 0 publishes it for the finish step
-    const float W = scal ? scal[0] : weight_sum_block_ahead(w, B, red, wv);
-    if (!scal && blockIdx.x == 0 && threadIdx.x == 0) scal_out[0] = W;
+    const float W = row_loss_weight_sum(scal, scal_out, w, B, red, wv);
     if (!TILE && !live) return;
     if (live) {
     if (!staged) {
@@ -226,28 +225,17 @@ __global__ __launch_bounds__(TILE ? 512 : 256) void adversarial_rows_kernel(cons
     }
 }
 
-__global__ __launch_bounds__(256) void adversarial_finish_kernel(const float *__restrict__ rowpart, int B,
-                                                                 const float *__restrict__ scal, float *__restrict__ loss) {
-    __shared__ float red[4];
-    adversarial_finish_block(rowpart, B, scal, loss, red);
-}
-
 int adversarial_launch(const float *pos, const float *neg, const float *weight, const uint16_t *cnt, int64_t B, int64_t K,
                        float alpha, const float *weight_sum, float *loss, float *dpos, float *dneg, float *scratch,
-                       hipStream_t st, bool defer_finish, SeedLayout seeds, const GemmTail *neg_tail,
+                       hipStream_t st, RowLoss *deferred, SeedLayout seeds, const GemmTail *neg_tail,
                        int *occ, const int64_t *occ_sample, const int64_t *occ_pool) {
-    float *scal = scratch, *rowpart = scratch + 1;
     GemmTail nt{};
     if (neg_tail && (neg_tail->kind == 1 || neg_tail->kind == 3)) {
         if (K > kStageCols) return set_error(MKB_ERR_INVALID, "split-K scores can only ride rows of <= %d columns", kStageCols);
         nt = *neg_tail;
     }
-    const float *scal_in = weight_sum;  // W of the whole (sharded) batch when the caller supplies it
     ProfScope ps(MKB_PROF_LOSS, st);
-    if (!weight_sum && B > 8192) {      // too many rows for every workgroup to re-reduce W: one extra launch
-        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
-        scal_in = scal;
-    }
+    const RowLoss L = RowLoss::open(weight, weight_sum, B, scratch, st);
     if (seeds.log2_blocks >= 0) {  // tile-blocked seeds: one row tile per 512-lane workgroup, staged through LDS
         const int cap = 64 << (seeds.log2_blocks + seeds.log2_halves);
         if (cap < K) return set_error(MKB_ERR_INVALID, "blocked seed layout holds %d positions, the rows have %d", cap, (int)K);
@@ -256,17 +244,16 @@ int adversarial_launch(const float *pos, const float *neg, const float *weight, 
         static LdsOptIn lds_ok;  // more than 64 KB (pools of ~1000 positions and up): opt in once per device
         if (int rc = lds_ok.ensure(reinterpret_cast<const void *>(&adversarial_rows_kernel<true>), lds)) return rc;
         hipLaunchKernelGGL(adversarial_rows_kernel<true>, dim3((unsigned)((B + 7) / 8)), dim3(512), lds, st, pos, neg,
-                           weight, cnt, (int)B, (int)K, alpha, scal_in, scal, dpos, dneg, rowpart, seeds, nt, occ,
+                           weight, cnt, (int)B, (int)K, alpha, L.scal_in, L.scal_out, dpos, dneg, L.rowpart, seeds, nt, occ,
                            occ_sample, occ_pool);
     } else {
         const size_t lds = K <= kStageCols ? (size_t)K * 5 * 4 * 2 : 0;  // scores + multiplicities [K][5] of staged rows
         hipLaunchKernelGGL(adversarial_rows_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, st, pos, neg, weight, cnt,
-                           (int)B, (int)K, alpha, scal_in, scal, dpos, dneg, rowpart, seeds, nt, occ, occ_sample,
+                           (int)B, (int)K, alpha, L.scal_in, L.scal_out, dpos, dneg, L.rowpart, seeds, nt, occ, occ_sample,
                            occ_pool);
     }
-    if (!defer_finish)
-        hipLaunchKernelGGL(adversarial_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B,
-                           weight_sum ? weight_sum : scal, loss);
+    if (deferred) *deferred = L;
+    else L.finish(B, -0.5f, loss, st);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
@@ -281,5 +268,5 @@ extern "C" int mkb_adversarial(const float *pos, const float *neg, const float *
     MKB_REQUIRE(pos && neg && weight && loss && dpos && dneg && scratch, "null pointer");
     MKB_REQUIRE(B > 0 && K > 0 && B <= INT32_MAX && K <= INT32_MAX, "bad B / K");
     return adversarial_launch(pos, neg, weight, cnt, B, K, alpha, weight_sum, loss, dpos, dneg, scratch, (hipStream_t)stream,
-                              /*defer_finish=*/false);
+                              /*deferred=*/nullptr);
 }

@@ -10,8 +10,8 @@
 // c_ij: optional multiplicities (the pooled path: a column is a pool position).  A position with c_ij = 0 takes no part: its
 // score is loaded but never enters an expression (it may be NaN), its seed is written as 0.
 //
-// The shape of loss.hip: one wave per row, four rows per 256-lane workgroup, every workgroup reduces W itself with the fixed
-// tree of loss_math.h (up to 8192 rows; beyond, one launch in front), per-row partials, one finishing workgroup.  Rows of up to
+// The shape of loss.hip: one wave per row, four rows per 256-lane workgroup, W, the scratch and the finishing workgroup by the
+// row-loss protocol of loss_math.h (RowLoss), per-row partials.  Rows of up to
 // kNsStageCols columns are read from global memory once and kept in LDS ([row][column]: the 64 lanes of a column group hit 64
 // consecutive words) for the three passes (max, partition sums, seeds); longer rows re-read global memory.  Every exponent is
 // taken relative to the row maximum IN SCORE UNITS ((v - m) * scale): the subtraction is exact where it matters, and the
@@ -58,9 +58,7 @@ __global__ __launch_bounds__(256) void ns_loss_rows_kernel(const float *__restri
             s_e[j] = c;
         }
     }
-    // W: the caller's, or reduced here by every workgroup alike (bit-identical in each); workgroup 0 publishes it for the finish
-    const float W = scal ? scal[0] : (w ? weight_sum_block(w, B, red) : (float)B);
-    if (!scal && blockIdx.x == 0 && threadIdx.x == 0) scal_out[0] = W;
+    const float W = row_loss_weight_sum(scal, scal_out, w, B, red);
     if (!live) return;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
@@ -127,23 +125,12 @@ __global__ __launch_bounds__(256) void ns_loss_rows_kernel(const float *__restri
     }
 }
 
-// loss = sum_i rowpart[i] / W by one 256-lane workgroup: strided partial sums, then the fixed tree of block_sum_256
-__global__ __launch_bounds__(256) void ns_loss_finish_kernel(const float *__restrict__ rowpart, int B,
-                                                             const float *__restrict__ scal, float *__restrict__ loss) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < B; i += 256) acc += rowpart[i];
-    const float total = block_sum_256(acc, red);
-    if (threadIdx.x == 0) loss[0] = total / scal[0];
-}
-
 template <int KIND>
 static void ns_loss_launch_rows(const float *pos, const float *neg, const float *weight, const uint16_t *cnt, int B, int K,
-                                float param, float alpha, const float *scal_in, float *scal, float *dpos, float *dneg,
-                                float *rowpart, hipStream_t st) {
+                                float param, float alpha, const RowLoss &L, float *dpos, float *dneg, hipStream_t st) {
     const size_t lds = K <= kNsStageCols ? (size_t)K * kNsRows * 2 * sizeof(float) : 0;  // <= 32 KB
     hipLaunchKernelGGL(ns_loss_rows_kernel<KIND>, dim3((unsigned)(((int64_t)B + kNsRows - 1) / kNsRows)), dim3(256), lds, st, pos,
-                       neg, weight, cnt, B, K, param, alpha, scal_in, scal, dpos, dneg, rowpart);
+                       neg, weight, cnt, B, K, param, alpha, L.scal_in, L.scal_out, dpos, dneg, L.rowpart);
 }
 
 }  // namespace mkb
@@ -160,24 +147,19 @@ extern "C" int mkb_ns_loss(int kind, const float *pos, const float *neg, const f
     MKB_REQUIRE(alpha >= 0.f && alpha - alpha == 0.f, "alpha must be finite and >= 0");
     MKB_REQUIRE(kind != MKB_LOSS_SOFTMAX || param > 0.f, "the softmax temperature must be > 0");
     hipStream_t st = (hipStream_t)stream;
-    float *scal = scratch, *rowpart = scratch + 1;
-    const float *scal_in = weight_sum;  // W of the whole (sharded) batch when the caller supplies it
     ProfScope ps(MKB_PROF_LOSS, st);
-    if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one extra launch
-        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
-        scal_in = scal;
-    }
+    const RowLoss L = RowLoss::open(weight, weight_sum, B, scratch, st);
     switch (kind) {
         case MKB_LOSS_MARGIN:
-            ns_loss_launch_rows<MKB_LOSS_MARGIN>(pos, neg, weight, cnt, (int)B, (int)K, param, alpha, scal_in, scal, dpos, dneg, rowpart, st);
+            ns_loss_launch_rows<MKB_LOSS_MARGIN>(pos, neg, weight, cnt, (int)B, (int)K, param, alpha, L, dpos, dneg, st);
             break;
         case MKB_LOSS_PAIR_LOGISTIC:
-            ns_loss_launch_rows<MKB_LOSS_PAIR_LOGISTIC>(pos, neg, weight, cnt, (int)B, (int)K, param, alpha, scal_in, scal, dpos, dneg, rowpart, st);
+            ns_loss_launch_rows<MKB_LOSS_PAIR_LOGISTIC>(pos, neg, weight, cnt, (int)B, (int)K, param, alpha, L, dpos, dneg, st);
             break;
         default:
-            ns_loss_launch_rows<MKB_LOSS_SOFTMAX>(pos, neg, weight, cnt, (int)B, (int)K, param, alpha, scal_in, scal, dpos, dneg, rowpart, st);
+            ns_loss_launch_rows<MKB_LOSS_SOFTMAX>(pos, neg, weight, cnt, (int)B, (int)K, param, alpha, L, dpos, dneg, st);
     }
-    hipLaunchKernelGGL(ns_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B, weight_sum ? weight_sum : scal, loss);
+    L.finish(B, 1.f, loss, st);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }

@@ -13,7 +13,7 @@
 //      run's weights (lane-strided partial sums in run order, then the fixed tree of block_sum_256), reads the row once with
 //      16-byte loads where the dimension allows, adds lambda c f'(row) * scale to the gradient row -- a single writer per row, plain
 //      vector stores, no atomics -- and writes the row's share of the value to its slot of `part` (0 for the other positions);
-//   3. one workgroup sums the 3 B slots in a fixed order.
+//   3. one workgroup sums the 3 B slots in a fixed order (the row losses' finish, loss_math.h, with c = 1 and no W).
 // Nothing is accumulated with float atomics, so the value and both gradient tables have the same bits run to run, and a batch
 // that puts every occurrence on one relation row (FB15k-237: ~4 per row at B = 1024; one relation: all B) costs one row write.
 #include "common.h"
@@ -38,7 +38,7 @@ struct RegArgs {
     const int *keys, *vals;   // the sorted occurrence list: row keys (relations: n_entity + r) and occurrence indices
     int n, B, n_entity;
     const float *w;           // [B] or null
-    const float *scal;        // W on the device, or null: every workgroup reduces it from w (or takes B)
+    const float *scal;        // W on the device, or null: every workgroup reduces it from w (or takes B): RowLoss::scal_in
     const float *scale;       // upstream gradient on the device, or null = 1
     float *part;              // [n] or null (gradient only)
     int p;
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void reg_rows_kernel(RegArgs A) {
     // the run's weights: lane-strided in run order (a lane stops at the first key that is not the run's), then the fixed tree
     float acc = 0.f;
     for (int j = pos + (int)threadIdx.x; j < A.n && A.keys[j] == key; j += 256) acc += A.w ? A.w[A.vals[j] % A.B] : 1.f;
-    const float W = A.scal ? A.scal[0] : (A.w ? weight_sum_block(A.w, A.B, red) : (float)A.B);
+    const float W = row_loss_weight_sum(A.scal, A.w, A.B, red);  // (nothing to publish: the finish adds the slots up as they are)
     const float c = block_sum_256(acc, red) / W;
     const float cg = T.lambda * c * (A.scale ? A.scale[0] : 1.f);
     const int64_t row = is_rel ? key - A.n_entity : key;  // (a row of its table: the keys were clamped, pair_sort.hip)
@@ -141,15 +141,6 @@ __global__ __launch_bounds__(256) void reg_rows_kernel(RegArgs A) {
         s = block_sum_256(s, red);
         if (threadIdx.x == 0) A.part[pos] = T.lambda * c * s;
     }
-}
-
-// value = the n slots by one 256-lane workgroup: strided partial sums, then the fixed tree of block_sum_256
-__global__ __launch_bounds__(256) void reg_rows_finish_kernel(const float *__restrict__ part, int n, float *__restrict__ value) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc += part[i];
-    const float total = block_sum_256(acc, red);
-    if (threadIdx.x == 0) value[0] = total;
 }
 
 constexpr int64_t kRegMaxB = (int64_t)1 << 30;
@@ -228,15 +219,12 @@ extern "C" int mkb_reg_rows(const mkb_tables_t *tb, const mkb_grads_t *gr, const
     A.ent = reg_table(tb->ent, gr ? gr->g_ent : nullptr, tb->entity_dim, tb->hidden_dim, halves_e, p, lambda_ent);
     A.rel = reg_table(tb->rel, gr ? gr->g_rel : nullptr, tb->relation_dim, tb->hidden_dim, halves_r, p, lambda_rel);
     A.n = n; A.B = (int)B; A.n_entity = (int)tb->n_entity;
-    A.w = weight; A.scal = weight_sum; A.scale = scale; A.p = p;
+    A.w = weight; A.scale = scale; A.p = p;
     A.part = value ? (float *)((unsigned char *)ws + P.part_off) : nullptr;
-    if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one launch in front
-        float *scal = (float *)((unsigned char *)ws + P.scal_off);
-        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
-        A.scal = scal;
-    }
+    // (W only: the value's slots are one per occurrence, in the workspace's own segment)
+    A.scal = RowLoss::open(weight, weight_sum, B, (float *)((unsigned char *)ws + P.scal_off), st).scal_in;
     hipLaunchKernelGGL(reg_rows_kernel, dim3((unsigned)n), dim3(256), 0, st, A);
-    if (value) hipLaunchKernelGGL(reg_rows_finish_kernel, dim3(1), dim3(256), 0, st, A.part, n, value);
+    if (value) hipLaunchKernelGGL(row_loss_finish_kernel, dim3(1), dim3(256), 0, st, A.part, n, 1.f, nullptr, value);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }

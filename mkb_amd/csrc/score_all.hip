@@ -18,6 +18,9 @@
 // something end as that + the step's result, bit for bit.
 // KvsAll (include/mkb_hip.h, "KvsAll") is the same step around another loss kernel, all_bce_kernel: the multi-label binary cross
 // entropy with label smoothing, its labels read from the sorted key arrays of the filtered ranking.
+// Written once for both: the step (all_step: carve, forward, the loss on the block, backward) and the launch of "a loss
+// kernel on the block" (all_loss_launch), which runs it inside the row-loss protocol of loss_math.h (RowLoss: W, the scratch, the
+// launch in front of many rows, the finish).
 #include "common.h"
 #include "loss_math.h"
 #include "pair_sort.h"
@@ -42,7 +45,7 @@ __device__ __forceinline__ float block_max_256(float v, float *red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// scal: W on the device, or null: every workgroup reduces it from w alike (or takes B) and workgroup 0 publishes it in scal_out
+// scal / scal_out / rowpart: the row-loss protocol (RowLoss, row_loss_weight_sum)
 __global__ __launch_bounds__(256) void all_softmax_kernel(float *__restrict__ S, int B, int64_t N, int64_t ld,
                                                           const int64_t *__restrict__ target, int64_t tstride,
                                                           const float *__restrict__ w, const float *__restrict__ scal,
@@ -64,8 +67,7 @@ __global__ __launch_bounds__(256) void all_softmax_kernel(float *__restrict__ S,
         m = fmaxf(m, v);
         if (staged) s_row[j] = v;
     }
-    const float W = scal ? scal[0] : (w ? weight_sum_block(w, B, red) : (float)B);
-    if (!scal && blockIdx.x == 0 && tid == 0) scal_out[0] = W;
+    const float W = row_loss_weight_sum(scal, scal_out, w, B, red);
     m = block_max_256(m, red);
 
     // every exponent relative to the row maximum in score units: the row is (m - pos) / T + log Z with Z >= 1
@@ -88,29 +90,21 @@ __global__ __launch_bounds__(256) void all_softmax_kernel(float *__restrict__ S,
     }
 }
 
-// loss = sum_i rowpart[i] / W by one 256-lane workgroup: strided partial sums, then the fixed tree of block_sum_256
-__global__ __launch_bounds__(256) void all_loss_finish_kernel(const float *__restrict__ rowpart, int B, const float *__restrict__ scal,
-                                                              float *__restrict__ loss) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < B; i += 256) acc += rowpart[i];
-    const float total = block_sum_256(acc, red);
-    if (threadIdx.x == 0) loss[0] = total / scal[0];
+// A loss kernel on the block inside the row-loss protocol: run(L) launches it with L.scal_in, L.scal_out and L.rowpart
+template <class Run>
+static void all_loss_launch(const float *weight, const float *weight_sum, int64_t B, float *loss, float *scratch, hipStream_t st, Run &&run) {
+    const RowLoss L = RowLoss::open(weight, weight_sum, B, scratch, st);
+    run(L);
+    L.finish(B, 1.f, loss, st);
 }
 
-// scratch: [0] = W, [1 .. B] = the rows' terms
 static void all_softmax_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride, const float *weight,
                                const float *weight_sum, float T, float *loss, float *pos, float *scratch, hipStream_t st) {
-    float *scal = scratch, *rowpart = scratch + 1;
-    const float *scal_in = weight_sum;
-    if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one launch in front
-        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
-        scal_in = scal;
-    }
-    const size_t lds = N <= kAllStageCols ? (size_t)N * sizeof(float) : 0;
-    hipLaunchKernelGGL(all_softmax_kernel, dim3((unsigned)B), dim3(256), lds, st, S, (int)B, N, ld, target, tstride, weight, scal_in, scal,
-                       1.f / T, pos, rowpart);
-    hipLaunchKernelGGL(all_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B, weight_sum ? weight_sum : scal, loss);
+    all_loss_launch(weight, weight_sum, B, loss, scratch, st, [&](const RowLoss &L) {
+        const size_t lds = N <= kAllStageCols ? (size_t)N * sizeof(float) : 0;
+        hipLaunchKernelGGL(all_softmax_kernel, dim3((unsigned)B), dim3(256), lds, st, S, (int)B, N, ld, target, tstride, weight, L.scal_in,
+                           L.scal_out, 1.f / T, pos, L.rowpart);
+    });
 }
 
 // ---- KvsAll (include/mkb_hip.h, "KvsAll"): multi-label binary cross entropy over the whole row, labels smoothed by eps,
@@ -139,8 +133,7 @@ __global__ __launch_bounds__(256) void all_bce_kernel(float *__restrict__ S, int
 
     float lab = 0.f;
     for (int64_t k = lo + tid; k < hi; k += 256) lab += row[table_row(keys[k] - base, N)];
-    const float W = scal ? scal[0] : (w ? weight_sum_block(w, B, red) : (float)B);
-    if (!scal && blockIdx.x == 0 && tid == 0) scal_out[0] = W;
+    const float W = row_loss_weight_sum(scal, scal_out, w, B, red);
     lab = block_sum_256(lab, red);  // lane-strided partial sums, then the fixed tree; its barriers stand between the reads above and the writes below
 
     const float y0 = eps / (float)N, coef = wi * c / W;
@@ -171,19 +164,13 @@ __global__ __launch_bounds__(256) void all_bce_kernel(float *__restrict__ S, int
     }
 }
 
-// scratch: [0] = W, [1 .. B] = the rows' terms (as all_softmax_launch)
 static void all_bce_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, bool head, int64_t R, const int64_t *keys,
                            int64_t n_keys, const float *weight, const float *weight_sum, float eps, bool sum_over_entities, float *loss,
                            float *pos, float *scratch, hipStream_t st) {
-    float *scal = scratch, *rowpart = scratch + 1;
-    const float *scal_in = weight_sum;
-    if (!weight_sum && weight && B > 8192) {  // too many rows for every workgroup to re-reduce W: one launch in front
-        hipLaunchKernelGGL(weight_sum_kernel, dim3(1), dim3(256), 0, st, weight, (int)B, scal);
-        scal_in = scal;
-    }
-    hipLaunchKernelGGL(all_bce_kernel, dim3((unsigned)B), dim3(256), 0, st, S, (int)B, N, ld, sample, head ? 1 : 0, R, keys, n_keys, weight,
-                       scal_in, scal, eps, sum_over_entities ? 1.f : 1.f / (float)N, pos, rowpart);
-    hipLaunchKernelGGL(all_loss_finish_kernel, dim3(1), dim3(256), 0, st, rowpart, (int)B, weight_sum ? weight_sum : scal, loss);
+    all_loss_launch(weight, weight_sum, B, loss, scratch, st, [&](const RowLoss &L) {
+        hipLaunchKernelGGL(all_bce_kernel, dim3((unsigned)B), dim3(256), 0, st, S, (int)B, N, ld, sample, head ? 1 : 0, R, keys, n_keys,
+                           weight, L.scal_in, L.scal_out, eps, sum_over_entities ? 1.f : 1.f / (float)N, pos, L.rowpart);
+    });
 }
 
 // ---- query chain: dQ -> the query's entity row (h; t for head-batch) and relation row, one writer per distinct row
@@ -329,15 +316,17 @@ static int all_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t 
     return MKB_OK;
 }
 
-// f(std::integral_constant<int, MODEL>{}, std::bool_constant<HEAD>{}) for the two models whose all-entity block is one product
+// dispatch_model_side (common.h) for the two models whose all-entity block is one product; the others are refused
 template <class F>
 static int dispatch_dot_model(int model, bool head, F &&f) {
-    auto side = [&](auto m) { return head ? f(m, std::true_type{}) : f(m, std::false_type{}); };
-    if (model == MKB_COMPLEX) return side(std::integral_constant<int, MKB_COMPLEX>{});
-    if (model == MKB_DISTMULT) return side(std::integral_constant<int, MKB_DISTMULT>{});
-    return set_error(MKB_ERR_UNSUPPORTED,
-                     "1vsAll covers ComplEx and DistMult, whose all-entity block is one matrix product; for TransE, RotatE and pRotatE "
-                     "use the sampled softmax (losses.CrossEntropy)");
+    if (model != MKB_COMPLEX && model != MKB_DISTMULT)
+        return set_error(MKB_ERR_UNSUPPORTED,
+                         "1vsAll covers ComplEx and DistMult, whose all-entity block is one matrix product; for TransE, RotatE and "
+                         "pRotatE use the sampled softmax (losses.CrossEntropy)");
+    return dispatch_model_side(model, head, [&](auto m, auto h) {  // (no kernels are instantiated for the models refused above)
+        if constexpr (decltype(m)::value == MKB_COMPLEX || decltype(m)::value == MKB_DISTMULT) return f(m, h);
+        else return (int)MKB_ERR_UNSUPPORTED;
+    });
 }
 
 // what every entry point that takes tables, a batch and the workspace checks, in this order
@@ -377,6 +366,24 @@ static int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n
                     !__builtin_mul_overflow(nq, N, &top),
                 "(n_entity * n_relation + n_relation) * n_entity must fit a signed 64-bit key");
     return MKB_OK;
+}
+
+// The step behind mkb_all_step and mkb_all_kvs_step, whose checks (all_check among them) have passed: the forward block, the loss
+// on it -- loss(S, ld, scratch) launches it from the forward's finish and leaves dS in S --, the backward.
+template <class Loss>
+static int all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode, const AllPlan &P, void *ws,
+                    hipStream_t st, Loss &&loss) {
+    const AllWs w = all_carve(P, ws);
+    const int64_t N = tb->n_entity;
+    int64_t ld_S = 0;
+    auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
+        ld_S = ld;
+        loss(w.S, ld, w.scratch);
+    };
+    return dispatch_dot_model(tb->model, mode == MKB_MODE_HEAD, [&](auto m, auto h) {
+        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
+        return all_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, ld_S > N, P, w, st);
+    });
 }
 
 }  // namespace mkb
@@ -436,18 +443,10 @@ extern "C" int mkb_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const
     MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
     MKB_REQUIRE(temperature - temperature == 0.f && temperature > 0.f, "the softmax temperature must be finite and > 0");
     if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    const AllWs w = all_carve(P, ws);
     hipStream_t st = (hipStream_t)stream;
-    const bool head = mode == MKB_MODE_HEAD;
-    const int64_t N = tb->n_entity;
-    int64_t ld_S = 0;
-    auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
-        ld_S = ld;
-        all_softmax_launch(w.S, B, N, ld, sample + (head ? 0 : 2), 3, weight, weight_sum, temperature, loss, pos, w.scratch, st);
-    };
-    return dispatch_dot_model(tb->model, head, [&](auto m, auto h) {
-        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
-        return all_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, ld_S > N, P, w, st);
+    return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
+        all_softmax_launch(S, B, tb->n_entity, ld, sample + (mode == MKB_MODE_HEAD ? 0 : 2), 3, weight, weight_sum, temperature, loss, pos,
+                           scratch, st);
     });
 }
 
@@ -469,18 +468,9 @@ extern "C" int mkb_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, c
     MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
     if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
     if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing)) return rc;
-    const AllWs w = all_carve(P, ws);
     hipStream_t st = (hipStream_t)stream;
-    const bool head = mode == MKB_MODE_HEAD;
-    const int64_t N = tb->n_entity;
-    int64_t ld_S = 0;
-    auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
-        ld_S = ld;
-        all_bce_launch(w.S, B, N, ld, sample, head, tb->n_relation, keys, n_keys, weight, weight_sum, smoothing, sum_over_entities != 0,
-                       loss, pos, w.scratch, st);
-    };
-    return dispatch_dot_model(tb->model, head, [&](auto m, auto h) {
-        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
-        return all_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, ld_S > N, P, w, st);
+    return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
+        all_bce_launch(S, B, tb->n_entity, ld, sample, mode == MKB_MODE_HEAD, tb->n_relation, keys, n_keys, weight, weight_sum, smoothing,
+                       sum_over_entities != 0, loss, pos, scratch, st);
     });
 }

@@ -4,6 +4,7 @@
 #include "score_pool_plan.h"
 #include "query_side.h"
 #include "gemm_mfma.h"
+#include "loss_math.h"  // RowLoss, row_loss_finish_block
 
 #include <stdlib.h>
 #include <algorithm>
@@ -72,7 +73,7 @@ struct RowStepArgs {
     int64_t De, Dr;
     int d, B, nslices;
     float kd, gamma;
-    // row_bwd inside mkb_pool_step: its last workgroup also finishes the loss (adversarial_finish_block), or nullptr
+    // row_bwd inside mkb_pool_step: its last workgroup also finishes the loss (row_loss_finish_block), or nullptr
     const float *loss_rowpart, *loss_scal;
     float *loss_out;
     // ... and extra workgroups behind the B row workgroups reduce the dx partials of the single-pass backward (blocks > 0)
@@ -227,8 +228,10 @@ __global__ __launch_bounds__(256) void row_bwd_kernel(RowStepArgs A) {
         extra = block_sum_4waves(extra, red);
         if (threadIdx.x == 0) atomicAdd(A.g_modulus, -extra);
     }
-    if (A.loss_out && i == A.B - 1)  // the per-row loss terms were written by an earlier kernel
-        adversarial_finish_block(A.loss_rowpart, A.B, A.loss_scal, A.loss_out, red);
+    if (A.loss_out && i == A.B - 1) {  // the per-row loss terms were written by an earlier kernel
+        __builtin_assume(A.loss_scal != nullptr);  // (set together with loss_out: the finish has no W = 1 case to select here)
+        row_loss_finish_block(A.loss_rowpart, A.B, -0.5f, A.loss_scal, A.loss_out, red);
+    }
 }
 
 // g_rel[e] += sum_c rep[c][e]   (fixed order; rep was zeroed by this step's loss kernel)
@@ -756,11 +759,11 @@ static int pool_step_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const in
         ra.rel_rep = w.rel_rep; ra.rel_copies = L.rel_copies; ra.n_rel = (int)tb->n_relation;
     }
     // (the occurrence counts: the VALU forward kernel counted them; the MFMA path has no such kernel, the loss rows do it)
+    RowLoss rl;
     if (int rc = adversarial_launch(pos_score, pool_score, weight, cnt, B, P, alpha, weight_sum, loss, w.dpos, w.G, w.scratch, st,
-                                    /*defer_finish=*/true, L.seeds(), s_tail, L.matrix() ? ra.occ : nullptr,
-                                    sample, pool)) return rc;
-    ra.loss_rowpart = w.scratch + 1;
-    ra.loss_scal = weight_sum ? weight_sum : w.scratch;
+                                    &rl, L.seeds(), s_tail, L.matrix() ? ra.occ : nullptr, sample, pool)) return rc;
+    ra.loss_rowpart = rl.rowpart;
+    ra.loss_scal = rl.scal;
     ra.loss_out = loss;
     // backward (pipeline.py:236): pooled negatives, then the positive pair and both query chains in one row kernel
     if (int rc = pooled_bwd(tb, head, gr, pool, cnt, B, P, w, L, st, L.single_pass() ? &ra.dx : nullptr, &ra.sc)) return rc;

@@ -150,19 +150,10 @@ def sampled_step(step, sample, weight, sampler, mode, **kwargs):
     return step(sample, weight, neg, mode, **kwargs)
 
 
-class FusedTrainStep:
-    """``loss = step(sample, weight, negative_sample, mode)``: fills ``param.grad`` (dense, accumulated) and returns
-    the loss as a 0-dim device tensor.  ``positive_score`` [B,1] and ``negative_score`` [B,size] of the last call
-    stay available for inspection.
-
-    ``regularizer``: a ``mkb_amd.regularizers.Lp`` (``N3``, ``L2``) whose term on the batch's positive triples joins the step:
-    one more library call (``mkb_reg_rows``, value and gradient in one launch sequence) behind ``mkb_pool_step`` -- which may
-    STORE the batch's gradient rows (``rows_clear``), so the regulariser adds onto them afterwards.  Its rows are the batch's heads
-    and tails, which the row-lazy protocol has already made current and marked.  The loss returned is loss + regulariser;
-    ``regularization`` keeps the term alone."""
-
-    def __init__(self, model, alpha, regularizer=None):
-        self.model, self.alpha, self.regularizer, self.regularization = model, float(alpha), regularizer, None
+class _PooledStep:
+    """What the steps over a shared candidate pool share (``FusedTrainStep``, ``PooledLossStep``): the sampler entry point, the
+    opening of a call and the outputs kept for inspection.  A subclass says whether ``weight`` may be None and whether its library
+    calls honour ``rows_clear``, makes those calls in ``_launch`` and returns the loss [1]."""
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
         return sampled_step(self, sample, weight, sampler, mode, weight_sum=weight_sum)
@@ -176,30 +167,53 @@ class FusedTrainStep:
             raise ValueError("negative_sample does not come from mkb_amd.sampling.NegativeSampling.generate")
         mode_id = _hip.mode_id(mode)
         sample = _hip.contiguous(sample, torch.int64)
-        weight = _hip.contiguous(weight, torch.float32)
+        weight = None if weight is None and self.weight_optional else _hip.contiguous(weight, torch.float32)
         _hip.require_device(m.entity_embedding, sample, weight)
         B, K = sample.shape[0], info.size
         dev = sample.device
         pos = torch.empty((B, 1), dtype=torch.float32, device=dev)
         S = torch.empty((B, 2 * K), dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
         ws = _workspace(m, B, K)
         gr = grad_buffers(m)
         ent = m.entity_embedding
         lazy = _links.owner(ent)
-        if lazy is not None and lazy.begin_step_on(ent, info.rows(sample)):  # row-lazy Adam: the rows read become current first
+        # row-lazy Adam: the rows read become current, and are marked as written, before anything writes a gradient row
+        if lazy is not None and lazy.begin_step_on(ent, info.rows(sample)) and self.may_clear_rows:
             gr.rows_clear = 1
-        with _hip.on_device(dev):
-            _hip.check(_hip.lib().mkb_pool_step(m._tables(), gr, _hip.ptr(sample), _hip.ptr(weight), _hip.ptr(info.pool),
-                                                _hip.ptr(info.cnt), B, K, mode_id, self.alpha, _hip.ptr(weight_sum),
-                                                _hip.ptr(pos), _hip.ptr(S),
-                                                _hip.ptr(loss), _hip.ptr(ws), _hip.stream_ptr()), "mkb_pool_step")
+        loss = self._launch(m._tables(), gr, sample, weight, info, B, K, mode_id, weight_sum, pos, S, ws, dev)
         self.positive_score, self._S, self._info = pos, S, info
         return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)
 
     @property
     def negative_score(self):
         return self._S.gather(1, self._info.pos.long())
+
+
+class FusedTrainStep(_PooledStep):
+    """``loss = step(sample, weight, negative_sample, mode)``: fills ``param.grad`` (dense, accumulated) and returns
+    the loss as a 0-dim device tensor.  ``positive_score`` [B,1] and ``negative_score`` [B,size] of the last call
+    stay available for inspection.
+
+    ``regularizer``: a ``mkb_amd.regularizers.Lp`` (``N3``, ``L2``) whose term on the batch's positive triples joins the step:
+    one more library call (``mkb_reg_rows``, value and gradient in one launch sequence) behind ``mkb_pool_step`` -- which may
+    STORE the batch's gradient rows (``rows_clear``), so the regulariser adds onto them afterwards.  Its rows are the batch's heads
+    and tails, which the row-lazy protocol has already made current and marked.  The loss returned is loss + regulariser;
+    ``regularization`` keeps the term alone."""
+
+    def __init__(self, model, alpha, regularizer=None):
+        self.model, self.alpha, self.regularizer, self.regularization = model, float(alpha), regularizer, None
+
+    weight_optional = False  # (mkb_pool_step requires weights)
+    may_clear_rows = True  # (mkb_pool_step honours rows_clear: it STORES rows the row-lazy optimizer has just consumed and cleared)
+
+    def _launch(self, tb, gr, sample, weight, info, B, K, mode_id, weight_sum, pos, S, ws, dev):
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        with _hip.on_device(dev):
+            _hip.check(_hip.lib().mkb_pool_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), _hip.ptr(info.pool),
+                                                _hip.ptr(info.cnt), B, K, mode_id, self.alpha, _hip.ptr(weight_sum),
+                                                _hip.ptr(pos), _hip.ptr(S),
+                                                _hip.ptr(loss), _hip.ptr(ws), _hip.stream_ptr()), "mkb_pool_step")
+        return loss
 
 
 def _with_regularizer(step, loss, sample, weight, weight_sum, gr):
@@ -210,7 +224,7 @@ def _with_regularizer(step, loss, sample, weight, weight_sum, gr):
     return loss + step.regularization
 
 
-class PooledLossStep:
+class PooledLossStep(_PooledStep):
     """``FusedTrainStep`` for a loss of the ``mkb_ns_loss`` family (``losses.MarginRanking``, ``PairwiseLogistic``, ``CrossEntropy``):
     ``loss = step(sample, weight, negative_sample, mode)`` fills ``param.grad`` (dense, accumulated) and returns the loss as a
     0-dim device tensor; ``positive_score`` [B,1] and ``negative_score`` [B,size] of the last call stay available.
@@ -226,33 +240,14 @@ class PooledLossStep:
             raise TypeError("PooledLossStep takes losses.MarginRanking, losses.PairwiseLogistic or losses.CrossEntropy")
         self.model, self.loss, self.regularizer, self.regularization = model, loss, regularizer, None
 
-    def sampled(self, sample, weight, sampler, mode, weight_sum=None):
-        return sampled_step(self, sample, weight, sampler, mode, weight_sum=weight_sum)
+    weight_optional = True
+    # rows_clear stays 0 whatever the optimizer answers: the promise is only honoured by mkb_pool_step / _bwd, and the two backward
+    # calls of _launch both add to the rows of the batch's heads and tails -- they must accumulate.
+    may_clear_rows = False
 
-    def __call__(self, sample, weight, negative_sample, mode, weight_sum=None):
-        """``weight_sum``: as for ``FusedTrainStep`` (the sum of weights of the whole batch when these rows are a shard of it)."""
+    def _launch(self, tb, gr, sample, weight, info, B, K, mode_id, weight_sum, pos, S, ws, dev):
         m = self.model
-        info = getattr(negative_sample, "_mkb_pool", None)
-        if info is None:
-            raise ValueError("negative_sample does not come from mkb_amd.sampling.NegativeSampling.generate")
-        mode_id = _hip.mode_id(mode)
-        sample = _hip.contiguous(sample, torch.int64)
-        weight = None if weight is None else _hip.contiguous(weight, torch.float32)
-        _hip.require_device(m.entity_embedding, sample, weight)
-        B, K = sample.shape[0], info.size
-        dev = sample.device
-        pos = torch.empty((B, 1), dtype=torch.float32, device=dev)
-        S = torch.empty((B, 2 * K), dtype=torch.float32, device=dev)
-        ws = _workspace(m, B, K)
-        gr = grad_buffers(m)
-        ent = m.entity_embedding
-        lazy = _links.owner(ent)
-        if lazy is not None:
-            # row-lazy Adam: the rows read become current, and are marked as written, before anything writes a gradient row.
-            # (rows_clear stays 0 whatever this answers: the promise is only honoured by mkb_pool_step / _bwd, and the two
-            # backward calls below both add to the rows of the batch's heads and tails -- they must accumulate.)
-            lazy.begin_step_on(ent, info.rows(sample))
-        lib, tb, st = _hip.lib(), m._tables(), _hip.stream_ptr(dev)
+        lib, st = _hip.lib(), _hip.stream_ptr(dev)
         with _hip.on_device(dev):
             _hip.check(lib.mkb_score_fwd(tb, _hip.ptr(sample), None, B, 1, _hip.MODE_DEFAULT, _hip.ptr(pos), st), "mkb_score_fwd")
             _hip.check(lib.mkb_pool_score_fwd(tb, _hip.ptr(sample), _hip.ptr(info.pool), _hip.ptr(info.cnt), B, K, mode_id,
@@ -273,12 +268,7 @@ class PooledLossStep:
                        "mkb_score_bwd")
         if gr.g_modulus:
             m.modulus.grad += mod_parts[0] + mod_parts[1]
-        self.positive_score, self._S, self._info = pos, S, info
-        return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)
-
-    @property
-    def negative_score(self):
-        return self._S.gather(1, self._info.pos.long())
+        return loss
 
 
 # ---------------------------------------------------------------------------------------------------- 1vsAll (ComplEx / DistMult)
@@ -290,13 +280,6 @@ def _all_workspace(model, B):
     dev = model.entity_embedding.device
     key = (dev, _hip.stream_ptr(dev).value, "all", model.name, model.entity_dim, model.n_entity, model.n_relation, B)
     return cached_workspace(key, dev, lambda: _hip.lib().mkb_all_step_workspace_bytes(model._tables(), B))
-
-
-def _side(mode):
-    mode_id = _hip.mode_id(mode)
-    if mode_id == _hip.MODE_DEFAULT:
-        raise ValueError(f"1vsAll scores one side of a triple: mode must be 'head-batch' or 'tail-batch', not {mode!r}")
-    return mode_id
 
 
 class _ScoreAllFn(torch.autograd.Function):
@@ -330,7 +313,7 @@ class _ScoreAllFn(torch.autograd.Function):
 
 def score_all(model, sample, mode):
     """What ``model.score_all(sample, mode)`` runs (models/base.py checks the arguments and makes row-lazy tables current)."""
-    return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, model, sample, _side(mode))
+    return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, model, sample, _hip.side_id(mode, "1vsAll scores"))
 
 
 class _AllEntityStep:
@@ -350,7 +333,7 @@ class _AllEntityStep:
 
     def __call__(self, sample, weight, mode, weight_sum=None):
         m = self.model
-        mode_id = _side(mode)
+        mode_id = _hip.side_id(mode, "1vsAll scores")
         if sample.dim() != 2 or sample.shape[1] != 3 or sample.shape[0] < 1:
             raise ValueError("sample must be [B, 3] with B >= 1")
         if weight is not None and weight.shape != (sample.shape[0],):

@@ -27,6 +27,7 @@ import math
 import torch
 
 from .. import _hip
+from . import _rows
 from ..utils.true_keys import true_keys
 
 __all__ = ["KvsAll"]
@@ -44,41 +45,17 @@ def checked_settings(label_smoothing, reduction):
     return eps, reduction
 
 
-def side(mode):
-    mode_id = _hip.mode_id(mode)
-    if mode_id == _hip.MODE_DEFAULT:
-        raise ValueError(f"KvsAll labels one side of a triple: mode must be 'head-batch' or 'tail-batch', not {mode!r}")
-    return mode_id
-
-
 def launch(S, n_cols, sample, mode_id, n_relation, keys, weight, weight_sum, label_smoothing, reduction):
     """One ``mkb_all_bce`` call on a contiguous float32 device block ``S`` [B, ld] of which the first ``n_cols`` columns count;
     ``keys``: the sorted int64 device keys of ``mode_id``'s side.  ``S`` is OVERWRITTEN with the gradient seeds.
     -> (loss [1], pos [B])."""
     B, ld = S.shape
-    dev = S.device
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    pos = torch.empty(B, dtype=torch.float32, device=dev)
-    scratch = torch.empty(B + 1, dtype=torch.float32, device=dev)
-    with _hip.on_device(dev):
+    loss, pos, scratch = _rows.block_outputs(S)
+    with _hip.on_device(S.device):
         _hip.check(_hip.lib().mkb_all_bce(_hip.ptr(S), B, n_cols, ld, _hip.ptr(sample), mode_id, n_relation, _hip.ptr(keys), keys.numel(),
                                           _hip.ptr(weight), _hip.ptr(weight_sum), label_smoothing, int(reduction == "sum"),
                                           _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(scratch), _hip.stream_ptr()), "mkb_all_bce")
     return loss, pos
-
-
-class _KvsAllFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores, sample, mode_id, n_relation, keys, weight, label_smoothing, reduction):
-        seeds = scores.detach().clone(memory_format=torch.contiguous_format)  # the kernel works in place
-        loss, _ = launch(seeds, seeds.shape[1], sample, mode_id, n_relation, keys, weight, None, label_smoothing, reduction)
-        ctx.save_for_backward(seeds)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (seeds,) = ctx.saved_tensors
-        return (g * seeds,) + (None,) * 7
 
 
 class KvsAll:
@@ -96,23 +73,21 @@ class KvsAll:
 
     def __call__(self, scores, sample, mode, weight=None, n_relation=None):
         _hip.require_device(scores, sample, weight)
-        mode_id = side(mode)
+        mode_id = _hip.side_id(mode, "KvsAll labels")
         if self.true_triples is None:
             raise ValueError("KvsAll needs true_triples to label a score block (only compose.Pipeline fills them in from its dataset)")
-        if scores.dim() != 2 or scores.size(1) < 1:
-            raise ValueError("scores must be [B, N] with N >= 1")
+        _rows.check_scores(scores)
         if sample.shape != (scores.size(0), 3) or sample.dtype != torch.int64:
             raise ValueError("sample must be an int64 tensor [B, 3]")
-        if weight is not None and weight.shape != (scores.size(0),):
-            raise ValueError("weight must be [B]")
-        s = _hip.contiguous(scores, torch.float32)
-        w = None if weight is None else _hip.contiguous(weight, torch.float32)
-        if s.shape[0] == 0:  # as the sampled losses answer an empty batch: empty sums over W = 0 -> nan, no launch
-            wsum = s.sum() if w is None else w.sum()
-            return (s.sum() + wsum) / wsum
+        _rows.check_weight(weight, scores.size(0))
+        s, w = _rows.f32(scores), _rows.f32(weight)
+        if s.shape[0] == 0:
+            return _rows.empty_batch(w, s)
         n_relation = self._relations() if n_relation is None else int(n_relation)
         keys = true_keys(self.true_triples, s.device, s.size(1), n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
-        return _KvsAllFn.apply(s, _hip.contiguous(sample, torch.int64), mode_id, n_relation, keys, w, self.label_smoothing, self.reduction)
+        sample = _hip.contiguous(sample, torch.int64)
+        return _rows.SeedsInPlaceFn.apply(s, lambda S: launch(S, S.shape[1], sample, mode_id, n_relation, keys, w, None, self.label_smoothing,
+                                                              self.reduction))
 
     def __repr__(self):
         return f"KvsAll(label_smoothing={self.label_smoothing}, reduction={self.reduction!r})"

@@ -20,6 +20,7 @@ import math
 import torch
 
 from .. import _hip
+from . import _rows
 
 __all__ = ["MarginRanking", "PairwiseLogistic", "CrossEntropy"]
 
@@ -28,29 +29,12 @@ def launch(kind, pos, neg, weight, cnt, param, alpha, weight_sum=None):
     """One ``mkb_ns_loss`` call on contiguous float32 device tensors -> (loss [1], dpos [B], dneg [B, K]); ``cnt`` (uint16
     [B, K] multiplicities) and ``weight`` / ``weight_sum`` may be None."""
     B, K = neg.shape
-    dev = neg.device
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    dpos = torch.empty(B, dtype=torch.float32, device=dev)
-    dneg = torch.empty((B, K), dtype=torch.float32, device=dev)
-    scratch = torch.empty(B + 1, dtype=torch.float32, device=dev)
-    with _hip.on_device(dev):
+    loss, dpos, dneg, scratch = _rows.pair_outputs(neg)
+    with _hip.on_device(neg.device):
         _hip.check(_hip.lib().mkb_ns_loss(kind, _hip.ptr(pos), _hip.ptr(neg), _hip.ptr(weight), _hip.ptr(cnt), B, K, param, alpha,
                                           _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(dpos), _hip.ptr(dneg), _hip.ptr(scratch),
                                           _hip.stream_ptr()), "mkb_ns_loss")
     return loss, dpos, dneg
-
-
-class _NsLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pos, neg, weight, kind, param, alpha):
-        loss, dpos, dneg = launch(kind, pos, neg, weight, None, param, alpha)
-        ctx.save_for_backward(dpos, dneg)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        dpos, dneg = ctx.saved_tensors
-        return (g * dpos).view(-1, 1), g * dneg, None, None, None, None
 
 
 class _NsLoss:
@@ -69,15 +53,12 @@ class _NsLoss:
             raise ValueError("positive_score must be [B, 1]")
         if negative_score.dim() != 2 or negative_score.size(0) != positive_score.size(0) or negative_score.size(1) < 1:
             raise ValueError("negative_score must be [B, K] with K >= 1")
-        if weight is not None and weight.shape != (positive_score.size(0),):
-            raise ValueError("weight must be [B]")
-        pos = _hip.contiguous(positive_score, torch.float32)
-        neg = _hip.contiguous(negative_score, torch.float32)
-        w = None if weight is None else _hip.contiguous(weight, torch.float32)
-        if pos.shape[0] == 0:  # as Adversarial answers an empty batch: two empty sums over W = 0 -> nan, no launch
-            wsum = pos.sum() if w is None else w.sum()
-            return (pos.sum() + neg.sum() + wsum) / wsum
-        return _NsLossFn.apply(pos, neg, w, self.kind, float(self.param), float(self.alpha))
+        _rows.check_weight(weight, positive_score.size(0))
+        pos, neg, w = _rows.f32(positive_score), _rows.f32(negative_score), _rows.f32(weight)
+        if pos.shape[0] == 0:
+            return _rows.empty_batch(w, pos, neg)
+        kind, param, alpha = self.kind, float(self.param), float(self.alpha)
+        return _rows.PairSeedsFn.apply(pos, neg, lambda p, n: launch(kind, p, n, w, None, param, alpha))
 
 
 def _checked(name, value, positive=False, nonnegative=False):

@@ -17,6 +17,7 @@ distance models use the sampled ``CrossEntropy``.
 import torch
 
 from .. import _hip
+from . import _rows
 from .ns_losses import _checked
 
 __all__ = ["OneVsAll"]
@@ -27,29 +28,12 @@ def launch(S, n_cols, target, target_stride, weight, weight_sum, temperature):
     ``target``: int64 device tensor read at ``i * target_stride``.  ``S`` is OVERWRITTEN with the gradient seeds.
     -> (loss [1], pos [B])."""
     B, ld = S.shape
-    dev = S.device
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    pos = torch.empty(B, dtype=torch.float32, device=dev)
-    scratch = torch.empty(B + 1, dtype=torch.float32, device=dev)
-    with _hip.on_device(dev):
+    loss, pos, scratch = _rows.block_outputs(S)
+    with _hip.on_device(S.device):
         _hip.check(_hip.lib().mkb_all_softmax(_hip.ptr(S), B, n_cols, ld, _hip.ptr(target), target_stride, _hip.ptr(weight),
                                               _hip.ptr(weight_sum), temperature, _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(scratch),
                                               _hip.stream_ptr()), "mkb_all_softmax")
     return loss, pos
-
-
-class _OneVsAllFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores, target, weight, temperature):
-        seeds = scores.detach().clone(memory_format=torch.contiguous_format)  # the kernel works in place
-        loss, _ = launch(seeds, seeds.shape[1], target, 1, weight, None, temperature)
-        ctx.save_for_backward(seeds)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (seeds,) = ctx.saved_tensors
-        return g * seeds, None, None, None
 
 
 class OneVsAll:
@@ -60,18 +44,15 @@ class OneVsAll:
 
     def __call__(self, scores, target, weight=None):
         _hip.require_device(scores, target, weight)
-        if scores.dim() != 2 or scores.size(1) < 1:
-            raise ValueError("scores must be [B, N] with N >= 1")
+        _rows.check_scores(scores)
         if target.shape != (scores.size(0),) or target.dtype != torch.int64:
             raise ValueError("target must be an int64 tensor [B]")
-        if weight is not None and weight.shape != (scores.size(0),):
-            raise ValueError("weight must be [B]")
-        s = _hip.contiguous(scores, torch.float32)
-        w = None if weight is None else _hip.contiguous(weight, torch.float32)
-        if s.shape[0] == 0:  # as the sampled losses answer an empty batch: empty sums over W = 0 -> nan, no launch
-            wsum = s.sum() if w is None else w.sum()
-            return (s.sum() + wsum) / wsum
-        return _OneVsAllFn.apply(s, _hip.contiguous(target, torch.int64), w, float(self.temperature))
+        _rows.check_weight(weight, scores.size(0))
+        s, w = _rows.f32(scores), _rows.f32(weight)
+        if s.shape[0] == 0:
+            return _rows.empty_batch(w, s)
+        target, T = _hip.contiguous(target, torch.int64), float(self.temperature)
+        return _rows.SeedsInPlaceFn.apply(s, lambda S: launch(S, S.shape[1], target, 1, w, None, T))
 
     def __repr__(self):
         return f"OneVsAll(temperature={self.temperature})"

@@ -111,6 +111,23 @@ def test_kernel_on_a_block(case):
     assert not failures, failures
 
 
+@pytest.mark.parametrize("B", [8192, 8193])
+def test_kernel_on_a_block_on_each_side_of_the_weight_sum_limit(B):
+    """One batch on each side of the limit up to which every workgroup reduces the weight sum itself: the 32-row batch, labels and
+    weights of one case repeated cyclically; once with weights and no weight sum, once with a given weight sum."""
+    case = U.CASES[U.CASE_IDS.index("t64-n130-d16")]
+    pb = U.problem(case)
+    rows = np.arange(B) % pb.B
+    settings = ((0.1, "mean", True, None), (0.1, "mean", True, 2.0))
+    failures = []
+    for mode in U.MODES:
+        L = K.labels(case, mode)
+        S32 = K.expected(case, mode)[0]["S"].astype(np.float32)[rows]
+        failures += _check_block(f"limit B={B}", case[0], S32, pb.N, np.asarray(L.sample)[rows], mode, L.keys, np.asarray(pb.weight)[rows],
+                                 U.entity_dim(pb.model, pb.hidden), settings)
+    assert not failures, failures
+
+
 def test_scores_of_300_stay_finite_and_within_tolerance():
     case = U.CASES[U.CASE_IDS.index("t64-n131-d16")]
     pb = U.problem(case)

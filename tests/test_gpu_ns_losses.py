@@ -136,6 +136,30 @@ def test_two_runs_give_the_same_bits(kind, param, alpha):
         assert a[1].tobytes() == b[1].tobytes() and a[2].tobytes() == b[2].tobytes()
 
 
+@pytest.mark.parametrize("B,K", SHAPES[-2:])
+def test_adversarial_on_each_side_of_the_weight_sum_limit(B, K):
+    """losses.Adversarial shares the limit up to which every workgroup reduces the weight sum itself: one batch on each side of it,
+    weights given, against the float64 formula (reference mkb/losses/adversarial.py) with ``check``'s bounds; two runs give the
+    same loss bits."""
+    from mkb_amd import losses
+
+    alpha = 0.5
+    pos, neg, w = draw(B, K, 4000 + B, "adversarial", alpha)
+    p64, n64, w64 = pos.double().requires_grad_(True), neg.double().requires_grad_(True), w.double()
+    logsig = torch.nn.functional.logsigmoid
+    ns = (torch.softmax(alpha * n64, 1).detach() * logsig(-n64)).sum(1)
+    ref = (-(w64 * logsig(p64)).sum() / w64.sum() - (w64 * ns).sum() / w64.sum()) / 2
+    ref.backward()
+    runs = []
+    for _ in range(2):
+        pd, nd = pos.cuda().view(B, 1).requires_grad_(True), neg.cuda().requires_grad_(True)
+        loss = losses.Adversarial(alpha)(pd, nd, w.cuda())
+        loss.backward()
+        runs.append((float(loss), pd.grad.cpu().numpy()[:, 0], nd.grad.cpu().numpy()))
+    check(runs[0], (float(ref), p64.grad.numpy(), n64.grad.numpy()), ("adversarial", alpha, B, K))
+    assert np.float32(runs[0][0]).tobytes() == np.float32(runs[1][0]).tobytes()
+
+
 def _loss_object(kind, param, alpha):
     from mkb_amd import losses
 

@@ -118,6 +118,45 @@ def test_step_against_float64_and_the_pad_trap(case):
     assert not failures, failures
 
 
+@pytest.mark.parametrize("B", [8192, 8193])
+def test_softmax_kernel_on_each_side_of_the_weight_sum_limit(B):
+    """mkb_all_softmax on a [B, 130] block of given scores, one batch on each side of the limit up to which every workgroup reduces
+    the weight sum itself: weights given, no weight sum, the leading dimension padded as the forward pads it.  Loss, positive scores
+    and dS against the float64 formula on those very values within 8 x the float32 formula's own error (at least one float32 ulp of
+    the largest magnitude); pad columns of dS exactly 0; two runs give the same loss bits."""
+    from mkb_amd.losses import one_vs_all
+
+    N, rs = 130, np.random.RandomState(B)
+    S32 = rs.normal(0, 2, size=(B, N)).astype(np.float32)
+    target, weight = rs.randint(N, size=B), rs.uniform(0.1, 1.1, size=B).astype(np.float32)
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        S = torch.from_numpy(S32).to(dtype).requires_grad_(True)
+        w = torch.from_numpy(weight).to(dtype)
+        pos = S[torch.arange(B), torch.from_numpy(target)]
+        loss = (w * (torch.logsumexp(S, 1) - pos)).sum() / w.sum()
+        loss.backward()
+        out.append({"loss": loss.detach().numpy(), "pos": pos.detach().numpy(), "dS": S.grad.numpy()})
+    f64, f32 = out
+    runs = []
+    for _ in range(2):
+        block = torch.cat([_dev(S32)] + [_dev(S32[:, -1:])] * ((-N) % 4), 1).contiguous()  # (the pad columns repeat the last entity's score)
+        loss, pos = one_vs_all.launch(block, N, _dev(target), 1, _dev(weight), None, 1.0)
+        torch.cuda.synchronize()
+        runs.append({"loss": loss.cpu().numpy()[0], "pos": pos.cpu().numpy(), "dS": block.cpu().numpy()})
+    got = runs[0]
+    assert got["dS"].shape[1] == 132 and not got["dS"][:, N:].any(), "pad columns of dS must be exactly 0"
+    assert np.float32(got["loss"]).tobytes() == np.float32(runs[1]["loss"]).tobytes()
+    failures = []
+    for what, g in (("loss", got["loss"]), ("pos", got["pos"]), ("dS", got["dS"][:, :N])):
+        err = max(float(np.abs(f32[what].astype(np.float64) - f64[what]).max()), 2.0 ** -24 * float(np.abs(f64[what]).max()))
+        e = float(np.abs(np.asarray(g, dtype=np.float64) - f64[what]).max())
+        print(f"onevsall-limit B={B} {what}: error {e:.3e} err_ref {err:.3e} ratio {e / err:.2f}")
+        if not e <= U.ERR_FACTOR * err:
+            failures.append((what, e, U.ERR_FACTOR * err))
+    assert not failures, failures
+
+
 @pytest.mark.parametrize("case", U.CASES, ids=U.CASE_IDS)
 def test_checks_that_need_no_tolerance(case):
     pb = U.problem(case)

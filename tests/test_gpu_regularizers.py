@@ -93,7 +93,10 @@ def test_kernel_against_float64(name, p):
     of ``prefill + gradient`` (2^-24 of the sum) joins grad_close's bound.  Rows of exact zeros in both tables: gradient exactly
     0, nothing NaN."""
     le, lr = 0.3, 0.7
-    for k, (what, N, R, hidden, B, weighted, weight_sum, scale) in enumerate(_cases(name)):
+    cases = _cases(name)
+    if (name, p) == ("ComplEx", 3):  # past the rows up to which every workgroup reduces the weight sum itself: one launch in front
+        cases.append(("B = 8193", 50, 4, 6, 8193, True, None, None))
+    for k, (what, N, R, hidden, B, weighted, weight_sum, scale) in enumerate(cases):
         g = torch.Generator().manual_seed(100 * k + p)
         ent, rel = _tables(name, N, R, hidden, 7 * k + 1)
         ent[1] = 0.0

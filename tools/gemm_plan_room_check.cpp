@@ -18,7 +18,7 @@ int set_error(int code, const char *, ...) { return code; }
 ProfScope::ProfScope(int kind, hipStream_t st) : kind(kind), st(st), slot(-1) {}
 ProfScope::~ProfScope() {}
 int adversarial_launch(const float *, const float *, const float *, const uint16_t *, int64_t, int64_t, float, const float *, float *, float *,
-                       float *, float *, hipStream_t, bool, SeedLayout, const GemmTail *, int *, const int64_t *, const int64_t *) { return MKB_ERR_INVALID; }
+                       float *, float *, hipStream_t, RowLoss *, SeedLayout, const GemmTail *, int *, const int64_t *, const int64_t *) { return MKB_ERR_INVALID; }
 template <int MODEL, bool HEAD>
 int pool_launch(int, const PoolPlan &, const PoolArgs &, hipStream_t) { return MKB_ERR_INVALID; }
 }  // namespace mkb
