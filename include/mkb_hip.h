@@ -596,8 +596,8 @@ int mkb_reg_rows(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *s
  *   row_i = log sum_{e < n_entity} exp(s_i(e) / T) - s_i(target_i) / T,   loss = sum_i w_i row_i / W
  *   over sample [B, 3] in MKB_MODE_TAIL (s_i(e) = score of (h_i, r_i, e), target t_i) or MKB_MODE_HEAD ((e, r_i, t_i), target h_i);
  *   weight [B] or null (all ones), W = sum of weight (B when null), or weight_sum[0] when given (the rows are a shard, as for
- *   mkb_ns_loss).  No filtering of other known answers.  Only the two models whose all-entity block is one matrix product:
- *   TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED (their sampled softmax is mkb_ns_loss with MKB_LOSS_SOFTMAX).
+ *   mkb_ns_loss).  No filtering of other known answers and no label smoothing in these calls: the "filtered 1vsAll" section
+ *   below has both.  Only the two models whose all-entity block is one matrix product: TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED (their sampled softmax is mkb_ns_loss with MKB_LOSS_SOFTMAX).
  *   mkb_all_score_fwd: scores [B, n_entity] out = the all-entity block of the evaluation, the bits mkb_rank_scores hands out (the
  *   same routes, chosen in the same place).
  *   mkb_all_softmax: one pass per row over a block S [B, ld] of which the first N columns count, target[i * target_stride] the
@@ -652,6 +652,37 @@ int mkb_all_bce(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sampl
 int mkb_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
                      const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities, const float *weight_sum, float *loss,
                      float *pos, void *ws, int64_t ws_bytes, void *stream);
+
+/* ---- filtered 1vsAll: the softmax cross entropy without a row's other known answers, with label smoothing ---------------------
+ * The 1vsAll step around a third loss kernel; mkb_amd/csrc/score_all.hip.  New symbols under ABI 8: the version is not bumped
+ * (symbols are only added).  With A_i the keys of row i's query (the key arrays and ranges of the KvsAll section), t_i its target:
+ *   F_i = A_i \ {t_i} (filtered),   C_i = [0, N) \ F_i (kept),   n_i = |C_i| >= 1,   eps = smoothing
+ *   y_ij = (1 - eps) [j = t_i] + eps / n_i,   row_i = log sum_{C_i} exp(s_ij / T) - (1 - eps) s_it / T - (eps / n_i) sum_{C_i} s_ij / T,
+ *   loss = sum_i w_i row_i / W,   dS_ij = (w_i / (W T)) (p_ij - y_ij) on C_i with p_ij = exp(s_ij / T) / sum_{C_i} exp(s_ik / T),
+ *   dS_ij = 0 exactly on F_i.  A filtered column takes no part in anything: not in the maximum, the partition sum, the linear sum or
+ *   n_i.  The target is never filtered, whether or not it is a key.  Without keys this is the cross entropy with label smoothing
+ *   over the whole row; with eps = 0 as well, the loss of mkb_all_softmax.  A query without keys and two rows with one query are
+ *   legal.  weight, W, weight_sum: as for the 1vsAll calls.  TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED.
+ *   mkb_all_softmax_filtered: one workgroup per row over a block S [B, ld] of which the first N columns count, target[i *
+ *   target_stride] the row's target column, sample [B, 3] and mode naming its query (tail-batch: h_i n_relation + r_i; head-batch:
+ *   t_i n_relation + r_i).  The target may differ from the sample's open-slot entity; that entity is then filtered like any other
+ *   key.  Writes loss [1] and pos [B] (the target's score, read before anything is overwritten) and OVERWRITES S with dS; columns
+ *   N .. ld - 1 take no part in the sums and are written as exactly 0.  Stable logsumexp over the kept columns only, fixed-order
+ *   reductions, no float atomics.  scratch: 1 + B floats (device).  An id outside its table counts as the nearest row or column:
+ *   the glue flags it with mkb_check_ids.
+ *   mkb_all_filtered_step: forward, this loss and the backward of mkb_all_step in one call, the target the sample's open slot;
+ *   pos [B] out; gradients accumulate into gr as for mkb_all_step, two runs give the same bits.
+ *   ws: mkb_all_step_workspace_bytes(tb, B) bytes, the 1vsAll step's.  A null pointer (keys may be null only with n_keys == 0),
+ *   n_keys < 0, T <= 0 or not finite, smoothing outside [0, 1) or not finite, a mode other than head-/tail-batch, B < 1, ld < N,
+ *   the size limits of the 1vsAll calls, (n_entity * n_relation + n_relation) * n_entity past 2^63 - 1, a short or misaligned
+ *   workspace, an unknown model -> MKB_ERR_INVALID before any launch. */
+int mkb_all_softmax_filtered(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t target_stride,
+                             const int64_t *sample, int mode, int64_t n_relation, const int64_t *keys, int64_t n_keys,
+                             const float *weight, const float *weight_sum, float T, float smoothing, float *loss, float *pos,
+                             float *scratch, void *stream);
+int mkb_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
+                          const int64_t *keys, int64_t n_keys, float T, float smoothing, const float *weight_sum, float *loss,
+                          float *pos, void *ws, int64_t ws_bytes, void *stream);
 
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream

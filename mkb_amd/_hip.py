@@ -187,6 +187,10 @@ _SIGNATURES = {
                             c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mkb_all_kvs_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_all_softmax_filtered": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mkb_all_filtered_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_float,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -102,10 +102,12 @@ class Pipeline:
         when model, sampler and loss are the mkb_amd ones on a ROCm device, else None.  ``losses.OneVsAll`` always takes
         ``OneVsAllStep`` and ``losses.KvsAll`` always ``KvsAllStep``: they have no explicit sequence (no negatives are drawn:
         ``sampling`` is not used).  A ``KvsAll`` without triples of its own is labelled by the training triples of ``dataset``
-        (``DeviceBatches`` hands out the wrapped dataset's)."""
+        (``DeviceBatches`` hands out the wrapped dataset's); a ``OneVsAll(filter_known=True)`` without triples filters by them."""
         if isinstance(loss, OneVsAll):
             self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
-            return OneVsAllStep(model, loss.temperature, regularizer=self.regularizer)
+            triples = (dataset.train if loss.true_triples is None else loss.true_triples) if loss.filter_known else None
+            return OneVsAllStep(model, loss.temperature, regularizer=self.regularizer, label_smoothing=loss.label_smoothing,
+                                true_triples=triples)
         if isinstance(loss, KvsAll):
             self._borrowed = []
             triples = dataset.train if loss.true_triples is None else loss.true_triples

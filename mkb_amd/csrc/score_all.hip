@@ -18,6 +18,8 @@
 // something end as that + the step's result, bit for bit.
 // KvsAll (include/mkb_hip.h, "KvsAll") is the same step around another loss kernel, all_bce_kernel: the multi-label binary cross
 // entropy with label smoothing, its labels read from the sorted key arrays of the filtered ranking.
+// Filtered 1vsAll (include/mkb_hip.h, "filtered 1vsAll") is the third loss kernel, all_softmax_filtered_kernel: the softmax with a
+// row's other known answers -- the same key range -- taken out of the row, and label smoothing over the columns that stay.
 // Written once for both: the step (all_step: carve, forward, the loss on the block, backward) and the launch of "a loss
 // kernel on the block" (all_loss_launch), which runs it inside the row-loss protocol of loss_math.h (RowLoss: W, the scratch, the
 // launch in front of many rows, the finish).
@@ -170,6 +172,110 @@ static void all_bce_launch(float *S, int64_t B, int64_t N, int64_t ld, const int
     all_loss_launch(weight, weight_sum, B, loss, scratch, st, [&](const RowLoss &L) {
         hipLaunchKernelGGL(all_bce_kernel, dim3((unsigned)B), dim3(256), 0, st, S, (int)B, N, ld, sample, head ? 1 : 0, R, keys, n_keys,
                            weight, L.scal_in, L.scal_out, eps, sum_over_entities ? 1.f : 1.f / (float)N, pos, L.rowpart);
+    });
+}
+
+// ---- filtered 1vsAll (include/mkb_hip.h, "filtered 1vsAll"): the softmax over the row WITHOUT the query's other known answers,
+//     C_i = [0, N) \ (A_i \ {t_i}),  n_i = |C_i|,  y_ij = (1 - eps) [j = t_i] + eps / n_i,
+//     row_i = log sum_{C_i} exp(s_ij / T) - (1 - eps) s_it / T - (eps / n_i) sum_{C_i} s_ij / T,  dS_ij = (w_i / (W T)) (p_ij - y_ij) on C_i, 0 off it
+// A_i: the key range of all_bce_kernel.  One 256-lane workgroup per row.  The filtered columns are marked first, in S itself (it is
+// overwritten anyway; keys are unique and the target is never marked: one writer per element, and the target's score stays
+// readable): -inf, which no maximum picks, whose exponent is 0 and which the linear sum skips by test -- nothing is added and taken
+// back.  Then all_softmax_kernel's three passes, LDS staging up to kAllStageCols, the global loads four strides at a time.  The sums
+// are taken relative to the row maximum m (the weights of m in the row add up to 1 - (1 - eps) - n_i eps / n_i = 0):
+//     row_i = log Z - (1 - eps) (s_it - m) / T - (eps / n_i) sum_{C_i} (s_ij - m) / T,   Z = sum_{C_i} exp((s_ij - m) / T) >= 1.
+// scal / scal_out / rowpart: as for all_softmax_kernel.
+
+// f(j, row[j]) for the lane's columns j = tid, tid + 256, ... < N in that order, four strides' loads in flight at a time (f may
+// write row[j]: a lane only ever touches its own columns)
+template <class F>
+__device__ __forceinline__ void row_cols_256(float *__restrict__ row, int64_t N, F &&f) {
+    int64_t j = threadIdx.x;
+    for (; j + 768 < N; j += 1024) {
+        float v[4];
+#pragma unroll
+        for (int z = 0; z < 4; ++z) v[z] = row[j + 256 * z];
+#pragma unroll
+        for (int z = 0; z < 4; ++z) f(j + 256 * z, v[z]);
+    }
+    for (; j < N; j += 256) f(j, row[j]);
+}
+
+__global__ __launch_bounds__(256) void all_softmax_filtered_kernel(float *__restrict__ S, int B, int64_t N, int64_t ld,
+                                                                   const int64_t *__restrict__ target, int64_t tstride,
+                                                                   const int64_t *__restrict__ sample, int head, int64_t R,
+                                                                   const int64_t *__restrict__ keys, int64_t n_keys,
+                                                                   const float *__restrict__ w, const float *__restrict__ scal,
+                                                                   float *__restrict__ scal_out, float inv_T, float eps,
+                                                                   float *__restrict__ pos, float *__restrict__ rowpart) {
+    __shared__ float red[4];
+    extern __shared__ float s_row[];
+    const int tid = threadIdx.x;
+    const int64_t i = blockIdx.x;
+    float *row = S + i * ld;
+    const bool staged = N <= kAllStageCols;
+    const int64_t *s = sample + 3 * i;
+    // (an id outside its table counts as the nearest row, so that no marked column leaves the row: the glue flags it, mkb_check_ids)
+    const int64_t q = table_row(s[head ? 2 : 0], N) * R + table_row(s[1], R), base = q * N;
+    const int64_t t = table_row(target[i * tstride], N);
+    const int64_t lo = lower_bound_dev(keys, n_keys, base), hi = lower_bound_dev(keys, n_keys, base + N);  // (uniform; empty: lo == hi)
+    const float p_i = row[t];  // before anything is overwritten (and column t is never marked)
+    const float wi = w ? w[i] : 1.f;
+
+    int own = 0;  // the target is one of the keys: it stays in the row
+    for (int64_t k = lo + tid; k < hi; k += 256) {
+        const int64_t c = table_row(keys[k] - base, N);
+        if (c == t) own = 1;
+        else row[c] = -INFINITY;
+    }
+    own = __syncthreads_or(own);  // (its barrier stands between the marks and the passes that read them)
+    const int64_t n = N - (hi - lo) + (own ? 1 : 0);  // >= 1: the target
+    const float W = row_loss_weight_sum(scal, scal_out, w, B, red);
+
+    float m = -INFINITY;
+    row_cols_256(row, N, [&](int64_t j, float v) {
+        m = fmaxf(m, v);
+        if (staged) s_row[j] = v;
+    });
+    m = block_max_256(m, red);  // finite: the target's score is in it
+
+    // every exponent and every term of the linear sum relative to the row maximum; a marked column: exponent 0, no linear term
+    float z = 0.f, sv = 0.f;
+    auto term = [&](float v) {
+        const float d = (v - m) * inv_T;
+        if (v != -INFINITY) sv += d;
+        const float e = expf(d);
+        z += e;
+        return v != -INFINITY ? e : -1.f;  // (staged: the mark outlives the exponent, which may be 0 for a kept column too)
+    };
+    if (staged)
+        for (int64_t j = tid; j < N; j += 256) s_row[j] = term(s_row[j]);
+    else
+        row_cols_256(row, N, [&](int64_t, float v) { term(v); });
+    z = block_sum_256(z, red);  // lane-strided partial sums, then the fixed tree
+    sv = block_sum_256(sv, red);
+    const float inv = 1.f / z, coef = wi * inv_T / W;
+    const float y0 = eps / (float)n, yt = 1.f - eps * ((float)(n - 1) / (float)n);  // (n = 1: the target's label is exactly 1)
+    auto seed = [&](int64_t j, float e) { return e < 0.f ? 0.f : coef * (e * inv - (j == t ? yt : y0)); };
+    if (staged)
+        for (int64_t j = tid; j < N; j += 256) row[j] = seed(j, s_row[j]);
+    else
+        row_cols_256(row, N, [&](int64_t j, float v) { row[j] = seed(j, v != -INFINITY ? expf((v - m) * inv_T) : -1.f); });
+    for (int64_t j = N + tid; j < ld; j += 256) row[j] = 0.f;  // the forward's pad columns
+    if (tid == 0) {
+        pos[i] = p_i;
+        rowpart[i] = wi * (logf(z) - (1.f - eps) * ((p_i - m) * inv_T) - y0 * sv);
+    }
+}
+
+static void all_softmax_filtered_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride,
+                                        const int64_t *sample, bool head, int64_t R, const int64_t *keys, int64_t n_keys,
+                                        const float *weight, const float *weight_sum, float T, float eps, float *loss, float *pos,
+                                        float *scratch, hipStream_t st) {
+    all_loss_launch(weight, weight_sum, B, loss, scratch, st, [&](const RowLoss &L) {
+        const size_t lds = N <= kAllStageCols ? (size_t)N * sizeof(float) : 0;
+        hipLaunchKernelGGL(all_softmax_filtered_kernel, dim3((unsigned)B), dim3(256), lds, st, S, (int)B, N, ld, target, tstride, sample,
+                           head ? 1 : 0, R, keys, n_keys, weight, L.scal_in, L.scal_out, 1.f / T, eps, pos, L.rowpart);
     });
 }
 
@@ -356,9 +462,10 @@ static int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const 
     return MKB_OK;
 }
 
-// what the two KvsAll entry points check of their label arguments (N, R: the table sizes the keys were built for)
-static int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n_keys, float eps) {
-    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "KvsAll needs head-batch or tail-batch");
+// what the entry points that read the key arrays (KvsAll, filtered 1vsAll: `what`) check of their label arguments (N, R: the table
+// sizes the keys were built for)
+static int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n_keys, float eps, const char *what = "KvsAll") {
+    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "%s needs head-batch or tail-batch", what);
     MKB_REQUIRE(n_keys >= 0 && (keys || n_keys == 0), "keys may be null only with n_keys == 0, and n_keys must be >= 0");
     MKB_REQUIRE(eps - eps == 0.f && eps >= 0.f && eps < 1.f, "the label smoothing must be finite and in [0, 1)");
     int64_t nq, top;  // the largest value a range bound takes: ((N - 1) R + R - 1) N + N <= (N R + R) N
@@ -368,7 +475,7 @@ static int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n
     return MKB_OK;
 }
 
-// The step behind mkb_all_step and mkb_all_kvs_step, whose checks (all_check among them) have passed: the forward block, the loss
+// The step behind mkb_all_step, mkb_all_kvs_step and mkb_all_filtered_step, whose checks (all_check among them) have passed: the forward block, the loss
 // on it -- loss(S, ld, scratch) launches it from the forward's finish and leaves dS in S --, the backward.
 template <class Loss>
 static int all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode, const AllPlan &P, void *ws,
@@ -472,5 +579,33 @@ extern "C" int mkb_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, c
     return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
         all_bce_launch(S, B, tb->n_entity, ld, sample, mode == MKB_MODE_HEAD, tb->n_relation, keys, n_keys, weight, weight_sum, smoothing,
                        sum_over_entities != 0, loss, pos, scratch, st);
+    });
+}
+
+extern "C" int mkb_all_softmax_filtered(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t target_stride,
+                                        const int64_t *sample, int mode, int64_t n_relation, const int64_t *keys, int64_t n_keys,
+                                        const float *weight, const float *weight_sum, float T, float smoothing, float *loss, float *pos,
+                                        float *scratch, void *stream) {
+    MKB_REQUIRE(sample, "null pointer");
+    if (int rc = softmax_check(S, B, N, ld, target, target_stride, T, loss, pos, scratch)) return rc;
+    if (int rc = bce_check(N, n_relation, mode, keys, n_keys, smoothing, "filtered 1vsAll")) return rc;
+    all_softmax_filtered_launch(S, B, N, ld, target, target_stride, sample, mode == MKB_MODE_HEAD, n_relation, keys, n_keys, weight,
+                                weight_sum, T, smoothing, loss, pos, scratch, (hipStream_t)stream);
+    MKB_LAUNCH_CHECK();
+    return MKB_OK;
+}
+
+extern "C" int mkb_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
+                                     int mode, const int64_t *keys, int64_t n_keys, float T, float smoothing, const float *weight_sum,
+                                     float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream) {
+    AllPlan P;
+    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
+    MKB_REQUIRE(T - T == 0.f && T > 0.f, "the softmax temperature must be finite and > 0");
+    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
+    if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing, "filtered 1vsAll")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
+        all_softmax_filtered_launch(S, B, tb->n_entity, ld, sample + (mode == MKB_MODE_HEAD ? 0 : 2), 3, sample, mode == MKB_MODE_HEAD,
+                                    tb->n_relation, keys, n_keys, weight, weight_sum, T, smoothing, loss, pos, scratch, st);
     });
 }

@@ -362,20 +362,37 @@ class OneVsAllStep(_AllEntityStep):
     """``loss = step(sample, weight, mode)``: the 1vsAll softmax step of ComplEx / DistMult.  Every entity is scored for each
     ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``) and the cross entropy is taken over the whole row, at
     ``temperature``; fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.  ``positive_score``
-    [B, 1] of the last call stays available.  One library call (``mkb_all_step``), no autograd, no negatives, no filtering of a
-    row's other known answers.  ``weight``: [B] or None (all ones); ``weight_sum`` and ``regularizer``: as for ``FusedTrainStep``.
+    [B, 1] of the last call stays available.  One library call (``mkb_all_step``), no autograd, no negatives.  ``weight``: [B] or
+    None (all ones); ``weight_sum`` and ``regularizer``: as for ``FusedTrainStep``.
+
+    ``true_triples`` (not None) filters: a row's OTHER known answers in them -- the columns the filtered evaluation leaves out of
+    the rank -- are taken out of its softmax and get a gradient of exactly 0; they are read from the sorted key arrays of the
+    filtered ranking (``utils.true_keys``, built once), no [B, n_entity] mask exists.  ``label_smoothing`` spreads that much of the
+    label over the columns that stay (``losses.OneVsAll`` has the formulas).  With either, the one call is
+    ``mkb_all_filtered_step``: the same products around another loss kernel.
 
     Optimizers: the step writes EVERY entity row.  A row-lazily stepped table (``optim.Adam(lazy_rows=True)``) is flushed first and
     its step then takes the route "touched rows unknown -> dense"; ``optim.Adagrad`` uses its all-rows form."""
 
-    def __init__(self, model, temperature=1.0, regularizer=None):
+    def __init__(self, model, temperature=1.0, regularizer=None, label_smoothing=0.0, true_triples=None):
         super().__init__(model, regularizer)
         self.temperature = ns_losses._checked("temperature", temperature, positive=True)
+        self.label_smoothing = kvs_all.checked_settings(label_smoothing, kvs_all.REDUCTIONS[0])[0]
+        self.true_triples = true_triples
 
     def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
-        _hip.check(_hip.lib().mkb_all_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, self.temperature,
-                                           _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
-                                           _hip.stream_ptr()), "mkb_all_step")
+        if self.true_triples is None and self.label_smoothing == 0.0:
+            _hip.check(_hip.lib().mkb_all_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, self.temperature,
+                                               _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
+                                               _hip.stream_ptr()), "mkb_all_step")
+            return
+        m, keys = self.model, None
+        if self.true_triples is not None:
+            keys = true_keys(self.true_triples, sample.device, m.n_entity, m.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
+        _hip.check(_hip.lib().mkb_all_filtered_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, _hip.ptr(keys),
+                                                    0 if keys is None else keys.numel(), self.temperature, self.label_smoothing,
+                                                    _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
+                                                    _hip.stream_ptr()), "mkb_all_filtered_step")
 
 
 class KvsAllStep(_AllEntityStep):

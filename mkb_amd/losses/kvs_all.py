@@ -58,6 +58,14 @@ def launch(S, n_cols, sample, mode_id, n_relation, keys, weight, weight_sum, lab
     return loss, pos
 
 
+def relation_count(loss):
+    """The ``n_relation`` a loss that holds ``true_triples`` assumes when none is given: 1 + their largest relation id (kept until
+    their number changes)."""
+    if loss._n_relation is None or loss._n_relation[0] != len(loss.true_triples):
+        loss._n_relation = (len(loss.true_triples), 1 + max((int(t[1]) for t in loss.true_triples), default=0))
+    return loss._n_relation[1]
+
+
 class KvsAll:
     kind = None  # (not one of mkb_ns_loss's kinds: fused.PooledLossStep refuses it)
 
@@ -65,11 +73,6 @@ class KvsAll:
         self.label_smoothing, self.reduction = checked_settings(label_smoothing, reduction)
         self.true_triples = true_triples
         self._n_relation = None
-
-    def _relations(self):
-        if self._n_relation is None or self._n_relation[0] != len(self.true_triples):
-            self._n_relation = (len(self.true_triples), 1 + max((int(t[1]) for t in self.true_triples), default=0))
-        return self._n_relation[1]
 
     def __call__(self, scores, sample, mode, weight=None, n_relation=None):
         _hip.require_device(scores, sample, weight)
@@ -83,7 +86,7 @@ class KvsAll:
         s, w = _rows.f32(scores), _rows.f32(weight)
         if s.shape[0] == 0:
             return _rows.empty_batch(w, s)
-        n_relation = self._relations() if n_relation is None else int(n_relation)
+        n_relation = relation_count(self) if n_relation is None else int(n_relation)
         keys = true_keys(self.true_triples, s.device, s.size(1), n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
         sample = _hip.contiguous(sample, torch.int64)
         return _rows.SeedsInPlaceFn.apply(s, lambda S: launch(S, S.shape[1], sample, mode_id, n_relation, keys, w, None, self.label_smoothing,

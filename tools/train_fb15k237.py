@@ -3,12 +3,13 @@ FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamm
 
     python tools/train_fb15k237.py [--epochs 200] [--lr 5e-5] [--eval-every 50] [--model RotatE]
                                    [--loss adversarial|margin|pairwise|softmax|onevsall|kvsall] [--reg none|l2|n3] [--reg-weight 1e-3]
-                                   [--optimizer adam|adagrad]
+                                   [--optimizer adam|adagrad] [--label-smoothing 0.1] [--filter-known]
 
 --loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
 --alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
 PooledLossStep, or onevsall (OneVsAll(--temperature) through OneVsAllStep: ComplEx / DistMult, every entity scored for each row, no
-negatives drawn; --size is then not used), or kvsall (KvsAllStep: the same two models, binary cross entropy against the multi-hot
+negatives drawn; --size is then not used; --label-smoothing, and --filter-known to take a row's other known answers in the
+training triples out of its softmax), or kvsall (KvsAllStep: the same two models, binary cross entropy against the multi-hot
 labels of every known answer in the training triples, --label-smoothing, --reduction mean|sum over the entities).  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
 handed to the step.  --optimizer: adam (the default: row-lazy optim.Adam) or adagrad (row-sparse optim.Adagrad; the literature's
 ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.
@@ -41,7 +42,8 @@ def main():
     ap.add_argument("--dataset", default="Fb15k237")
     ap.add_argument("--loss", default="adversarial", choices=["adversarial", "margin", "pairwise", "softmax", "onevsall", "kvsall"])
     ap.add_argument("--temperature", type=float, default=1.0, help="--loss softmax / onevsall")
-    ap.add_argument("--label-smoothing", type=float, default=0.0, help="--loss kvsall")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="--loss onevsall / kvsall")
+    ap.add_argument("--filter-known", action="store_true", help="--loss onevsall: filter a row's other known training answers")
     ap.add_argument("--reduction", default="mean", choices=["mean", "sum"], help="--loss kvsall: over the entities of a row")
     ap.add_argument("--reg", default="none", choices=["none", "l2", "n3"])
     ap.add_argument("--reg-weight", type=float, default=1e-3, help="--reg l2 / n3")
@@ -65,7 +67,8 @@ def main():
     if args.loss == "adversarial":
         step = FusedTrainStep(model, args.alpha, regularizer=reg)
     elif args.loss == "onevsall":
-        step = OneVsAllStep(model, temperature=args.temperature, regularizer=reg)
+        step = OneVsAllStep(model, temperature=args.temperature, regularizer=reg, label_smoothing=args.label_smoothing,
+                            true_triples=ds.train if args.filter_known else None)
     elif args.loss == "kvsall":
         step = KvsAllStep(model, ds.train, label_smoothing=args.label_smoothing, reduction=args.reduction, regularizer=reg)
     else:
