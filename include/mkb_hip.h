@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
-#define MKB_ABI_VERSION 8
+/* 9: lr, beta1 and beta2 of the five mkb_adam_* calls are doubles (floats through 8).  The notes "under ABI 8" below say when a
+ * group of symbols was added; all of them are part of 9. */
+#define MKB_ABI_VERSION 9
 
 typedef enum {
     MKB_OK = 0,
@@ -208,9 +210,11 @@ int mkb_kl_divergence(const float *student, const float *teacher, int64_t n, int
  * == torch.optim.Adam(lr, betas, eps).step() + zero_grad() for one parameter tensor as the README loop
  * uses it (README.md:123-126, pipeline.py:238-240): every element moves every step.  step is 1-based.
  * zero_grad != 0 also clears g (fused optimizer.zero_grad()).
+ * lr, beta1 and beta2 are doubles, as torch holds them: 1 - beta and the bias corrections are formed in double from the caller's
+ * own values and rounded once (from a float beta2 = 0.999f, 1 - beta2 is off by 1.3e-5 of itself, and exp_avg_sq with it).
  */
-int mkb_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, float lr,
-                  float beta1, float beta2, float eps, int zero_grad, void *stream);
+int mkb_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, double lr,
+                  double beta1, double beta2, float eps, int zero_grad, void *stream);
 
 typedef struct {
     float *param, *grad, *exp_avg, *exp_avg_sq; /* a small dense tensor (e.g. the relation table), 16-byte aligned */
@@ -220,7 +224,7 @@ typedef struct {
 /* mkb_adam_step for up to 8 parameter tensors in ONE launch (each with its own step count): what an optimizer over a model's
  * few dense tensors does per step -- small models are bound by launches, not by bytes (Umls TransE-64: 9 launches of ~5 us).
  * draw_ahead: null, or a sampler whose next pool draw runs as one more workgroup of this launch (see below). */
-int mkb_adam_step_multi(const mkb_adam_dense_t *tensors_host, int n_tensors, float lr, float beta1, float beta2, float eps,
+int mkb_adam_step_multi(const mkb_adam_dense_t *tensors_host, int n_tensors, double lr, double beta1, double beta2, float eps,
                         int zero_grad, mkb_sampler_t *draw_ahead, void *stream);
 
 /* ---- row-lazy Adam: the same dense Adam, bit for bit, with the steps of untouched rows deferred (mkb_amd/csrc/adam.hip) ----
@@ -256,15 +260,15 @@ int mkb_adam_step_multi(const mkb_adam_dense_t *tensors_host, int n_tensors, flo
  *   pool holds global ids): the pool entries this rank owns, then the shard indices local_ids [n_local_ids].
  */
 int mkb_adam_rows_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                       int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step, float lr, float beta1,
-                       float beta2, float eps, const mkb_adam_dense_t *rider, void *stream);
+                       int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step, double lr, double beta1,
+                       double beta2, float eps, const mkb_adam_dense_t *rider, void *stream);
 int mkb_adam_rows_advance(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
                           int64_t n_rows, int64_t D, const int64_t *global_ids, int64_t n_global, int world, int rank,
-                          const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr, float beta1, float beta2,
+                          const int64_t *ids, int64_t n_ids, int64_t step_upto, double lr, double beta1, double beta2,
                           float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead, void *stream);
 int mkb_adam_rows_advance_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
                                    int64_t n_rows, int64_t D, int world, int rank, const int64_t *local_ids,
-                                   int64_t n_local_ids, int64_t step_upto, float lr, float beta1, float beta2, float eps,
+                                   int64_t n_local_ids, int64_t step_upto, double lr, double beta1, double beta2, float eps,
                                    const mkb_adam_dense_t *rider, mkb_sampler_t *sampler, const int64_t *sample, int64_t B,
                                    int mode, int64_t *neg, int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched,
                                    void *stream);

@@ -6,7 +6,7 @@ infrastructure and is never imported from here).
 """
 import ctypes
 import pathlib
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint16, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint16, c_uint32, c_void_p
 
 import torch
 
@@ -14,7 +14,7 @@ import os
 
 # MKB_HIP_LIB selects an experimental build of the same ABI (tools/kbench.py); default = the in-tree product library
 _LIB_PATH = pathlib.Path(os.environ.get("MKB_HIP_LIB") or (pathlib.Path(__file__).resolve().parent / "libmkb_hip.so"))
-ABI_VERSION = 8  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a symbol or a signature changes)
+ABI_VERSION = 9  # == MKB_ABI_VERSION of include/mkb_hip.h (bumped whenever a symbol or a signature changes)
 
 MODEL_IDS = {"TransE": 0, "RotatE": 1, "ComplEx": 2, "DistMult": 3, "pRotatE": 4}
 MODE_DEFAULT, MODE_HEAD, MODE_TAIL = 0, 1, 2
@@ -71,7 +71,7 @@ _lib = None
 #   param, grad, exp_avg, exp_avg_sq, last, consts, n_rows, D
 _ROWS_TABLE = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]
 #   step, lr, beta1, beta2, eps, rider
-_ROWS_STEP = [c_int64, c_float, c_float, c_float, c_float, POINTER(AdamDense)]
+_ROWS_STEP = [c_int64, c_double, c_double, c_double, c_float, POINTER(AdamDense)]
 #   sampler, sample, B, mode, neg, pool, pos, cnt, touched, stream (the arguments of mkb_sampler_generate)
 _SAMPLER_TAIL = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 
@@ -107,9 +107,9 @@ _SIGNATURES = {
                                    c_void_p, c_void_p]),
     "mkb_pool_score_bwd": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                    c_void_p, c_void_p, c_void_p]),
-    "mkb_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_float,
+    "mkb_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, c_double, c_double,
                               c_float, c_int, c_void_p]),
-    "mkb_adam_step_multi": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
+    "mkb_adam_step_multi": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_float, c_int, c_void_p, c_void_p]),
     "mkb_profile_enable": (c_int, [c_int, c_int]),
     "mkb_profile_read": (c_int, [c_int, POINTER(c_int64), POINTER(ctypes.c_double)]),
     "mkb_adam_rows_step": (c_int, _ROWS_TABLE + [c_void_p, c_int64] + _ROWS_STEP + [c_void_p]),

@@ -7,6 +7,7 @@
 // Pure HBM streaming: 4 reads + 3 writes (+1 write when zeroing g) of n floats; float4 per lane,
 // grid-stride over <= 2048 workgroups.
 #include "common.h"
+#include "adam_plan.h"
 #include "sampler_draw.h"
 
 #include <math.h>
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, float 
 struct StepScalars {
     float neg_step, sqrt_bc2;
 };
-static StepScalars step_scalars(float lr, float beta1, float beta2, int64_t step) {
+static StepScalars step_scalars(double lr, double beta1, double beta2, int64_t step) {
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     return {(float)(-((double)lr / bc1)), (float)sqrt(bc2)};
@@ -80,28 +81,28 @@ struct DenseWork {
     StepScalars s;
     int64_t blocks;
 };
-static int dense_work(DenseWork &w, const mkb_adam_dense_t &T, float lr, float beta1, float beta2, int threads, int64_t max_blocks) {
+static int dense_work(DenseWork &w, const mkb_adam_dense_t &T, double lr, double beta1, double beta2, int threads, int64_t max_blocks) {
     MKB_REQUIRE(T.param && T.grad && T.exp_avg && T.exp_avg_sq, "dense tensor: null pointer");
     MKB_REQUIRE(T.n >= 0 && T.step >= 1, "dense tensor: bad n / step");
     MKB_REQUIRE((((uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.exp_avg | (uintptr_t)T.exp_avg_sq) & 15) == 0,
                 "buffers must be 16-byte aligned");
     w.s = step_scalars(lr, beta1, beta2, T.step);
-    w.blocks = std::min(std::max(((T.n >> 2) + threads - 1) / threads, (int64_t)1), max_blocks);
+    w.blocks = adam_dense_blocks(T.n, threads, max_blocks);
     return MKB_OK;
 }
 
 }  // namespace mkb
 
 extern "C" int mkb_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step,
-                             float lr, float beta1, float beta2, float eps, int zero_grad, void *stream) {
+                             double lr, double beta1, double beta2, float eps, int zero_grad, void *stream) {
     mkb::DenseWork w;
     const mkb_adam_dense_t T{param, grad, exp_avg, exp_avg_sq, n, step};
-    if (int rc = mkb::dense_work(w, T, lr, beta1, beta2, 256, 2048)) return rc;
+    if (int rc = mkb::dense_work(w, T, lr, beta1, beta2, mkb::kAdamHostThreads, mkb::kAdamDenseMaxBlocks)) return rc;
     if (n == 0) return MKB_OK;
     const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
     mkb::ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
     hipLaunchKernelGGL(mkb::adam_kernel, dim3((unsigned)w.blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                       exp_avg_sq, n, w1, beta2, w2, w.s.neg_step, w.s.sqrt_bc2, eps, zero_grad);
+                       exp_avg_sq, n, w1, (float)beta2, w2, w.s.neg_step, w.s.sqrt_bc2, eps, zero_grad);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }
@@ -133,17 +134,17 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamMultiArgs A) {
 }
 }  // namespace mkb
 
-extern "C" int mkb_adam_step_multi(const mkb_adam_dense_t *tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
+extern "C" int mkb_adam_step_multi(const mkb_adam_dense_t *tensors, int n_tensors, double lr, double beta1, double beta2, float eps,
                                    int zero_grad, mkb_sampler_t *draw_ahead, void *stream) {
     MKB_REQUIRE(tensors && n_tensors >= 1 && n_tensors <= mkb::kAdamMulti, "1..%d tensors", mkb::kAdamMulti);
     mkb::AdamMultiArgs A{};
-    A.n_tensors = n_tensors; A.zero_grad = zero_grad; A.eps = eps; A.b2 = beta2;
+    A.n_tensors = n_tensors; A.zero_grad = zero_grad; A.eps = eps; A.b2 = (float)beta2;
     A.w1 = (float)(1.0 - (double)beta1); A.w2 = (float)(1.0 - (double)beta2);
     int blocks = 0;
     for (int t = 0; t < n_tensors; ++t) {
         const mkb_adam_dense_t &T = tensors[t];
         mkb::DenseWork w;
-        if (int rc = mkb::dense_work(w, T, lr, beta1, beta2, 256, 2048)) return rc;
+        if (int rc = mkb::dense_work(w, T, lr, beta1, beta2, mkb::kAdamHostThreads, mkb::kAdamDenseMaxBlocks)) return rc;
         A.p[t] = T.param; A.g[t] = T.grad; A.m[t] = T.exp_avg; A.v[t] = T.exp_avg_sq; A.n[t] = T.n;
         A.neg_step[t] = w.s.neg_step; A.sqrt_bc2[t] = w.s.sqrt_bc2;
         A.first_block[t] = blocks;
@@ -219,19 +220,7 @@ struct AdamRowArgs {
     int64_t n_table;
 };
 
-// workgroup size of the catch-up / advance kernel (the sampler's filter and draw blocks that ride it are sized by it too)
-// 512 lanes: one 2000-float row per workgroup, two workgroups per CU (107 VGPRs): their phases -- ownership exchange, loads, replay,
-// stores -- interleave.  Round 4, same box, 1024 -> 512 lanes: headline step 0.2273 -> 0.2242 ms, WN18RR 0.1302 -> 0.1262, YAGO3-10
-// 0.1933 -> 0.1862 (256 lanes: better still for YAGO3-10's long replays, worse at the headline; variants built with
-// -DMKB_CATCH_THREADS / -DMKB_REPLAY_UNROLL by tools/kbench.py)
-#ifndef MKB_CATCH_THREADS
-#define MKB_CATCH_THREADS 512
-#endif
-constexpr int kCatchThreads = MKB_CATCH_THREADS;
-#ifndef MKB_REPLAY_UNROLL
-#define MKB_REPLAY_UNROLL 4
-#endif
-constexpr int kReplayUnroll = MKB_REPLAY_UNROLL;  // pending zero-gradient steps replayed side by side
+// (kCatchThreads, the workgroup size of the catch-up / advance kernel, and kReplayUnroll: adam_plan.h)
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 // adam_one (with a gradient, and at g = 0) on two elements at once (v_pk_* where the scalar code has v_*: the same IEEE operations,
@@ -549,84 +538,55 @@ __global__ __launch_bounds__(256) void adam_rows_step_kernel(AdamRowArgs A) {
 }
 
 static int fill_args(AdamRowArgs &A, float *param, float *grad, float *m, float *v, int32_t *last, float *consts,
-                     const int64_t *ids, int64_t D, int64_t step, float lr, float beta1, float beta2, float eps) {
+                     const int64_t *ids, int64_t D, int64_t step, double lr, double beta1, double beta2, float eps) {
     MKB_REQUIRE(param && m && v && last && consts, "null pointer");
     MKB_REQUIRE(D > 0 && D < INT32_MAX && step >= 0 && step < INT32_MAX, "bad D / step");
     A.p = param; A.g = grad; A.m = m; A.v = v; A.last = last; A.consts = (float2 *)consts; A.ids = ids; A.D = D;
     A.step = (int32_t)step;
-    A.w1 = (float)(1.0 - (double)beta1); A.b2 = beta2; A.w2 = (float)(1.0 - (double)beta2); A.eps = eps;
+    A.w1 = (float)(1.0 - (double)beta1); A.b2 = (float)beta2; A.w2 = (float)(1.0 - (double)beta2); A.eps = eps;
     const StepScalars s = step_scalars(lr, beta1, beta2, step > 0 ? step : 1);
     A.neg_step = s.neg_step; A.sqrt_bc2 = s.sqrt_bc2;
     return MKB_OK;
 }
 
-// Sweep.  Exact dense Adam moves every parameter every step, so the replay's arithmetic is N x D element-steps per step no
-// matter when it happens (measured: ~85 ns per wave and pending step at 4 elements per lane: WN18RR +16 us, FB15k-237
-// +12 us, YAGO3-10 ~40 us per launch if spread evenly).  It is NOT spread evenly when entities are rare: a YAGO3-10 entity
-// that only the random pool reaches waits ~1,500 steps in the tail, its chain is serial, and the launch lasts as long as
-// its longest chain (99 us measured).  So when the mean gap N / rows-per-step is large, each per-step launch also visits
-// a moving window of min(N / period, rows-of-this-launch) rows: every row is brought up to date at least once per
-// max(period, N / rows-per-launch) steps (the window never exceeds the launch's own row count, so for N > period * rows the
-// bound is N / rows; the window's start is a function of the step and of THAT launch's window, so launches with different row
-// counts -- a catch-up of a few ids between two training steps -- move it unevenly: a latency aid, not a guarantee).  Same
-// arithmetic, same results bit for bit (every pending step of every row is replayed exactly once, whenever that happens);
-// cost: the window's rows x (p, m, v) in + out.  YAGO3-10: 99 -> 64 us per launch, step 0.268 -> 0.211 ms; WN18RR / FB15k-237
-// (mean gap 18 / 6 steps, every entity is a positive often enough): no gain, so no sweep.
-// Round 5, with the replay's per-step round trips gone and in runs long enough for the gaps to reach their steady state (1,500
-// steps): WN18RR's launch 36.5 us without a sweep, 31.3-31.9 with a period of 24-48 (step 0.1193 -> 0.1144 ms), 32.5 at 128;
-// YAGO3-10 91.8 without, 53.1 / 54.5 / 65.1 / 79.0 at 32 / 64 / 128 / 256; FB15k-237 37.7 without, 37.7-39.1 with.  Hence: a
-// period of 32 from a mean gap of 12 steps on.
-constexpr int kSweepPeriod = 32, kSweepMinGap = 12;
-
-static void set_row_blocks(AdamRowArgs &A, int64_t rows, int64_t n_table = 0) {
-    int64_t sweep = 0;
-    A.n_batch_rows = (int32_t)rows; A.sweep_start = 0; A.n_table = n_table;
-    if (rows > 0 && n_table > 0 && A.step > 0) {
-        const char *fe = getenv("MKB_ADAM_SWEEP");  // period, 0 = off (read per call: the tests switch it within one process)
-        const int forced = fe ? atoi(fe) : -1;
-        if (forced > 0) sweep = (n_table + forced - 1) / forced;
-        else if (forced < 0 && n_table >= (int64_t)kSweepMinGap * rows) sweep = std::min((n_table + kSweepPeriod - 1) / kSweepPeriod, rows);
-        if (sweep > 0) {
-            A.sweep_start = (int32_t)((((int64_t)A.step - 1) * sweep) % n_table);
-            rows += sweep;
-        }
-    }
-    bool vec4 = (A.D & 3) == 0 && (((uintptr_t)A.p | (uintptr_t)A.m | (uintptr_t)A.v | (uintptr_t)A.g) & 15) == 0;
-    A.vec4 = vec4 ? 1 : 0;
-    // as many rows per workgroup (kCatchThreads lanes) as fit with one chunk per lane (whole waves per row): at 1024 lanes 2000-float rows 2,
-    // 1000-float rows 4, the 250-float rows of an 8-way dimension shard 8 -- short rows used to idle most of the lanes
-    const int64_t per_lane = vec4 ? 4 : 2;
-    int64_t lanes = ((A.D + per_lane - 1) / per_lane + 63) / 64 * 64;
-    int rpb = 1;
-    while (rpb < 16 && (int64_t)kCatchThreads / (rpb * 2) >= lanes) rpb *= 2;
-    A.rows_per_block = rpb;
-    A.n_rows_listed = (int32_t)rows;
-    A.n_ids = (int32_t)((rows + A.rows_per_block - 1) / A.rows_per_block);
+// The environment's part of the plan: MKB_ADAM_SWEEP = period, 0 = off (read per call: the tests switch it within one process)
+static int forced_sweep() {
+    const char *fe = getenv("MKB_ADAM_SWEEP");
+    return fe ? atoi(fe) : -1;
 }
 
-// dense rider of a row-lazy launch (its extra workgroups have `threads` lanes) -> their number (0 = none)
-static int attach_rider(AdamRowArgs &A, const mkb_adam_dense_t *rider, float lr, float beta1, float beta2, int threads,
-                        int64_t *extra) {
-    *extra = 0;
-    if (!rider || rider->n <= 0) return MKB_OK;
+static bool aligned16(const AdamRowArgs &A) {
+    return (((uintptr_t)A.p | (uintptr_t)A.m | (uintptr_t)A.v | (uintptr_t)A.g) & 15) == 0;
+}
+
+// plan_adam_rows (adam_plan.h) decides the launch -- kernel, rows per workgroup, access width, the sweep window (see there), the
+// rider's workgroups; this writes its row geometry into the kernel's arguments
+static AdamRowsPlan plan_rows(AdamRowArgs &A, int64_t rows, int64_t n_table, bool listed, const mkb_adam_dense_t *rider) {
+    const AdamRowsPlan P = plan_adam_rows(AdamRowsCall::Advance, AdamRowsShape{A.D, aligned16(A), rows, n_table, A.step, listed, forced_sweep(),
+                                                                               rider && rider->n > 0 ? rider->n : 0});
+    A.n_batch_rows = (int32_t)rows; A.sweep_start = (int32_t)P.sweep_start; A.n_table = P.table_bound;
+    A.vec4 = P.vec4;
+    A.rows_per_block = P.rows_per_block;
+    A.n_rows_listed = (int32_t)P.rows_listed;
+    A.n_ids = (int32_t)P.row_blocks;
+    return P;
+}
+
+// dense rider of a row-lazy launch, checked; the plan's rider_blocks extra workgroups of the launch stream it
+static int attach_rider(AdamRowArgs &A, const mkb_adam_dense_t *rider, double lr, double beta1, double beta2, const AdamRowsPlan &P) {
+    if (P.rider_blocks == 0) return MKB_OK;
     DenseWork w;
-    if (int rc = dense_work(w, *rider, lr, beta1, beta2, threads, 1024)) return rc;
+    if (int rc = dense_work(w, *rider, lr, beta1, beta2, P.threads, kAdamRiderMaxBlocks)) return rc;
     A.dp = rider->param; A.dg = rider->grad; A.dm = rider->exp_avg; A.dv = rider->exp_avg_sq; A.dn = rider->n;
     A.d_neg_step = w.s.neg_step; A.d_sqrt_bc2 = w.s.sqrt_bc2;
-    *extra = w.blocks;
     return MKB_OK;
-}
-
-// mean gap between two visits of a row = table rows / rows a launch lists: short gaps take the lean replay (see the kernel)
-static bool short_gaps(const AdamRowArgs &A) {
-    return A.n_table > 0 && A.n_batch_rows > 0 && (int64_t)A.n_table < (int64_t)12 * A.n_batch_rows;
 }
 
 // need_big_lds: the sampler's filter blocks ride (16 rows per filter workgroup need ~73 KB of dynamic LDS: opt in once per
 // device and instance; 160 KB per CU)
-static int launch_catchup(const AdamRowArgs &A, int64_t grid, size_t lds, hipStream_t st, bool need_big_lds) {
+static int launch_catchup(const AdamRowArgs &A, const AdamRowsPlan &P, int64_t grid, size_t lds, hipStream_t st, bool need_big_lds) {
     static LdsOptIn big_lds[2];
-    if (short_gaps(A)) {
+    if (P.kernel == AdamRowsKernel::CatchupLean) {
         if (need_big_lds)
             if (int rc = big_lds[0].ensure(reinterpret_cast<const void *>(&adam_rows_catchup_kernel<1>), 96 * 1024)) return rc;
         hipLaunchKernelGGL(adam_rows_catchup_kernel<1>, dim3((unsigned)grid), dim3(kCatchThreads), lds, st, A);
@@ -643,12 +603,12 @@ static int launch_catchup(const AdamRowArgs &A, int64_t grid, size_t lds, hipStr
 
 extern "C" int mkb_adam_rows_advance(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
                                      int64_t n_rows, int64_t D, const int64_t *global_ids, int64_t n_global, int world, int rank,
-                                     const int64_t *ids, int64_t n_ids, int64_t step_upto, float lr, float beta1, float beta2,
+                                     const int64_t *ids, int64_t n_ids, int64_t step_upto, double lr, double beta1, double beta2,
                                      float eps, const mkb_adam_dense_t *rider, mkb_sampler_t *draw_ahead, void *stream) {
     using namespace mkb;
     MKB_REQUIRE(grad || !rider, "a dense rider needs the advance form (grad != null)");
     AdamRowArgs A{};
-    if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, ids, D, step_upto, grad ? lr : 0.f, beta1, beta2, eps))
+    if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, ids, D, step_upto, grad ? lr : 0.0, beta1, beta2, eps))
         return rc;
     int64_t n = ids ? n_ids : n_rows;
     if (global_ids) {
@@ -661,27 +621,25 @@ extern "C" int mkb_adam_rows_advance(float *param, float *grad, float *exp_avg, 
     if (n <= 0 || step_upto <= 0) n = 0;  // nothing can be pending before the first step
     MKB_REQUIRE(n <= INT32_MAX, "too many rows");
     const bool listed = ids || global_ids;
-    set_row_blocks(A, n, listed ? n_rows : 0);  // (a flush walks the whole table anyway)
-    int64_t extra = 0;
-    if (!listed && A.n_rows_listed > 0) {  // the whole table
-        if (int rc = attach_rider(A, rider, lr, beta1, beta2, 256, &extra)) return rc;
+    const AdamRowsPlan P = plan_rows(A, n, n_rows, listed, rider);
+    if (int rc = attach_rider(A, rider, lr, beta1, beta2, P)) return rc;
+    if (P.kernel == AdamRowsKernel::Flush) {  // the whole table
         ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
-        hipLaunchKernelGGL(adam_rows_flush_kernel, dim3((unsigned)(A.n_rows_listed + extra)), dim3(256), 0, (hipStream_t)stream, A);
+        hipLaunchKernelGGL(adam_rows_flush_kernel, dim3((unsigned)(P.row_blocks + P.rider_blocks)), dim3(P.threads), 0, (hipStream_t)stream, A);
         MKB_LAUNCH_CHECK();
         return MKB_OK;
     }
-    if (int rc = attach_rider(A, rider, lr, beta1, beta2, kCatchThreads, &extra)) return rc;
-    if (A.n_ids + extra == 0) return MKB_OK;
+    if (P.row_blocks + P.rider_blocks == 0) return MKB_OK;
     size_t lds = 0;
     if (draw_ahead && listed && sampler_draw_ahead(draw_ahead, &A.draw, &lds)) A.first_row_block = 1;
     ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
-    return launch_catchup(A, A.n_ids + extra + A.first_row_block, lds, (hipStream_t)stream, false);
+    return launch_catchup(A, P, P.row_blocks + P.rider_blocks + A.first_row_block, lds, (hipStream_t)stream, false);
 }
 
 extern "C" int mkb_adam_rows_advance_generate(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last,
                                               float *consts, int64_t n_rows, int64_t D, int world, int rank,
-                                              const int64_t *local_ids, int64_t n_local_ids, int64_t step_upto, float lr,
-                                              float beta1, float beta2, float eps, const mkb_adam_dense_t *rider,
+                                              const int64_t *local_ids, int64_t n_local_ids, int64_t step_upto, double lr,
+                                              double beta1, double beta2, float eps, const mkb_adam_dense_t *rider,
                                               mkb_sampler_t *sampler, const int64_t *sample, int64_t B, int mode, int64_t *neg,
                                               int64_t *pool, int32_t *pos, uint16_t *cnt, int64_t *touched, void *stream) {
     using namespace mkb;
@@ -692,7 +650,7 @@ extern "C" int mkb_adam_rows_advance_generate(float *param, float *grad, float *
                 "bad ownership");
     AdamRowArgs A{};
     if (int rc = fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, nullptr, D, step_upto > 0 ? step_upto : 0,
-                           grad ? lr : 0.f, beta1, beta2, eps)) return rc;
+                           grad ? lr : 0.0, beta1, beta2, eps)) return rc;
     size_t lds = 0;
     ProfScope ps(MKB_PROF_SAMPLER, st);
     if (int rc = sampler_ride(sampler, sample, B, mode, neg, pool, pos, cnt, touched, &A.filt, &A.draw, &A.seg_pool, &lds, st, kCatchThreads))
@@ -708,24 +666,24 @@ extern "C" int mkb_adam_rows_advance_generate(float *param, float *grad, float *
         A.ids = local_ids; A.seg_pool = nullptr;
         n = (int64_t)A.own_n + n_local_ids;
     }
-    set_row_blocks(A, step_upto > 0 ? n : 0, n_rows);  // nothing is pending before the first step
-    int64_t extra = 0;
-    if (int rc = attach_rider(A, rider, lr, beta1, beta2, kCatchThreads, &extra)) return rc;
-    return launch_catchup(A, 1 + A.n_filter + A.n_ids + extra, lds, st, true);
+    const AdamRowsPlan P = plan_rows(A, step_upto > 0 ? n : 0, n_rows, true, rider);  // nothing is pending before the first step
+    if (int rc = attach_rider(A, rider, lr, beta1, beta2, P)) return rc;
+    return launch_catchup(A, P, 1 + A.n_filter + P.row_blocks + P.rider_blocks, lds, st, true);
 }
 
 extern "C" int mkb_adam_rows_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t *last, float *consts,
-                                  int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step, float lr,
-                                  float beta1, float beta2, float eps, const mkb_adam_dense_t *rider, void *stream) {
+                                  int64_t n_rows, int64_t D, const int64_t *ids, int64_t n_ids, int64_t step, double lr,
+                                  double beta1, double beta2, float eps, const mkb_adam_dense_t *rider, void *stream) {
     mkb::AdamRowArgs A{};
     if (int rc = mkb::fill_args(A, param, grad, exp_avg, exp_avg_sq, last, consts, ids, D, step, lr, beta1, beta2, eps)) return rc;
     MKB_REQUIRE(grad && ids && step >= 1 && n_ids > 0 && n_ids <= INT32_MAX, "bad arguments");
-    A.n_ids = (int32_t)n_ids;
-    A.n_table = n_rows;  // (ids past the table are skipped, not stepped out of bounds)
-    int64_t extra = 0;
-    if (int rc = mkb::attach_rider(A, rider, lr, beta1, beta2, 256, &extra)) return rc;
+    const mkb::AdamRowsPlan P = mkb::plan_adam_rows(mkb::AdamRowsCall::Step, mkb::AdamRowsShape{D, mkb::aligned16(A), n_ids, n_rows, step, true, 0,
+                                                                                                  rider && rider->n > 0 ? rider->n : 0});
+    A.n_ids = (int32_t)P.row_blocks;
+    A.n_table = P.table_bound;
+    if (int rc = mkb::attach_rider(A, rider, lr, beta1, beta2, P)) return rc;
     mkb::ProfScope ps(MKB_PROF_ADAM, (hipStream_t)stream);
-    hipLaunchKernelGGL(mkb::adam_rows_step_kernel, dim3((unsigned)(n_ids + extra)), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(mkb::adam_rows_step_kernel, dim3((unsigned)(P.row_blocks + P.rider_blocks)), dim3(P.threads), 0, (hipStream_t)stream, A);
     MKB_LAUNCH_CHECK();
     return MKB_OK;
 }

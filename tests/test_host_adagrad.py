@@ -14,12 +14,12 @@ def test_adagrad_step_is_declared_exported_and_bound_at_abi_8():
 
     header = (ROOT / "include" / "mkb_hip.h").read_text()
     assert re.search(r"\bint\s+mkb_adagrad_step\s*\(", header) and "mkb_adagrad_dense_t" in header
-    assert re.search(r"#define\s+MKB_ABI_VERSION\s+8\b", header) and _hip.ABI_VERSION == 8
+    assert re.search(r"#define\s+MKB_ABI_VERSION\s+9\b", header) and _hip.ABI_VERSION == 9
     raw = ctypes.CDLL(str(ROOT / "mkb_amd" / "libmkb_hip.so"))
     assert hasattr(raw, "mkb_adagrad_step")
     assert "mkb_adagrad_step" in _hip.EXPORTED_SYMBOLS
     lib = _hip.lib()
-    assert lib.mkb_abi_version() == 8
+    assert lib.mkb_abi_version() == 9
     assert len(lib.mkb_adagrad_step.argtypes) == 15
     assert [name for name, _ in _hip.AdagradDense._fields_] == ["param", "grad", "sum", "n"]
     assert ctypes.sizeof(_hip.AdagradDense) == 32

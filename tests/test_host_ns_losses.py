@@ -22,7 +22,7 @@ def test_symbol_signature_and_abi():
     from mkb_amd import _hip
 
     header = (ROOT / "include" / "mkb_hip.h").read_text()
-    assert re.search(r"#define MKB_ABI_VERSION 8\b", header) and _hip.ABI_VERSION == 8
+    assert re.search(r"#define MKB_ABI_VERSION 9\b", header) and _hip.ABI_VERSION == 9
     assert re.search(r"typedef enum \{ MKB_LOSS_MARGIN = 0, MKB_LOSS_PAIR_LOGISTIC = 1, MKB_LOSS_SOFTMAX = 2 \} mkb_loss_t;", header)
     decl = re.search(r"\bint mkb_ns_loss\(([^)]*)\);", header)
     assert decl
@@ -35,7 +35,7 @@ def test_symbol_signature_and_abi():
     assert _hip._SIGNATURES["mkb_ns_loss"] == (c.c_int, [ctype(p) for p in PARAMS])
     assert hasattr(ctypes.CDLL(str(ROOT / "mkb_amd" / "libmkb_hip.so")), "mkb_ns_loss")
     assert (_hip.LOSS_MARGIN, _hip.LOSS_PAIR_LOGISTIC, _hip.LOSS_SOFTMAX) == (un.MARGIN, un.PAIR_LOGISTIC, un.SOFTMAX) == (0, 1, 2)
-    assert _hip.lib().mkb_abi_version() == 8
+    assert _hip.lib().mkb_abi_version() == 9
 
 
 def test_abi_rejects_bad_arguments_before_any_launch():

@@ -42,9 +42,9 @@ def test_symbols_are_declared_exported_and_bound_under_abi_8():
     from mkb_amd import _hip
 
     header = (ROOT / "include" / "mkb_hip.h").read_text()
-    assert re.search(r"#define\s+MKB_ABI_VERSION\s+8\b", header) and _hip.ABI_VERSION == 8
+    assert re.search(r"#define\s+MKB_ABI_VERSION\s+9\b", header) and _hip.ABI_VERSION == 9
     lib = _hip.lib()
-    assert lib.mkb_abi_version() == 8
+    assert lib.mkb_abi_version() == 9
     for name, count in zip(SYMBOLS, (19, 16)):
         assert re.search(r"\b%s\s*\(" % name, header), name
         assert name in _hip.EXPORTED_SYMBOLS and hasattr(lib, name), name

@@ -25,7 +25,7 @@ def test_regulariser_symbols_signatures_and_abi():
     from mkb_amd import _hip
 
     header = (ROOT / "include" / "mkb_hip.h").read_text()
-    assert re.search(r"#define MKB_ABI_VERSION 8\b", header) and _hip.ABI_VERSION == 8
+    assert re.search(r"#define MKB_ABI_VERSION 9\b", header) and _hip.ABI_VERSION == 9
     lib = ctypes.CDLL(str(ROOT / "mkb_amd" / "libmkb_hip.so"))
     c = ctypes
 
@@ -42,7 +42,7 @@ def test_regulariser_symbols_signatures_and_abi():
         assert [" ".join(a.split()) for a in decl.group(1).split(",")] == params, name
         assert _hip._SIGNATURES[name] == ({"int": c.c_int, "int64_t": c.c_int64}[res], [ctype(p) for p in params]), name
         assert hasattr(lib, name) and name in _hip.EXPORTED_SYMBOLS, name
-    assert _hip.lib().mkb_abi_version() == 8
+    assert _hip.lib().mkb_abi_version() == 9
 
 
 def test_regulariser_abi_rejects_bad_arguments_before_any_launch():

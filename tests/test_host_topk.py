@@ -13,9 +13,9 @@ def test_topk_symbols_and_abi():
     from mkb_amd import _hip
 
     header = (ROOT / "include" / "mkb_hip.h").read_text()
-    assert re.search(r"#define MKB_ABI_VERSION 8\b", header)
+    assert re.search(r"#define MKB_ABI_VERSION 9\b", header)
     assert re.search(r"#define MKB_TOPK_MAX_K 1024\b", header) and re.search(r"#define MKB_TOPK_KEEP_TARGET 1\b", header)
-    assert _hip.ABI_VERSION == 8 and (_hip.TOPK_MAX_K, _hip.TOPK_KEEP_TARGET) == (1024, 1)
+    assert _hip.ABI_VERSION == 9 and (_hip.TOPK_MAX_K, _hip.TOPK_KEEP_TARGET) == (1024, 1)
     decl = re.search(r"int64_t mkb_topk_workspace_bytes\(([^)]*)\);", header)
     assert decl and [a.split()[-1].lstrip("*") for a in decl.group(1).split(",")] == ["tb", "B", "k"]
     decl = re.search(r"\bint mkb_topk\(([^)]*)\);", header)
@@ -30,7 +30,7 @@ def test_topk_symbols_and_abi():
                                                       c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p])
     lib = ctypes.CDLL(str(ROOT / "mkb_amd" / "libmkb_hip.so"))
     assert hasattr(lib, "mkb_topk") and hasattr(lib, "mkb_topk_workspace_bytes")
-    assert _hip.lib().mkb_abi_version() == 8
+    assert _hip.lib().mkb_abi_version() == 9
 
 
 def _fake_tables():

@@ -28,7 +28,7 @@ def test_nearest_declarations_match_the_binding():
     lib = ctypes.CDLL(str(ROOT / "mkb_amd" / "libmkb_hip.so"))
     for name in ("mkb_topk_nearest", "mkb_topk_nearest_dists", "mkb_topk_nearest_workspace_bytes"):
         assert hasattr(lib, name)
-    assert _hip.ABI_VERSION == 8
+    assert _hip.ABI_VERSION == 9
 
 
 def test_nearest_rejects_bad_arguments_before_any_launch():

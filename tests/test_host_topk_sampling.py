@@ -31,7 +31,7 @@ def test_masked_and_block_declarations_match_the_binding():
                                                             c.c_void_p, c.c_void_p])
     lib = ctypes.CDLL(str(ROOT / "mkb_amd" / "libmkb_hip.so"))
     assert hasattr(lib, "mkb_topk_masked") and hasattr(lib, "mkb_topk_block")
-    assert _hip.ABI_VERSION == 8
+    assert _hip.ABI_VERSION == 9
 
 
 def test_masked_and_block_reject_bad_arguments_before_any_launch():
