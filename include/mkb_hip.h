@@ -601,7 +601,7 @@ int mkb_reg_rows(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *s
  *   over sample [B, 3] in MKB_MODE_TAIL (s_i(e) = score of (h_i, r_i, e), target t_i) or MKB_MODE_HEAD ((e, r_i, t_i), target h_i);
  *   weight [B] or null (all ones), W = sum of weight (B when null), or weight_sum[0] when given (the rows are a shard, as for
  *   mkb_ns_loss).  No filtering of other known answers and no label smoothing in these calls: the "filtered 1vsAll" section
- *   below has both.  Only the two models whose all-entity block is one matrix product: TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED (their sampled softmax is mkb_ns_loss with MKB_LOSS_SOFTMAX).
+ *   below has both.  Only the two models whose all-entity block is one matrix product: TransE, RotatE and pRotatE -> MKB_ERR_UNSUPPORTED (their sampled softmax is mkb_ns_loss with MKB_LOSS_SOFTMAX, their all-entity losses the mkb_dist_all_* calls below).
  *   mkb_all_score_fwd: scores [B, n_entity] out = the all-entity block of the evaluation, the bits mkb_rank_scores hands out (the
  *   same routes, chosen in the same place).
  *   mkb_all_softmax: one pass per row over a block S [B, ld] of which the first N columns count, target[i * target_stride] the
@@ -687,6 +687,43 @@ int mkb_all_softmax_filtered(float *S, int64_t B, int64_t N, int64_t ld, const i
 int mkb_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
                           const int64_t *keys, int64_t n_keys, float T, float smoothing, const float *weight_sum, float *loss,
                           float *pos, void *ws, int64_t ws_bytes, void *stream);
+
+/* ---- all-entity losses, distance models: 1vsAll, filtered 1vsAll and KvsAll for TransE, RotatE and pRotatE ---------------------
+ * The three all-entity losses above for the models whose score is gamma - (modulus) sum_k f(q_i[k], E[e][k]) and whose
+ * all-entity block is therefore no matrix product; mkb_amd/csrc/score_all_dist.hip.  New symbols under ABI 9: the version is not
+ * bumped (symbols are only added), and the mkb_all_* calls keep refusing these models.  Loss formulas, key arrays, weight, W and
+ * weight_sum: those of the three sections above, by the call named beside each.
+ *   mkb_dist_all_score_fwd: scores [B, n_entity] out = the all-entity block of the evaluation, finished scores, the bits
+ *   mkb_rank_scores hands out (the same routes, chosen in the same place).
+ *   mkb_dist_all_score_bwd: accumulates d loss / d tables given dscore [B, ld] (columns past n_entity are not read) into gr->g_ent,
+ *   gr->g_rel and, for pRotatE, gr->g_modulus[0] (null: not wanted); never zeroed, rows_clear is not used.  Two passes that recompute
+ *   the pair terms: dQ [B, De] = sum_e dscore_ie ds_i(e)/dq (a workgroup owns 16 query rows x 256 units and walks the entities; with
+ *   few row tiles the entities are split into up to 8 slices whose partials are added left to right) and dE [n_entity, De] +=
+ *   sum_i dscore_ie ds_i(e)/dx (a workgroup owns 16 entity rows x 256 units and walks the batch in order); the modulus gradient is
+ *   summed from one partial per workgroup in fixed order; dQ is chained into the query's entity row and relation row with one
+ *   writer per distinct row, as in mkb_all_score_bwd.  The derivatives at the edges are those of every other backward here: the
+ *   sign of an exactly zero TransE difference is 0, a RotatE pair that coincides gets a gradient of exactly 0.  No float atomics:
+ *   two runs give the same bits in every output.  Tables at any alignment, any B >= 1, any n_entity >= 1, entity_dim <= 4096.
+ *   mkb_dist_all_step == mkb_all_step, mkb_dist_all_filtered_step == mkb_all_filtered_step, mkb_dist_all_kvs_step ==
+ *   mkb_all_kvs_step: arguments, their checks and the order of the checks are those calls'; forward, the loss kernel of that call
+ *   on the finished block, the backward above.  pos [B] out.
+ *   ws: mkb_dist_all_workspace_bytes(tb, B) bytes (the same for the five calls), 256-byte aligned, caller-owned; nothing is
+ *   allocated in a call.  What the mkb_all_* calls answer with MKB_ERR_INVALID, these do, before any launch.  ComplEx and DistMult
+ *   -> MKB_ERR_UNSUPPORTED (the message names the mkb_all_* calls), and the workspace function returns 0 for them as for B <= 0,
+ *   null tables or a B that the calls refuse. */
+int64_t mkb_dist_all_workspace_bytes(const mkb_tables_t *tb, int64_t B);
+int mkb_dist_all_score_fwd(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, float *scores, void *ws, int64_t ws_bytes,
+                           void *stream);
+int mkb_dist_all_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode,
+                           const float *dscore, int64_t ld, void *ws, int64_t ws_bytes, void *stream);
+int mkb_dist_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
+                      float temperature, const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
+int mkb_dist_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
+                               int mode, const int64_t *keys, int64_t n_keys, float T, float smoothing, const float *weight_sum,
+                               float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
+int mkb_dist_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, int mode,
+                          const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities, const float *weight_sum,
+                          float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
 
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream

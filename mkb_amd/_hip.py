@@ -192,6 +192,10 @@ _SIGNATURES = {
     "mkb_all_filtered_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_float,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
+# the all-entity losses of the distance models: argument for argument the mkb_all_* call each one mirrors
+_SIGNATURES.update({"mkb_dist_all_" + new: _SIGNATURES["mkb_all_" + old] for new, old in (
+    ("workspace_bytes", "step_workspace_bytes"), ("score_fwd", "score_fwd"), ("score_bwd", "score_bwd"), ("step", "step"),
+    ("filtered_step", "filtered_step"), ("kvs_step", "kvs_step"))})
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

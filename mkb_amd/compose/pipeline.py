@@ -13,7 +13,7 @@ README, or ``mkb_amd.optim.Adam``).
 import torch
 
 from ..datasets.device import DeviceBatches
-from ..fused import FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep, pooled_supported
+from ..fused import DISTANCE_MODELS, DistanceAllStep, FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep, pooled_supported
 from ..losses import Adversarial, CrossEntropy, KvsAll, MarginRanking, OneVsAll, PairwiseLogistic
 from ..models.base import BaseModel
 from ..sampling import NegativeSampling
@@ -102,7 +102,11 @@ class Pipeline:
         when model, sampler and loss are the mkb_amd ones on a ROCm device, else None.  ``losses.OneVsAll`` always takes
         ``OneVsAllStep`` and ``losses.KvsAll`` always ``KvsAllStep``: they have no explicit sequence (no negatives are drawn:
         ``sampling`` is not used).  A ``KvsAll`` without triples of its own is labelled by the training triples of ``dataset``
-        (``DeviceBatches`` hands out the wrapped dataset's); a ``OneVsAll(filter_known=True)`` without triples filters by them."""
+        (``DeviceBatches`` hands out the wrapped dataset's); a ``OneVsAll(filter_known=True)`` without triples filters by them.
+        With TransE, RotatE or pRotatE either loss takes ``DistanceAllStep``, with the same defaults."""
+        if isinstance(loss, (OneVsAll, KvsAll)) and getattr(model, "name", None) in DISTANCE_MODELS:
+            self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
+            return DistanceAllStep(model, loss, regularizer=self.regularizer, true_triples=dataset.train)
         if isinstance(loss, OneVsAll):
             self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
             triples = (dataset.train if loss.true_triples is None else loss.true_triples) if loss.filter_known else None

@@ -23,7 +23,10 @@
 // Written once for both: the step (all_step: carve, forward, the loss on the block, backward) and the launch of "a loss
 // kernel on the block" (all_loss_launch), which runs it inside the row-loss protocol of loss_math.h (RowLoss: W, the scratch, the
 // launch in front of many rows, the finish).
+// The loss launches and the query chain are shared with score_all_dist.hip, the same three losses for TransE / RotatE / pRotatE
+// (all_chain.h declares the former and holds the latter).
 #include "common.h"
+#include "all_chain.h"  // what is shared with score_all_dist.hip: the loss launches' declarations, the query chain
 #include "loss_math.h"
 #include "pair_sort.h"
 #include "rank_all.h"
@@ -100,7 +103,7 @@ static void all_loss_launch(const float *weight, const float *weight_sum, int64_
     L.finish(B, 1.f, loss, st);
 }
 
-static void all_softmax_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride, const float *weight,
+void all_softmax_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride, const float *weight,
                                const float *weight_sum, float T, float *loss, float *pos, float *scratch, hipStream_t st) {
     all_loss_launch(weight, weight_sum, B, loss, scratch, st, [&](const RowLoss &L) {
         const size_t lds = N <= kAllStageCols ? (size_t)N * sizeof(float) : 0;
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(256) void all_bce_kernel(float *__restrict__ S, int
     }
 }
 
-static void all_bce_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, bool head, int64_t R, const int64_t *keys,
+void all_bce_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, bool head, int64_t R, const int64_t *keys,
                            int64_t n_keys, const float *weight, const float *weight_sum, float eps, bool sum_over_entities, float *loss,
                            float *pos, float *scratch, hipStream_t st) {
     all_loss_launch(weight, weight_sum, B, loss, scratch, st, [&](const RowLoss &L) {
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(256) void all_softmax_filtered_kernel(float *__rest
     }
 }
 
-static void all_softmax_filtered_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride,
+void all_softmax_filtered_launch(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t tstride,
                                         const int64_t *sample, bool head, int64_t R, const int64_t *keys, int64_t n_keys,
                                         const float *weight, const float *weight_sum, float T, float eps, float *loss, float *pos,
                                         float *scratch, hipStream_t st) {
@@ -277,68 +280,6 @@ static void all_softmax_filtered_launch(float *S, int64_t B, int64_t N, int64_t 
         hipLaunchKernelGGL(all_softmax_filtered_kernel, dim3((unsigned)B), dim3(256), lds, st, S, (int)B, N, ld, target, tstride, sample,
                            head ? 1 : 0, R, keys, n_keys, weight, L.scal_in, L.scal_out, 1.f / T, eps, pos, L.rowpart);
     });
-}
-
-// ---- query chain: dQ -> the query's entity row (h; t for head-batch) and relation row, one writer per distinct row
-struct ChainArgs {
-    const float *ent, *rel;  // (the table fields query_row reads)
-    int64_t De, Dr;
-    int d;
-    float kd;
-    const int64_t *sample;
-    const float *dQ;
-    float *g_ent, *g_rel;
-    const int *keys, *vals;  // the sorted occurrences: row keys (relations: n_entity + r) and occurrence indices (relations: B + i)
-    int n, B, n_entity;
-    float *stash;  // [B, De]: what the gradient rows of the batch's query entities held before the step, by sorted position
-};
-
-// The gradient row of a query's entity takes two terms, its row of the product dE and the chain's.  Adding them one after the other
-// onto what the row already holds would round twice; so the row's content is set aside and the row cleared here, the product adds
-// onto zero (exact), and the chain kernel writes stash + (product + chain): the finished result is added once, as for every
-// other row.  One workgroup per sorted position of the entity keys (they sort in front of the relation keys: positions 0 .. B - 1).
-__global__ __launch_bounds__(256) void all_stash_kernel(ChainArgs A) {
-    const int pos = blockIdx.x;
-    const int key = A.keys[pos];
-    if (pos > 0 && A.keys[pos - 1] == key) return;
-    float *g = A.g_ent + (int64_t)key * A.De, *x = A.stash + (int64_t)pos * A.De;
-    for (int64_t u = threadIdx.x; u < A.De; u += 256) {
-        x[u] = g[u];
-        g[u] = 0.f;
-    }
-}
-
-template <int MODEL, bool HEAD>
-__global__ __launch_bounds__(256) void all_chain_kernel(ChainArgs A) {
-    constexpr bool CQ = ModelTraits<MODEL>::cplx_query;
-    const int pos = blockIdx.x;
-    const int key = A.keys[pos];
-    if (pos > 0 && A.keys[pos - 1] == key) return;  // (uniform) only the position that opens a run of equal keys owns the row
-    const bool is_rel = key >= A.n_entity;
-    float *g = is_rel ? A.g_rel + (int64_t)(key - A.n_entity) * A.Dr : A.g_ent + (int64_t)key * A.De;
-    const bool has_im = CQ && (!is_rel || MODEL == MKB_COMPLEX);
-    const int U = CQ ? A.d : (int)A.De;
-    for (int u = threadIdx.x; u < U; u += 256) {
-        float a_re = 0.f, a_im = 0.f;
-        for (int j = pos; j < A.n && A.keys[j] == key; ++j) {  // the run in batch order (the sort is stable)
-            const int64_t i = A.vals[j] % A.B;
-            const QueryRow R = query_row<MODEL>(A, A.sample, i);
-            const float *dq = A.dQ + i * A.De;
-            const float dq0 = dq[u], dq1 = CQ ? dq[A.d + u] : 0.f;
-            Cplx de, dr;
-            query_unit_bwd<MODEL, HEAD>(R, u, dq0, dq1, de, dr);
-            a_re += is_rel ? dr.re : de.re;
-            a_im += is_rel ? dr.im : de.im;
-        }
-        if (is_rel) {
-            g[u] += a_re;
-            if (has_im) g[A.d + u] += a_im;
-        } else {  // (see all_stash_kernel)
-            const float *x = A.stash + (int64_t)pos * A.De;
-            g[u] = x[u] + (g[u] + a_re);
-            if (has_im) g[A.d + u] = x[A.d + u] + (g[A.d + u] + a_im);
-        }
-    }
 }
 
 // ---- workspace: Q [B, De], the score block [B, Npad] (which becomes dS), the id list [Npad], dQ [B, De], the partial buffer of the
@@ -354,8 +295,6 @@ struct AllWs {
     void *sort;
     float *scratch;
 };
-
-static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // The shapes one int32 sort, one int32 GEMM and the softmax's B * ld limit cover (B >= 1 is the caller's).  false: outside them, or
 // the sort's size query failed (*rc < 0)
@@ -395,16 +334,8 @@ static int all_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t 
     const int64_t N = tb->n_entity, De = tb->entity_dim;
     const GemmSwitches sw = gemm_switches_from_env();
     const bool al = (((uintptr_t)dS | (uintptr_t)tb->ent | (uintptr_t)gr->g_ent) & 15) == 0;  // (Q, dQ: the 256-byte aligned workspace)
-    PairKeySegs segs{};
-    segs.seg[0] = PairKeySeg{sample + (HEAD ? 2 : 0), 3, B, N, 0};    // the query's entity
-    segs.seg[1] = PairKeySeg{sample + 1, 3, B, tb->n_relation, (int)N};  // its relation
-    segs.n_segs = 2;
-    ChainArgs A{};
-    if (int rc = pair_sort_launch_segs(segs, w.sort, P.sort, st, &A.keys, &A.vals)) return rc;
-    A.ent = tb->ent; A.rel = tb->rel; A.De = De; A.Dr = tb->relation_dim; A.d = tb->hidden_dim; A.kd = tb->phase_div;
-    A.sample = sample; A.dQ = w.dQ; A.g_ent = gr->g_ent; A.g_rel = gr->g_rel;
-    A.n = (int)(2 * B); A.B = (int)B; A.n_entity = (int)N; A.stash = w.stash;
-    hipLaunchKernelGGL(all_stash_kernel, dim3((unsigned)B), dim3(256), 0, st, A);
+    ChainArgs A;
+    if (int rc = all_chain_open<HEAD>(tb, gr, sample, B, w.dQ, w.stash, w.sort, P.sort, st, A)) return rc;
     {
         const GemmPlan plan = plan_gemm(all_dq_shape(B, N, De, ld, gathered, al), all_dq_limits(), sw);
         GemmArgs G = gemm_args(plan);
@@ -428,7 +359,8 @@ static int dispatch_dot_model(int model, bool head, F &&f) {
     if (model != MKB_COMPLEX && model != MKB_DISTMULT)
         return set_error(MKB_ERR_UNSUPPORTED,
                          "1vsAll covers ComplEx and DistMult, whose all-entity block is one matrix product; for TransE, RotatE and "
-                         "pRotatE use the sampled softmax (losses.CrossEntropy)");
+                         "pRotatE use the sampled softmax (losses.CrossEntropy), or the all-entity calls of the distance models, "
+                         "mkb_dist_all_* (fused.DistanceAllStep)");
     return dispatch_model_side(model, head, [&](auto m, auto h) {  // (no kernels are instantiated for the models refused above)
         if constexpr (decltype(m)::value == MKB_COMPLEX || decltype(m)::value == MKB_DISTMULT) return f(m, h);
         else return (int)MKB_ERR_UNSUPPORTED;
@@ -452,7 +384,7 @@ static int all_check(const mkb_tables_t *tb, const int64_t *sample, int64_t B, i
     return MKB_OK;
 }
 
-static int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const void *target, int64_t tstride, float T, const void *loss,
+int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const void *target, int64_t tstride, float T, const void *loss,
                          const void *pos, const void *scratch) {
     MKB_REQUIRE(S && target && loss && pos && scratch, "null pointer");
     MKB_REQUIRE(T - T == 0.f && T > 0.f, "the softmax temperature must be finite and > 0");
@@ -464,7 +396,7 @@ static int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const 
 
 // what the entry points that read the key arrays (KvsAll, filtered 1vsAll: `what`) check of their label arguments (N, R: the table
 // sizes the keys were built for)
-static int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n_keys, float eps, const char *what = "KvsAll") {
+int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n_keys, float eps, const char *what) {
     MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "%s needs head-batch or tail-batch", what);
     MKB_REQUIRE(n_keys >= 0 && (keys || n_keys == 0), "keys may be null only with n_keys == 0, and n_keys must be >= 0");
     MKB_REQUIRE(eps - eps == 0.f && eps >= 0.f && eps < 1.f, "the label smoothing must be finite and in [0, 1)");

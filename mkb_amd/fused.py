@@ -14,15 +14,20 @@
 ``KvsAllStep``       -- the KvsAll ("1-N") step of the same two models (``losses.KvsAll``): the same products around the multi-label
                         binary cross entropy with label smoothing (``mkb_all_kvs_step``).
 ``score_all``        -- the ``[B, n_entity]`` block behind ``model.score_all``, differentiable (``mkb_all_score_fwd`` / ``_bwd``).
+``DistanceAllStep``  -- the 1vsAll and KvsAll steps of TransE / RotatE / pRotatE, whose all-entity block is no product: the same loss
+                        kernels between the evaluation's forward block and a backward that recomputes the pair terms
+                        (``mkb_dist_all_step`` / ``_filtered_step`` / ``_kvs_step``).
+``distance_score_all`` -- their differentiable ``[B, n_entity]`` block (``mkb_dist_all_score_fwd`` / ``_bwd``).
 """
 import torch
 
 from . import _gradshare, _hip, _links
-from .losses import kvs_all, ns_losses
+from .losses import kvs_all, ns_losses, one_vs_all
 from .sampling.negative_sampling import PoolInfo
 from .utils.true_keys import true_keys
 
-__all__ = ["FusedTrainStep", "PooledLossStep", "OneVsAllStep", "KvsAllStep", "pooled_forward", "pooled_supported", "score_all"]
+__all__ = ["FusedTrainStep", "PooledLossStep", "OneVsAllStep", "KvsAllStep", "DistanceAllStep", "pooled_forward", "pooled_supported", "score_all",
+           "distance_score_all"]
 
 _workspaces = {}
 
@@ -317,15 +322,22 @@ def score_all(model, sample, mode):
 
 
 class _AllEntityStep:
-    """What the steps over the whole entity row share (``OneVsAllStep``, ``KvsAllStep``): the argument checks, the optimizer
+    """What the steps over the whole entity row share (``OneVsAllStep``, ``KvsAllStep``, ``DistanceAllStep``): the argument checks, the optimizer
     protocol of a step that writes EVERY entity row, the id check, the outputs, the workspace and the regulariser hook.  A subclass
     launches its one library call in ``_launch``."""
 
+    models = ONE_VS_ALL_MODELS  # the models the subclass's library call takes
+    workspace = staticmethod(_all_workspace)
+
     def __init__(self, model, regularizer=None):
-        if model.name not in ONE_VS_ALL_MODELS:
-            raise NotImplementedError(f"{type(self).__name__} covers {' and '.join(ONE_VS_ALL_MODELS)}, whose all-entity block is one "
-                                      f"matrix product, not {model.name}: train it with the sampled softmax, losses.CrossEntropy")
+        if model.name not in self.models:
+            raise NotImplementedError(self._refusal(model))
         self.model, self.regularizer, self.regularization = model, regularizer, None
+
+    def _refusal(self, model):
+        return (f"{type(self).__name__} covers {' and '.join(ONE_VS_ALL_MODELS)}, whose all-entity block is one "
+                f"matrix product, not {model.name}: train it with the sampled softmax, losses.CrossEntropy, or over all "
+                f"entities with fused.DistanceAllStep")
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
         """The other steps' entry point (``compose.Pipeline`` calls it): nothing is drawn from ``sampler``."""
@@ -350,7 +362,7 @@ class _AllEntityStep:
         m._launch_id_check(sample, None)
         pos = torch.empty((B, 1), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ws = _all_workspace(m, B)
+        ws = self.workspace(m, B)
         gr = grad_buffers(m)
         with _hip.on_device(dev):
             self._launch(m._tables(), gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws)
@@ -418,3 +430,119 @@ class KvsAllStep(_AllEntityStep):
                                                self.label_smoothing, int(self.reduction == "sum"), _hip.ptr(weight_sum),
                                                _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
                    "mkb_all_kvs_step")
+
+
+# ------------------------------------------------------------------------------- all-entity losses (TransE / RotatE / pRotatE)
+DISTANCE_MODELS = ("TransE", "RotatE", "pRotatE")  # the models whose all-entity block is a sum of distances
+
+
+def _dist_workspace(model, B):
+    """Device scratch of the five ``mkb_dist_all_*`` calls that take tables, cached like ``_workspace``."""
+    dev = model.entity_embedding.device
+    key = (dev, _hip.stream_ptr(dev).value, "dist_all", model.name, model.entity_dim, model.n_entity, model.n_relation, B)
+    return cached_workspace(key, dev, lambda: _hip.lib().mkb_dist_all_workspace_bytes(model._tables(), B))
+
+
+def _side_keys(triples, model, device, mode_id):
+    return true_keys(triples, device, model.n_entity, model.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
+
+
+class DistanceAllStep(_AllEntityStep):
+    """``loss = step(sample, weight, mode)``: the all-entity step of TransE / RotatE / pRotatE.  ``loss`` is a ``losses.OneVsAll``
+    (the softmax over the whole row at its temperature; with ``filter_known`` or ``label_smoothing`` the filtered form) or a
+    ``losses.KvsAll`` (the multi-label binary cross entropy) -- the markers hold every setting, the formulas are theirs.  Every
+    entity is scored for each ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``); fills ``param.grad`` (dense,
+    accumulated; pRotatE: the modulus too) and returns the loss as a 0-dim device tensor.  ``positive_score`` [B, 1] of the last
+    call stays available.  One library call (``mkb_dist_all_step`` / ``mkb_dist_all_filtered_step`` / ``mkb_dist_all_kvs_step``), no
+    autograd, no negatives.  The score is no product here, so the backward recomputes the pair terms in two passes (DESIGN.md has
+    them); arguments of the call, optimizers and ``regularizer``: as for ``OneVsAllStep``.
+
+    ``true_triples``: the known triples of a ``KvsAll`` marker, or of a ``OneVsAll(filter_known=True)``, that holds none."""
+
+    models = DISTANCE_MODELS
+    workspace = staticmethod(_dist_workspace)
+
+    def __init__(self, model, loss, regularizer=None, true_triples=None):
+        if not isinstance(loss, (one_vs_all.OneVsAll, kvs_all.KvsAll)):
+            raise TypeError("DistanceAllStep takes losses.OneVsAll or losses.KvsAll")
+        super().__init__(model, regularizer)
+        self.loss = loss
+        self.true_triples = loss.true_triples if loss.true_triples is not None else true_triples
+        self.kvs = isinstance(loss, kvs_all.KvsAll)
+        if self.true_triples is None and (self.kvs or loss.filter_known):
+            raise ValueError("DistanceAllStep needs true_triples: the known triples the loss labels or filters by")
+        self.filtered = not self.kvs and (loss.filter_known or loss.label_smoothing != 0.0)
+
+    def _refusal(self, model):
+        return (f"DistanceAllStep covers {', '.join(DISTANCE_MODELS)}, whose all-entity block is a sum of distances, not {model.name}: "
+                f"its block is one matrix product, use fused.OneVsAllStep / fused.KvsAllStep")
+
+    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
+        lib, L = _hip.lib(), self.loss
+        tail = (_hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(), _hip.stream_ptr())
+        head = (tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id)
+        if self.kvs:
+            keys = _side_keys(self.true_triples, self.model, sample.device, mode_id)
+            _hip.check(lib.mkb_dist_all_kvs_step(*head, _hip.ptr(keys), keys.numel(), L.label_smoothing, int(L.reduction == "sum"), *tail),
+                       "mkb_dist_all_kvs_step")
+        elif self.filtered:
+            keys = _side_keys(self.true_triples, self.model, sample.device, mode_id) if L.filter_known else None
+            _hip.check(lib.mkb_dist_all_filtered_step(*head, _hip.ptr(keys), 0 if keys is None else keys.numel(), L.temperature,
+                                                      L.label_smoothing, *tail), "mkb_dist_all_filtered_step")
+        else:
+            _hip.check(lib.mkb_dist_all_step(*head, L.temperature, *tail), "mkb_dist_all_step")
+
+
+class _DistanceScoreAllFn(torch.autograd.Function):
+    """``_ScoreAllFn`` for the distance models; backward = dense d loss / d tables and pRotatE's d loss / d modulus."""
+
+    @staticmethod
+    def forward(ctx, ent, rel, modulus, model, sample, mode):
+        B = sample.shape[0]
+        scores = torch.empty((B, model.n_entity), dtype=torch.float32, device=ent.device)
+        ws = _dist_workspace(model, B)
+        with _hip.on_device(ent.device):
+            _hip.check(_hip.lib().mkb_dist_all_score_fwd(model._tables(ent, rel, modulus), _hip.ptr(sample), B, mode, _hip.ptr(scores),
+                                                         _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), "mkb_dist_all_score_fwd")
+        ctx.model, ctx.mode = model, mode
+        ctx.save_for_backward(ent, rel, modulus, sample)
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscore):
+        ent, rel, modulus, sample = ctx.saved_tensors
+        model, B = ctx.model, sample.shape[0]
+        dscore = _hip.contiguous(dscore, torch.float32)
+        g_ent, g_rel = torch.zeros_like(ent), torch.zeros_like(rel)  # every entity row is written: dense, through autograd
+        g_mod = torch.zeros_like(modulus) if model.name == "pRotatE" else None
+        ws = _dist_workspace(model, B)
+        with _hip.on_device(ent.device):
+            gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
+            _hip.check(_hip.lib().mkb_dist_all_score_bwd(model._tables(ent, rel, modulus), gr, _hip.ptr(sample), B, ctx.mode,
+                                                         _hip.ptr(dscore), dscore.shape[1], _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
+                       "mkb_dist_all_score_bwd")
+        return g_ent, g_rel, g_mod, None, None, None
+
+
+def distance_score_all(model, sample, mode):
+    """float32 ``[B, n_entity]``: what ``model.score_all(sample, mode)`` is for ComplEx / DistMult, for TransE / RotatE / pRotatE --
+    ``out[i, e]`` is the score of ``sample[i]`` with its tail (``'tail-batch'``; its head for ``'head-batch'``) replaced by entity
+    ``e``, the bits ``Evaluation.ranks(..., with_scores=True)`` hands out, differentiable with respect to both tables and pRotatE's
+    modulus: ``losses.OneVsAll()(fused.distance_score_all(m, sample, mode), target, weight)`` trains the explicit way."""
+    from .models import base
+
+    if model.name not in DISTANCE_MODELS:
+        raise NotImplementedError(f"distance_score_all covers {', '.join(DISTANCE_MODELS)}, not {model.name}: use model.score_all")
+    mode_id = _hip.side_id(mode, "all-entity scores")
+    _hip.require_device(model.entity_embedding, sample)
+    if sample.dim() != 2 or sample.shape[1] != 3 or sample.shape[0] < 1:
+        raise ValueError("sample must be [B, 3] with B >= 1")
+    sample = _hip.contiguous(sample, torch.int64)
+    if base.VALIDATE_IDS:
+        model._launch_id_check(sample, None)
+    if _links.owner(model.entity_embedding) is not None or _links.owner(model.relation_embedding) is not None:
+        model._make_current(sample, None)  # every entity row is read
+    modulus = getattr(model, "modulus", None)
+    if modulus is None:
+        modulus = model.gamma
+    return _DistanceScoreAllFn.apply(model.entity_embedding, model.relation_embedding, modulus, model, sample, mode_id)

@@ -19,8 +19,8 @@ With ``reduction="mean"``, ``label_smoothing=0`` and no weights the value is the
 mean over all B N elements).
 
 The class is also the marker ``compose.Pipeline.learn`` reads: with this loss every batch goes through ``fused.KvsAllStep`` (no
-negatives are drawn; with ``true_triples=None`` the labels are the training triples of the dataset being iterated).  ComplEx and
-DistMult only.
+negatives are drawn; with ``true_triples=None`` the labels are the training triples of the dataset being iterated); with TransE,
+RotatE or pRotatE through ``fused.DistanceAllStep``.
 """
 import math
 

@@ -26,8 +26,8 @@ and ``mode`` (the row's query) and ``true_triples``; ``n_relation``: as for ``Kv
 
 The class is also the marker ``compose.Pipeline.learn`` reads: with this loss every batch goes through ``fused.OneVsAllStep`` (no
 negatives are drawn; the dataset's alternating head-batch / tail-batch gives both sides; with ``filter_known=True`` and
-``true_triples=None`` the known answers are the training triples of the dataset being iterated).  ComplEx and DistMult only -- for
-the distance models use the sampled ``CrossEntropy``.
+``true_triples=None`` the known answers are the training triples of the dataset being iterated); with TransE, RotatE or pRotatE
+through ``fused.DistanceAllStep``, whose explicit form is ``loss(fused.distance_score_all(model, sample, mode), target, weight)``.
 """
 import torch
 

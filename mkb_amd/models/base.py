@@ -352,7 +352,8 @@ class BaseModel(Base):
 
         if self.name not in ONE_VS_ALL_MODELS:
             raise NotImplementedError(f"score_all is differentiable for {' and '.join(ONE_VS_ALL_MODELS)} only, not {self.name}: "
-                                      "Evaluation.ranks(..., with_scores=True) gives the same block without a backward")
+                                      "Evaluation.ranks(..., with_scores=True) gives the same block without a backward, "
+                                      "fused.distance_score_all the differentiable block of TransE, RotatE and pRotatE")
         if _hip.mode_id(mode) == _hip.MODE_DEFAULT:
             raise ValueError(f"score_all scores one side of a triple: mode must be 'head-batch' or 'tail-batch', not {mode!r}")
         _hip.require_device(self.entity_embedding, sample)

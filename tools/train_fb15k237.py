@@ -10,7 +10,8 @@ FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamm
 PooledLossStep, or onevsall (OneVsAll(--temperature) through OneVsAllStep: ComplEx / DistMult, every entity scored for each row, no
 negatives drawn; --size is then not used; --label-smoothing, and --filter-known to take a row's other known answers in the
 training triples out of its softmax), or kvsall (KvsAllStep: the same two models, binary cross entropy against the multi-hot
-labels of every known answer in the training triples, --label-smoothing, --reduction mean|sum over the entities).  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
+labels of every known answer in the training triples, --label-smoothing, --reduction mean|sum over the entities); with --model
+TransE / RotatE / pRotatE both go through DistanceAllStep, same flags.  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
 handed to the step.  --optimizer: adam (the default: row-lazy optim.Adam) or adagrad (row-sparse optim.Adagrad; the literature's
 ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.
 
@@ -25,7 +26,7 @@ import torch
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from mkb_amd import datasets, evaluation, losses, models, optim, regularizers, sampling  # noqa: E402
-from mkb_amd.fused import FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep  # noqa: E402
+from mkb_amd.fused import DISTANCE_MODELS, DistanceAllStep, FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep  # noqa: E402
 
 
 def main():
@@ -66,6 +67,10 @@ def main():
     reg = {"none": lambda: None, "l2": lambda: regularizers.L2(args.reg_weight), "n3": lambda: regularizers.N3(args.reg_weight)}[args.reg]()
     if args.loss == "adversarial":
         step = FusedTrainStep(model, args.alpha, regularizer=reg)
+    elif args.loss in ("onevsall", "kvsall") and args.model in DISTANCE_MODELS:  # the same flags, the distance models' step
+        marker = (losses.OneVsAll(args.temperature, args.label_smoothing, args.filter_known) if args.loss == "onevsall"
+                  else losses.KvsAll(label_smoothing=args.label_smoothing, reduction=args.reduction))
+        step = DistanceAllStep(model, marker, regularizer=reg, true_triples=ds.train)
     elif args.loss == "onevsall":
         step = OneVsAllStep(model, temperature=args.temperature, regularizer=reg, label_smoothing=args.label_smoothing,
                             true_triples=ds.train if args.filter_known else None)
