@@ -158,6 +158,40 @@ int mkb_sampler_get_state(mkb_sampler_t *s, uint32_t *key624_host, int32_t *pos_
 int mkb_sampler_set_state(mkb_sampler_t *s, const uint32_t *key624_host, int32_t pos, void *stream);
 void mkb_sampler_destroy(mkb_sampler_t *s);
 
+/* ---- pool samplers: negatives from a candidate pool the caller made --------------------------------------------------
+ * No reference counterpart to match bit for bit (mkb/text/learn.py:366-400, in_batch_negative_triples, has the idea of one of
+ * the pool sources); mkb_amd/csrc/sampler_pool.hip.  New symbols under ABI 9: the version is not bumped.
+ * mkb_pool_filter: the per-row filter of a GIVEN pool [2K] of entity ids (duplicates allowed), with exact membership, and the
+ *   outputs of mkb_sampler_generate with the same meaning, so that whatever consumes those (mkb_pool_step and its relatives)
+ *   works unchanged.  sample [B, 3]; mode: MKB_MODE_HEAD (the row's target is its head, its query (?, r, t)) or MKB_MODE_TAIL.
+ *   keys [n_keys]: the sorted key array of that side (mkb_amd/utils/true_keys.py: (a * n_relation + r) * n_entity + x, a the
+ *   fixed entity, x the varying one), ascending and unique; null / 0 = no known answers.  A_i, the known answers of row i, is one
+ *   contiguous range of it; a query with no key at all is legal (no MKB_ERR_KEY here).  Pool position p is KEPT for row i iff
+ *   pool[p] is not in A_i and pool[p] is not the row's target (which is dropped even when the row's triple is not among the keys).
+ *   neg [B, K] = concat(f, f, ...)[:K], f = the kept pool entries in pool order; pos [B, K] int32, neg[i, j] == pool[pos[i, j]];
+ *   cnt [B, 2K] uint16, how often position p occurs among row i's K slots (every row sums to K); touched [2K + 2B] = the pool,
+ *   then the batch's heads, then its tails.  pos, cnt and touched may be null.
+ *   A row that keeps nothing: its neg / pos / cnt are zeroed and the call records MKB_ERR_EMPTY in status[0] and the smallest such
+ *   row in status[1].  status [2] int32 on the device, 8-byte aligned, is zeroed ONCE by the caller and read when it likes: it
+ *   accumulates over calls and no call waits for the device.
+ *   A pool id outside [0, n_entity) is nobody's known answer and is never used as an index.  No float arithmetic and one writer
+ *   per output element: two runs give the same bytes.
+ *   K outside [1, 1024], B < 1, n_entity or n_relation outside [1, 2^31 - 1], a null sample / pool / neg / status, a status that
+ *   is not 8-byte aligned, n_keys > 0 without keys, a mode other than head / tail -> MKB_ERR_INVALID before any launch.
+ * mkb_pool_draw_alias: pool [2K] drawn from a discrete distribution over [0, n_entity) by the alias method.  accept [n_entity]
+ *   int64 with values in [0, 2^32] and alias [n_entity] int32 are device tables (mkb_amd/sampling/pool_sampling.py builds them by
+ *   Vose's method).  Counter based, like the rocRAND draw of mkb_sampler_set_rng: entry p of draw number `draw` uses Philox4x32-10
+ *   at subsequence draw * 2K + p.  It chooses a column v uniform on [0, n_entity) by masked rejection (one 32-bit word per trial;
+ *   n_entity = 1 consumes none), takes one more word u, and is v if (uint64)u < accept[v], else alias[v]: probability 1 and
+ *   probability 0 are both exact.  words [2K, 2] uint32 or null: the accepted column word (0 when n_entity = 1) and u of every
+ *   entry, for a host that wants to redo the integer arithmetic.
+ *   A null accept / alias / pool, K outside [1, 1024], n_entity outside [1, 2^31 - 1] -> MKB_ERR_INVALID before any launch. */
+int mkb_pool_filter(const int64_t *sample, int64_t B, int mode, int64_t n_entity, int64_t n_relation, const int64_t *pool, int64_t K,
+                    const int64_t *keys, int64_t n_keys, int64_t *neg, int32_t *pos, uint16_t *cnt, int64_t *touched,
+                    int32_t *status, void *stream);
+int mkb_pool_draw_alias(const int64_t *accept, const int32_t *alias, int64_t n_entity, int64_t K, uint64_t seed, uint64_t draw,
+                        int64_t *pool, uint32_t *words, void *stream);
+
 /* ---- pooled training step ----------------------------------------------------------------------------
  * == compose/pipeline.py:211-236 for one batch whose negatives come from ONE shared pool
  * (negative_sampling.py:166): positive forward (mode None), negative forward (mode), Adversarial,

@@ -95,6 +95,9 @@ _SIGNATURES = {
     "mkb_sampler_get_state": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
     "mkb_sampler_set_state": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "mkb_sampler_destroy": (None, [c_void_p]),
+    "mkb_pool_filter": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mkb_pool_draw_alias": (c_int, [c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "mkb_pool_supported": (c_int, [POINTER(Tables), c_int64, c_int64]),
     "mkb_pool_step_workspace_bytes": (c_int64, [POINTER(Tables), c_int64, c_int64]),
     "mkb_pool_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,

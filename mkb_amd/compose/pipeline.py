@@ -16,7 +16,7 @@ from ..datasets.device import DeviceBatches
 from ..fused import DISTANCE_MODELS, DistanceAllStep, FusedTrainStep, KvsAllStep, OneVsAllStep, PooledLossStep, pooled_supported
 from ..losses import Adversarial, CrossEntropy, KvsAll, MarginRanking, OneVsAll, PairwiseLogistic
 from ..models.base import BaseModel
-from ..sampling import NegativeSampling
+from ..sampling import NegativeSampling, PoolNegativeSampling
 from ..utils import Bar, RollingMean
 
 __all__ = ["Pipeline"]
@@ -116,12 +116,13 @@ class Pipeline:
             self._borrowed = []
             triples = dataset.train if loss.true_triples is None else loss.true_triples
             return KvsAllStep(model, triples, loss.label_smoothing, loss.reduction, regularizer=self.regularizer)
-        if not (self.fuse and isinstance(model, BaseModel) and isinstance(sampling, NegativeSampling)
+        if not (self.fuse and isinstance(model, BaseModel) and isinstance(sampling, (NegativeSampling, PoolNegativeSampling))
                 and type(loss) in (Adversarial,) + _POOLED_LOSSES and model.entity_embedding.is_cuda
                 and pooled_supported(model, dataset.batch_size, sampling.size)):
             return None
         self._borrowed = []  # optimizer settings this loop switches on and learn() switches back off before it returns
-        if getattr(optimizer, "lazy_rows", False) and getattr(optimizer, "draw_ahead", "x") is None:
+        # (only NegativeSampling's draw can ride another launch: a PoolNegativeSampling makes its pool itself)
+        if isinstance(sampling, NegativeSampling) and getattr(optimizer, "lazy_rows", False) and getattr(optimizer, "draw_ahead", "x") is None:
             optimizer.draw_ahead = sampling  # mkb_amd.optim.Adam: the next pool's draw rides the catch-up launch
             self._borrowed.append("draw_ahead")
         if getattr(optimizer, "lazy_rows", False) and getattr(optimizer, "defer_step", "x") is None:

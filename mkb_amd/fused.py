@@ -147,7 +147,10 @@ def sampled_step(step, sample, weight, sampler, mode, **kwargs):
     ent = step.model.entity_embedding
     lazy = _links.owner(ent)
     sample = _hip.contiguous(sample, torch.int64)
-    if lazy is not None and not getattr(lazy, "rows_always_current", False) and sampler.size <= 512 and sample.is_cuda:
+    # (a sampler without generate_with_catch_up -- sampling.PoolNegativeSampling -- launches on its own; step(...) below catches the
+    # row-lazy optimizer up on the rows the batch reads)
+    if (lazy is not None and not getattr(lazy, "rows_always_current", False) and sampler.size <= 512 and sample.is_cuda
+            and hasattr(sampler, "generate_with_catch_up")):
         neg = sampler.generate_with_catch_up(sample, mode, lazy, ent)
     else:
         neg = sampler.generate(sample=sample, mode=mode)

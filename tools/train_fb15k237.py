@@ -4,6 +4,7 @@ FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamm
     python tools/train_fb15k237.py [--epochs 200] [--lr 5e-5] [--eval-every 50] [--model RotatE]
                                    [--loss adversarial|margin|pairwise|softmax|onevsall|kvsall] [--reg none|l2|n3] [--reg-weight 1e-3]
                                    [--optimizer adam|adagrad] [--label-smoothing 0.1] [--filter-known]
+                                   [--sampler uniform|weighted|inbatch] [--sampler-power 0.75]
 
 --loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
 --alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
@@ -13,7 +14,10 @@ training triples out of its softmax), or kvsall (KvsAllStep: the same two models
 labels of every known answer in the training triples, --label-smoothing, --reduction mean|sum over the entities); with --model
 TransE / RotatE / pRotatE both go through DistanceAllStep, same flags.  --reg: an L2 / N3 penalty of --reg-weight on the rows of each batch's positive triples (regularizers.L2 / N3),
 handed to the step.  --optimizer: adam (the default: row-lazy optim.Adam) or adagrad (row-sparse optim.Adagrad; the literature's
-ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.
+ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.  --sampler: uniform (the default:
+sampling.NegativeSampling, the reference's negatives), weighted (sampling.WeightedNegativeSampling: pool entries drawn with probability
+proportional to the entity's degree in the training triples to the power --sampler-power) or inbatch
+(sampling.InBatchNegativeSampling: the pool is 2 * --size of the batch's own tails / heads).
 
 Uses the public mkb_amd API only (models / sampling / losses / compose.Pipeline-equivalent loop / evaluation) plus
 the device batch producer.  Prints one JSON line per evaluation."""
@@ -49,6 +53,8 @@ def main():
     ap.add_argument("--reg", default="none", choices=["none", "l2", "n3"])
     ap.add_argument("--reg-weight", type=float, default=1e-3, help="--reg l2 / n3")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "adagrad"], help="optim.Adam(lazy_rows=True) or optim.Adagrad at --lr")
+    ap.add_argument("--sampler", default="uniform", choices=["uniform", "weighted", "inbatch"])
+    ap.add_argument("--sampler-power", type=float, default=0.75, help="--sampler weighted: p_e proportional to degree_e ** power")
     ap.add_argument("--no-defer", action="store_true", help="apply the optimizer step at once (one more launch per step)")
     args = ap.parse_args()
 
@@ -57,12 +63,18 @@ def main():
     torch.manual_seed(42)
     model = getattr(models, args.model)(hidden_dim=args.hidden, entities=ds.entities, relations=ds.relations,
                                         gamma=args.gamma).cuda()
-    sampler = sampling.NegativeSampling(size=args.size, train_triples=ds.train, entities=ds.entities,
-                                        relations=ds.relations, seed=42)
-    if args.optimizer == "adagrad":  # row-sparse: nothing is deferred, --no-defer has nothing to switch off
-        opt = optim.Adagrad([p for p in model.parameters() if p.requires_grad], lr=args.lr, draw_ahead=sampler)
+    sampler_args = dict(size=args.size, train_triples=ds.train, entities=ds.entities, relations=ds.relations, seed=42)
+    if args.sampler == "weighted":
+        sampler = sampling.WeightedNegativeSampling(weights="degree", power=args.sampler_power, **sampler_args)
+    elif args.sampler == "inbatch":
+        sampler = sampling.InBatchNegativeSampling(**sampler_args)
     else:
-        opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=sampler,
+        sampler = sampling.NegativeSampling(**sampler_args)
+    ahead = sampler if args.sampler == "uniform" else None  # (only the uniform sampler's draw can ride the optimizer's launch)
+    if args.optimizer == "adagrad":  # row-sparse: nothing is deferred, --no-defer has nothing to switch off
+        opt = optim.Adagrad([p for p in model.parameters() if p.requires_grad], lr=args.lr, draw_ahead=ahead)
+    else:
+        opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=ahead,
                          defer_step=not args.no_defer)  # gradients are cleared through opt.zero_grad() only: the step may wait
     reg = {"none": lambda: None, "l2": lambda: regularizers.L2(args.reg_weight), "n3": lambda: regularizers.N3(args.reg_weight)}[args.reg]()
     if args.loss == "adversarial":
