@@ -738,13 +738,12 @@ int mkb_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const i
  *   writer per distinct row, as in mkb_all_score_bwd.  The derivatives at the edges are those of every other backward here: the
  *   sign of an exactly zero TransE difference is 0, a RotatE pair that coincides gets a gradient of exactly 0.  No float atomics:
  *   two runs give the same bits in every output.  Tables at any alignment, any B >= 1, any n_entity >= 1, entity_dim <= 4096.
- *   mkb_dist_all_step == mkb_all_step, mkb_dist_all_filtered_step == mkb_all_filtered_step, mkb_dist_all_kvs_step ==
- *   mkb_all_kvs_step: arguments, their checks and the order of the checks are those calls'; forward, the loss kernel of that call
- *   on the finished block, the backward above.  pos [B] out.
+ *   The two families share one protocol (mkb_amd/csrc/all_host.h holds it once): each of the six calls below is the mkb_all_* call
+ *   of its name (mkb_dist_all_workspace_bytes: mkb_all_step_workspace_bytes) in arguments, checks, their order and their answers,
+ *   with this family's models, workspace and backward; the steps run the loss kernel of their call on the finished block.
  *   ws: mkb_dist_all_workspace_bytes(tb, B) bytes (the same for the five calls), 256-byte aligned, caller-owned; nothing is
- *   allocated in a call.  What the mkb_all_* calls answer with MKB_ERR_INVALID, these do, before any launch.  ComplEx and DistMult
- *   -> MKB_ERR_UNSUPPORTED (the message names the mkb_all_* calls), and the workspace function returns 0 for them as for B <= 0,
- *   null tables or a B that the calls refuse. */
+ *   allocated in a call.  ComplEx and DistMult -> MKB_ERR_UNSUPPORTED (the message names the mkb_all_* calls), and the workspace
+ *   function returns 0 for them. */
 int64_t mkb_dist_all_workspace_bytes(const mkb_tables_t *tb, int64_t B);
 int mkb_dist_all_score_fwd(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, float *scores, void *ws, int64_t ws_bytes,
                            void *stream);

@@ -20,16 +20,15 @@
 // entropy with label smoothing, its labels read from the sorted key arrays of the filtered ranking.
 // Filtered 1vsAll (include/mkb_hip.h, "filtered 1vsAll") is the third loss kernel, all_softmax_filtered_kernel: the softmax with a
 // row's other known answers -- the same key range -- taken out of the row, and label smoothing over the columns that stay.
-// Written once for both: the step (all_step: carve, forward, the loss on the block, backward) and the launch of "a loss
-// kernel on the block" (all_loss_launch), which runs it inside the row-loss protocol of loss_math.h (RowLoss: W, the scratch, the
-// launch in front of many rows, the finish).
-// The loss launches and the query chain are shared with score_all_dist.hip, the same three losses for TransE / RotatE / pRotatE
-// (all_chain.h declares the former and holds the latter).
+// Written once for the three: the launch of "a loss kernel on the block" (all_loss_launch), which runs it inside the row-loss
+// protocol of loss_math.h (RowLoss: W, the scratch, the launch in front of many rows, the finish).
+// Everything on the host around the kernels -- workspace plan, entry checks, model dispatch, the step (carve, forward, the loss on
+// the block, backward) and the bodies of the calls that take tables -- is all_host.h's, shared with score_all_dist.hip, the same
+// three losses for TransE / RotatE / pRotatE; this file gives it DotFamily: the two models, the partial buffer's size and the
+// backward of the block.  all_chain.h declares the loss launches and holds the query chain.
 #include "common.h"
-#include "all_chain.h"  // what is shared with score_all_dist.hip: the loss launches' declarations, the query chain
+#include "all_host.h"  // (all_chain.h, pair_sort.h, rank_all.h)
 #include "loss_math.h"
-#include "pair_sort.h"
-#include "rank_all.h"
 #include "sampler_draw.h"  // lower_bound_dev
 #include "score_row.h"     // table_row
 
@@ -282,108 +281,6 @@ void all_softmax_filtered_launch(float *S, int64_t B, int64_t N, int64_t ld, con
     });
 }
 
-// ---- workspace: Q [B, De], the score block [B, Npad] (which becomes dS), the id list [Npad], dQ [B, De], the partial buffer of the
-// two backward products (used one after the other), the stash [B, De] of all_stash_kernel, the sort's storage, the loss scratch [1 + B]
-struct AllPlan {
-    PairSortPlan sort;
-    size_t s_off, ids_off, dq_off, stash_off, part_off, sort_off, scr_off, total;
-};
-struct AllWs {
-    float *Q, *S;
-    int64_t *ids;
-    float *dQ, *stash, *part;
-    void *sort;
-    float *scratch;
-};
-
-// The shapes one int32 sort, one int32 GEMM and the softmax's B * ld limit cover (B >= 1 is the caller's).  false: outside them, or
-// the sort's size query failed (*rc < 0)
-static bool all_plan(const mkb_tables_t *tb, int64_t B, AllPlan &P, int *rc) {
-    *rc = 0;
-    const int64_t N = tb->n_entity, Npad = all_npad(N), De = tb->entity_dim;
-    if (N <= 0 || tb->n_relation <= 0 || De <= 0 || Npad >= (1 << 30) || N + tb->n_relation > INT32_MAX || B > INT32_MAX / 2 ||
-        B * Npad > INT32_MAX || B * De > INT32_MAX)
-        return false;
-    if ((*rc = pair_sort_plan(N + tb->n_relation, 2 * B, P.sort))) return false;
-    const GemmSwitches sw{false, false, true};  // (part_bound does not depend on the switches)
-    const size_t part = std::max(plan_gemm(all_dq_shape(B, N, De, Npad, true, true), all_dq_limits(), sw).part_bound,
-                                 plan_gemm(all_de_shape(B, N, De, Npad, true), all_de_limits(N, De), sw).part_bound);
-    P.s_off = up256((size_t)B * De * 4);
-    P.ids_off = P.s_off + up256((size_t)B * Npad * 4);
-    P.dq_off = P.ids_off + up256((size_t)Npad * 8);
-    P.stash_off = P.dq_off + up256((size_t)B * De * 4);
-    P.part_off = P.stash_off + up256((size_t)B * De * 4);
-    P.sort_off = P.part_off + up256(part * 4);
-    P.scr_off = P.sort_off + P.sort.total;
-    P.total = P.scr_off + up256((size_t)(B + 1) * 4);
-    return true;
-}
-
-static AllWs all_carve(const AllPlan &P, void *ws) {
-    unsigned char *b = (unsigned char *)ws;
-    return AllWs{(float *)b, (float *)(b + P.s_off), (int64_t *)(b + P.ids_off), (float *)(b + P.dq_off), (float *)(b + P.stash_off),
-                 (float *)(b + P.part_off),
-                 b + P.sort_off, (float *)(b + P.scr_off)};
-}
-
-// dS [B, ld] -> g_ent, g_rel (accumulated).  w.Q holds the batch's queries.  gathered: dS is the forward's padded block, its pad
-// columns exactly 0, and w.ids the forward's id list.
-template <int MODEL, bool HEAD>
-static int all_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, const float *dS, int64_t ld,
-                   bool gathered, const AllPlan &P, const AllWs &w, hipStream_t st) {
-    const int64_t N = tb->n_entity, De = tb->entity_dim;
-    const GemmSwitches sw = gemm_switches_from_env();
-    const bool al = (((uintptr_t)dS | (uintptr_t)tb->ent | (uintptr_t)gr->g_ent) & 15) == 0;  // (Q, dQ: the 256-byte aligned workspace)
-    ChainArgs A;
-    if (int rc = all_chain_open<HEAD>(tb, gr, sample, B, w.dQ, w.stash, w.sort, P.sort, st, A)) return rc;
-    {
-        const GemmPlan plan = plan_gemm(all_dq_shape(B, N, De, ld, gathered, al), all_dq_limits(), sw);
-        GemmArgs G = gemm_args(plan);
-        G.A = dS; G.B = tb->ent; G.C = w.dQ; G.b_idx = gathered ? w.ids : nullptr;
-        if (int rc = launch_gemm<true, false, GEMM_STORE>(plan, G, st, w.part)) return rc;
-    }
-    {
-        const GemmPlan plan = plan_gemm(all_de_shape(B, N, De, ld, al), all_de_limits(N, De), sw);
-        GemmArgs G = gemm_args(plan);
-        G.A = dS; G.B = w.Q; G.C = gr->g_ent;
-        if (int rc = launch_gemm<false, false, GEMM_ACCUM>(plan, G, st, w.part)) return rc;
-    }
-    hipLaunchKernelGGL((all_chain_kernel<MODEL, HEAD>), dim3((unsigned)(2 * B)), dim3(256), 0, st, A);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-// dispatch_model_side (common.h) for the two models whose all-entity block is one product; the others are refused
-template <class F>
-static int dispatch_dot_model(int model, bool head, F &&f) {
-    if (model != MKB_COMPLEX && model != MKB_DISTMULT)
-        return set_error(MKB_ERR_UNSUPPORTED,
-                         "1vsAll covers ComplEx and DistMult, whose all-entity block is one matrix product; for TransE, RotatE and "
-                         "pRotatE use the sampled softmax (losses.CrossEntropy), or the all-entity calls of the distance models, "
-                         "mkb_dist_all_* (fused.DistanceAllStep)");
-    return dispatch_model_side(model, head, [&](auto m, auto h) {  // (no kernels are instantiated for the models refused above)
-        if constexpr (decltype(m)::value == MKB_COMPLEX || decltype(m)::value == MKB_DISTMULT) return f(m, h);
-        else return (int)MKB_ERR_UNSUPPORTED;
-    });
-}
-
-// what every entry point that takes tables, a batch and the workspace checks, in this order
-static int all_check(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const void *ws, int64_t ws_bytes, AllPlan &P) {
-    if (int rc = validate_tables(tb)) return rc;
-    MKB_REQUIRE(sample && ws, "null pointer");
-    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "1vsAll needs head-batch or tail-batch");
-    MKB_REQUIRE(B >= 1, "B must be >= 1");
-    if (tb->model != MKB_COMPLEX && tb->model != MKB_DISTMULT) return dispatch_dot_model(tb->model, false, [](auto, auto) { return MKB_OK; });
-    MKB_REQUIRE(tb->entity_dim <= 4 * kWGr, "rows of more than 4096 units are not supported");
-    int rc;
-    if (!all_plan(tb, B, P, &rc)) {
-        if (rc) return rc;
-        MKB_REQUIRE(false, "B * (n_entity + 3) and B * entity_dim must stay below 2^31, n_entity below 2^30");
-    }
-    MKB_REQUIRE(ws_bytes >= (int64_t)P.total && (((uintptr_t)ws) & 255) == 0, "workspace too small / unaligned");
-    return MKB_OK;
-}
-
 int softmax_check(const void *S, int64_t B, int64_t N, int64_t ld, const void *target, int64_t tstride, float T, const void *loss,
                          const void *pos, const void *scratch) {
     MKB_REQUIRE(S && target && loss && pos && scratch, "null pointer");
@@ -407,48 +304,65 @@ int bce_check(int64_t N, int64_t R, int mode, const void *keys, int64_t n_keys, 
     return MKB_OK;
 }
 
-// The step behind mkb_all_step, mkb_all_kvs_step and mkb_all_filtered_step, whose checks (all_check among them) have passed: the forward block, the loss
-// on it -- loss(S, ld, scratch) launches it from the forward's finish and leaves dS in S --, the backward.
-template <class Loss>
-static int all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode, const AllPlan &P, void *ws,
-                    hipStream_t st, Loss &&loss) {
-    const AllWs w = all_carve(P, ws);
-    const int64_t N = tb->n_entity;
-    int64_t ld_S = 0;
-    auto finish = [&](float, float, int64_t ld) {  // (the two models' blocks are finished scores: c0 = 0, c1 = 1)
-        ld_S = ld;
-        loss(w.S, ld, w.scratch);
-    };
-    return dispatch_dot_model(tb->model, mode == MKB_MODE_HEAD, [&](auto m, auto h) {
-        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
-        return all_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, ld_S > N, P, w, st);
-    });
-}
+// ---- the family of the two models whose all-entity block is one product, for the protocol of all_host.h
+struct DotFamily {
+    static constexpr bool covers(int model) { return model == MKB_COMPLEX || model == MKB_DISTMULT; }
+    static constexpr const char *refusal =
+        "1vsAll covers ComplEx and DistMult, whose all-entity block is one matrix product; for TransE, RotatE and "
+        "pRotatE use the sampled softmax (losses.CrossEntropy), or the all-entity calls of the distance models, "
+        "mkb_dist_all_* (fused.DistanceAllStep)";
+    static constexpr const char *mode_text = "1vsAll needs head-batch or tail-batch";
+    struct Launch {};  // (the two backward products are planned where they are launched: plan_gemm)
+
+    // the partial buffer of the two backward products, used one after the other; nothing behind the loss scratch
+    static FamilyBytes plan(const mkb_tables_t *tb, int64_t B, Launch &) {
+        const int64_t N = tb->n_entity, Npad = all_npad(N), De = tb->entity_dim;
+        const GemmSwitches sw{false, false, true};  // (part_bound does not depend on the switches)
+        const size_t part = std::max(plan_gemm(all_dq_shape(B, N, De, Npad, true, true), all_dq_limits(), sw).part_bound,
+                                     plan_gemm(all_de_shape(B, N, De, Npad, true), all_de_limits(N, De), sw).part_bound);
+        return FamilyBytes{part * 4, 0};
+    }
+
+    // (never reached: the two models' blocks are finished scores on every route of run_rank, c0 = 0, c1 = 1)
+    static void finish_block(float *, int64_t, int64_t, int64_t, float, float, hipStream_t) {}
+
+    // dS [B, ld] -> g_ent, g_rel (accumulated)
+    template <int MODEL, bool HEAD>
+    static int bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, const float *dS, int64_t ld,
+                   bool gathered, const AllPlan<DotFamily> &P, const AllWs &w, hipStream_t st) {
+        const int64_t N = tb->n_entity, De = tb->entity_dim;
+        const GemmSwitches sw = gemm_switches_from_env();
+        const bool al = (((uintptr_t)dS | (uintptr_t)tb->ent | (uintptr_t)gr->g_ent) & 15) == 0;  // (Q, dQ: the 256-byte aligned workspace)
+        ChainArgs A;
+        if (int rc = all_chain_open<HEAD>(tb, gr, sample, B, w.dQ, w.stash, w.sort, P.sort, st, A)) return rc;
+        {
+            const GemmPlan plan = plan_gemm(all_dq_shape(B, N, De, ld, gathered, al), all_dq_limits(), sw);
+            GemmArgs G = gemm_args(plan);
+            G.A = dS; G.B = tb->ent; G.C = w.dQ; G.b_idx = gathered ? w.ids : nullptr;
+            if (int rc = launch_gemm<true, false, GEMM_STORE>(plan, G, st, w.part)) return rc;
+        }
+        {
+            const GemmPlan plan = plan_gemm(all_de_shape(B, N, De, ld, al), all_de_limits(N, De), sw);
+            GemmArgs G = gemm_args(plan);
+            G.A = dS; G.B = w.Q; G.C = gr->g_ent;
+            if (int rc = launch_gemm<false, false, GEMM_ACCUM>(plan, G, st, w.part)) return rc;
+        }
+        hipLaunchKernelGGL((all_chain_kernel<MODEL, HEAD>), dim3((unsigned)(2 * B)), dim3(256), 0, st, A);
+        MKB_LAUNCH_CHECK();
+        return MKB_OK;
+    }
+};
 
 }  // namespace mkb
 
 using namespace mkb;
 
-extern "C" int64_t mkb_all_step_workspace_bytes(const mkb_tables_t *tb, int64_t B) {
-    AllPlan P;
-    int rc;
-    if (!tb || B <= 0 || (tb->model != MKB_COMPLEX && tb->model != MKB_DISTMULT) || !all_plan(tb, B, P, &rc)) return 0;
-    return (int64_t)P.total;
-}
+// (the calls that take tables: the bodies of all_host.h for DotFamily)
+extern "C" int64_t mkb_all_step_workspace_bytes(const mkb_tables_t *tb, int64_t B) { return all_workspace_bytes<DotFamily>(tb, B); }
 
 extern "C" int mkb_all_score_fwd(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, float *scores, void *ws,
                                  int64_t ws_bytes, void *stream) {
-    AllPlan P;
-    MKB_REQUIRE(scores, "null pointer");
-    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    const AllWs w = all_carve(P, ws);
-    hipStream_t st = (hipStream_t)stream;
-    auto finish = [&](float f0, float f1, int64_t ld) {  // the evaluation's export: the bits mkb_rank_scores hands out
-        hipLaunchKernelGGL(export_scores_kernel, dim3((unsigned)std::min<int64_t>((tb->n_entity + 255) / 256, 64), (unsigned)B), dim3(256), 0,
-                           st, w.S, scores, tb->n_entity, ld, f0, f1);
-    };
-    return dispatch_dot_model(tb->model, mode == MKB_MODE_HEAD,
-                              [&](auto m, auto h) { return run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish); });
+    return all_score_fwd<DotFamily>(tb, sample, B, mode, scores, ws, ws_bytes, stream);
 }
 
 extern "C" int mkb_all_softmax(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t target_stride,
@@ -462,31 +376,13 @@ extern "C" int mkb_all_softmax(float *S, int64_t B, int64_t N, int64_t ld, const
 
 extern "C" int mkb_all_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode,
                                  const float *dscore, int64_t ld, void *ws, int64_t ws_bytes, void *stream) {
-    AllPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && dscore, "null pointer");
-    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    MKB_REQUIRE(ld >= tb->n_entity && B * ld <= INT32_MAX, "need ld >= n_entity and B * ld below 2^31");
-    const AllWs w = all_carve(P, ws);
-    hipStream_t st = (hipStream_t)stream;
-    return dispatch_dot_model(tb->model, mode == MKB_MODE_HEAD, [&](auto m, auto h) {
-        const RowArgs ra = query_build_args(tb->ent, tb->rel, sample, w.Q, tb->entity_dim, tb->relation_dim, tb->hidden_dim, B, tb->phase_div);
-        hipLaunchKernelGGL((query_build_kernel<m(), h()>), dim3((unsigned)B), dim3(256), 0, st, ra);
-        return all_bwd<m(), h()>(tb, gr, sample, B, dscore, ld, false, P, w, st);
-    });
+    return all_score_bwd<DotFamily>(tb, gr, sample, B, mode, dscore, ld, ws, ws_bytes, stream);
 }
 
 extern "C" int mkb_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
                             int mode, float temperature, const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes,
                             void *stream) {
-    AllPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
-    MKB_REQUIRE(temperature - temperature == 0.f && temperature > 0.f, "the softmax temperature must be finite and > 0");
-    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
-        all_softmax_launch(S, B, tb->n_entity, ld, sample + (mode == MKB_MODE_HEAD ? 0 : 2), 3, weight, weight_sum, temperature, loss, pos,
-                           scratch, st);
-    });
+    return all_softmax_step<DotFamily>(tb, gr, sample, weight, B, mode, temperature, weight_sum, loss, pos, ws, ws_bytes, stream);
 }
 
 extern "C" int mkb_all_bce(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *sample, int mode, int64_t n_relation,
@@ -503,15 +399,8 @@ extern "C" int mkb_all_bce(float *S, int64_t B, int64_t N, int64_t ld, const int
 extern "C" int mkb_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
                                 int mode, const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities,
                                 const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream) {
-    AllPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
-    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
-        all_bce_launch(S, B, tb->n_entity, ld, sample, mode == MKB_MODE_HEAD, tb->n_relation, keys, n_keys, weight, weight_sum, smoothing,
-                       sum_over_entities != 0, loss, pos, scratch, st);
-    });
+    return all_kvs_step<DotFamily>(tb, gr, sample, weight, B, mode, keys, n_keys, smoothing, sum_over_entities, weight_sum, loss, pos, ws,
+                                   ws_bytes, stream);
 }
 
 extern "C" int mkb_all_softmax_filtered(float *S, int64_t B, int64_t N, int64_t ld, const int64_t *target, int64_t target_stride,
@@ -530,14 +419,6 @@ extern "C" int mkb_all_softmax_filtered(float *S, int64_t B, int64_t N, int64_t 
 extern "C" int mkb_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
                                      int mode, const int64_t *keys, int64_t n_keys, float T, float smoothing, const float *weight_sum,
                                      float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream) {
-    AllPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
-    MKB_REQUIRE(T - T == 0.f && T > 0.f, "the softmax temperature must be finite and > 0");
-    if (int rc = all_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing, "filtered 1vsAll")) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return all_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
-        all_softmax_filtered_launch(S, B, tb->n_entity, ld, sample + (mode == MKB_MODE_HEAD ? 0 : 2), 3, sample, mode == MKB_MODE_HEAD,
-                                    tb->n_relation, keys, n_keys, weight, weight_sum, T, smoothing, loss, pos, scratch, st);
-    });
+    return all_filtered_step<DotFamily>(tb, gr, sample, weight, B, mode, keys, n_keys, T, smoothing, weight_sum, loss, pos, ws, ws_bytes,
+                                        stream);
 }

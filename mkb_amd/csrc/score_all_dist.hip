@@ -31,10 +31,12 @@
 // RotatE's clamped norm gives a coinciding pair a gradient of exactly 0.
 // A single pass producing dQ and dE from one evaluation of the pair term was not tried: one of the two sums would have to leave
 // the workgroup as a partial per tile ([N / 16, B, De] or [B / 16, N, De] floats) to keep the one-writer rule without atomics.
+// The host side -- workspace plan, entry checks, model dispatch, the step and the bodies of the calls -- is all_host.h's, shared with
+// score_all.hip; this file gives it DistFamily: the three models, the two passes' launch fields and buffers, the affine finish and
+// the backward above.
 #include "common.h"
-#include "all_chain.h"
+#include "all_host.h"   // (all_chain.h, rank_all.h)
 #include "loss_math.h"  // block_sum_256
-#include "rank_all.h"
 
 #include <algorithm>
 
@@ -216,218 +218,101 @@ static __global__ __launch_bounds__(256) void dist_affine_kernel(float *__restri
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < N; e += (int64_t)gridDim.x * 256) S[i * ld + e] = c0 + c1 * S[i * ld + e];
 }
 
-// ---- workspace: Q [B, De], the score block [B, Npad] (which becomes dS), the id list [Npad], dQ [B, De], the stash [B, De] of
-// all_stash_kernel, the dQ pass's partials [slices, B, De], the sort's storage, the loss scratch [1 + B], the
-// modulus partials (pRotatE: one float per workgroup of the dE pass)
-struct DistPlan {
-    PairSortPlan sort;
-    int slices, uslices;
-    int64_t per, de_tiles;
-    size_t s_off, ids_off, dq_off, stash_off, part_off, sort_off, scr_off, mod_off, total;
-};
-struct DistWs {
-    float *Q, *S;
-    int64_t *ids;
-    float *dQ, *stash, *part;
-    void *sort;
-    float *scratch, *modpart;
-};
-
 static int64_t dist_units(const mkb_tables_t *tb) { return tb->model == MKB_ROTATE ? tb->hidden_dim : tb->entity_dim; }
 
-// The shapes of all_plan (score_all.hip): one int32 sort and B * Npad, B * De below 2^31 (B >= 1 is the caller's).  false: outside
-// them, or the sort's size query failed (*rc < 0)
-static bool dist_plan(const mkb_tables_t *tb, int64_t B, DistPlan &P, int *rc) {
-    *rc = 0;
-    const int64_t N = tb->n_entity, Npad = all_npad(N), De = tb->entity_dim;
-    if (N <= 0 || tb->n_relation <= 0 || De <= 0 || Npad >= (1 << 30) || N + tb->n_relation > INT32_MAX || B > INT32_MAX / 2 ||
-        B * Npad > INT32_MAX || B * De > INT32_MAX)
-        return false;
-    if ((*rc = pair_sort_plan(N + tb->n_relation, 2 * B, P.sort))) return false;
-    P.uslices = (int)((dist_units(tb) + 255) / 256);
-    P.de_tiles = (N + kDT - 1) / kDT;
-    // the dQ pass: enough workgroups to fill the device, every slice a multiple of the staged block
-    const int64_t tiles = (B + kDT - 1) / kDT * P.uslices, blocks = (N + kDC - 1) / kDC;
-    const int64_t want = std::min<int64_t>(std::min<int64_t>((kDqTilesWanted + tiles - 1) / tiles, kDqSlicesMax), blocks);
-    P.per = (blocks + want - 1) / want * kDC;
-    P.slices = (int)((N + P.per - 1) / P.per);
-    P.s_off = up256((size_t)B * De * 4);
-    P.ids_off = P.s_off + up256((size_t)B * Npad * 4);
-    P.dq_off = P.ids_off + up256((size_t)Npad * 8);
-    P.stash_off = P.dq_off + up256((size_t)B * De * 4);
-    P.part_off = P.stash_off + up256((size_t)B * De * 4);
-    // the partials, sized by a bound that grows with B where slices * B itself does not: slices <= 8 and slices <= 1024 / tiles + 1
-    // with tiles >= B uslices / 16
-    const int64_t part_rows = std::min<int64_t>(kDqSlicesMax * B, (int64_t)kDqTilesWanted * kDT / P.uslices + B);
-    P.sort_off = P.part_off + up256((size_t)part_rows * De * 4);
-    P.scr_off = P.sort_off + P.sort.total;
-    P.mod_off = P.scr_off + up256((size_t)(B + 1) * 4);
-    P.total = P.mod_off + (tb->model == MKB_PROTATE ? up256((size_t)P.de_tiles * P.uslices * 4) : 0);
-    return true;
-}
-
-static DistWs dist_carve(const DistPlan &P, void *ws) {
-    unsigned char *b = (unsigned char *)ws;
-    return DistWs{(float *)b, (float *)(b + P.s_off), (int64_t *)(b + P.ids_off), (float *)(b + P.dq_off), (float *)(b + P.stash_off),
-                  (float *)(b + P.part_off), b + P.sort_off, (float *)(b + P.scr_off), (float *)(b + P.mod_off)};
-}
-
-static bool dist_model(int model) { return model == MKB_TRANSE || model == MKB_ROTATE || model == MKB_PROTATE; }
-
-// dispatch_model_side (common.h) for the three distance models; ComplEx and DistMult are sent to their own calls
-template <class F>
-static int dispatch_dist_model(int model, bool head, F &&f) {
-    if (!dist_model(model))
-        return set_error(MKB_ERR_UNSUPPORTED,
-                         "the mkb_dist_all_* calls cover TransE, RotatE and pRotatE; ComplEx and DistMult, whose all-entity block is one "
-                         "matrix product, have mkb_all_step, mkb_all_kvs_step, mkb_all_filtered_step and mkb_all_score_fwd / _bwd");
-    return dispatch_model_side(model, head, [&](auto m, auto h) {  // (no kernels are instantiated for the models refused above)
-        if constexpr (decltype(m)::value == MKB_TRANSE || decltype(m)::value == MKB_ROTATE || decltype(m)::value == MKB_PROTATE) return f(m, h);
-        else return (int)MKB_ERR_UNSUPPORTED;
-    });
-}
-
-// what every entry point that takes tables, a batch and the workspace checks, in the order of score_all.hip's all_check
-static int dist_check(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, const void *ws, int64_t ws_bytes, DistPlan &P) {
-    if (int rc = validate_tables(tb)) return rc;
-    MKB_REQUIRE(sample && ws, "null pointer");
-    MKB_REQUIRE(mode == MKB_MODE_HEAD || mode == MKB_MODE_TAIL, "the all-entity losses need head-batch or tail-batch");
-    MKB_REQUIRE(B >= 1, "B must be >= 1");
-    if (!dist_model(tb->model)) return dispatch_dist_model(tb->model, false, [](auto, auto) { return MKB_OK; });
-    MKB_REQUIRE(tb->entity_dim <= 4 * kWGr, "rows of more than 4096 units are not supported");
-    int rc;
-    if (!dist_plan(tb, B, P, &rc)) {
-        if (rc) return rc;
-        MKB_REQUIRE(false, "B * (n_entity + 3) and B * entity_dim must stay below 2^31, n_entity below 2^30");
-    }
-    MKB_REQUIRE(ws_bytes >= (int64_t)P.total && (((uintptr_t)ws) & 255) == 0, "workspace too small / unaligned");
-    return MKB_OK;
-}
-
-// dS [B, ld] -> g_ent, g_rel, g_modulus (accumulated).  w.Q holds the batch's queries.
-template <int MODEL, bool HEAD>
-static int dist_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, const float *dS, int64_t ld,
-                    const DistPlan &P, const DistWs &w, hipStream_t st) {
-    const int64_t N = tb->n_entity, De = tb->entity_dim;
-    ChainArgs C;
-    if (int rc = all_chain_open<HEAD>(tb, gr, sample, B, w.dQ, w.stash, w.sort, P.sort, st, C)) return rc;
-    DistArgs A{};
-    A.ent = tb->ent; A.Q = w.Q; A.dS = dS; A.modulus = tb->modulus; A.g_ent = gr->g_ent;
-    A.dQ = P.slices > 1 ? w.part : w.dQ;
-    A.modpart = MODEL == MKB_PROTATE && gr->g_modulus ? w.modpart : nullptr;
-    A.B = (int)B; A.d = tb->hidden_dim; A.U = (int)dist_units(tb); A.N = N; A.De = De; A.ld = ld; A.per = P.per; A.kd = tb->phase_div;
-    hipLaunchKernelGGL((dist_dq_kernel<MODEL, HEAD>), dim3((unsigned)((B + kDT - 1) / kDT), (unsigned)P.uslices, (unsigned)P.slices), dim3(256),
-                       0, st, A);
-    if (P.slices > 1)
-        hipLaunchKernelGGL(dist_dq_reduce_kernel, dim3((unsigned)((B * De + 255) / 256)), dim3(256), 0, st, w.part, w.dQ, B * De, P.slices);
-    hipLaunchKernelGGL((dist_de_kernel<MODEL, HEAD>), dim3((unsigned)P.de_tiles, (unsigned)P.uslices), dim3(256), 0, st, A);
-    if (A.modpart) hipLaunchKernelGGL(dist_mod_kernel, dim3(1), dim3(256), 0, st, w.modpart, P.de_tiles * P.uslices, gr->g_modulus);
-    hipLaunchKernelGGL((all_chain_kernel<MODEL, HEAD>), dim3((unsigned)(2 * B)), dim3(256), 0, st, C);
-    MKB_LAUNCH_CHECK();
-    return MKB_OK;
-}
-
-// The step behind mkb_dist_all_step, mkb_dist_all_kvs_step and mkb_dist_all_filtered_step, whose checks have passed: the forward
-// block, finished where the route left raw pair sums, the loss on it -- loss(S, ld, scratch) leaves dS in S --, the backward.
-template <class Loss>
-static int dist_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode, const DistPlan &P, void *ws,
-                     hipStream_t st, Loss &&loss) {
-    const DistWs w = dist_carve(P, ws);
-    const int64_t N = tb->n_entity;
-    int64_t ld_S = 0;
-    auto finish = [&](float c0, float c1, int64_t ld) {
-        ld_S = ld;
-        if (!(c0 == 0.f && c1 == 1.f))
-            hipLaunchKernelGGL(dist_affine_kernel, dim3((unsigned)std::min<int64_t>((N + 255) / 256, 64), (unsigned)B), dim3(256), 0, st, w.S, N,
-                               ld, c0, c1);
-        loss(w.S, ld, w.scratch);
+// ---- the family of the three distance models, for the protocol of all_host.h
+struct DistFamily {
+    static constexpr bool covers(int model) { return model == MKB_TRANSE || model == MKB_ROTATE || model == MKB_PROTATE; }
+    static constexpr const char *refusal =
+        "the mkb_dist_all_* calls cover TransE, RotatE and pRotatE; ComplEx and DistMult, whose all-entity block is one "
+        "matrix product, have mkb_all_step, mkb_all_kvs_step, mkb_all_filtered_step and mkb_all_score_fwd / _bwd";
+    static constexpr const char *mode_text = "the all-entity losses need head-batch or tail-batch";
+    struct Launch {
+        int slices, uslices;
+        int64_t per, de_tiles;
     };
-    return dispatch_dist_model(tb->model, mode == MKB_MODE_HEAD, [&](auto m, auto h) {
-        if (int rc = run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish)) return rc;
-        return dist_bwd<m(), h()>(tb, gr, sample, B, w.S, ld_S, P, w, st);
-    });
-}
+
+    // the dQ pass's partials [slices, B, De]; behind the loss scratch the modulus partials (pRotatE: one float per workgroup of the
+    // dE pass)
+    static FamilyBytes plan(const mkb_tables_t *tb, int64_t B, Launch &L) {
+        const int64_t N = tb->n_entity, De = tb->entity_dim;
+        L.uslices = (int)((dist_units(tb) + 255) / 256);
+        L.de_tiles = (N + kDT - 1) / kDT;
+        // the dQ pass: enough workgroups to fill the device, every slice a multiple of the staged block
+        const int64_t tiles = (B + kDT - 1) / kDT * L.uslices, blocks = (N + kDC - 1) / kDC;
+        const int64_t want = std::min<int64_t>(std::min<int64_t>((kDqTilesWanted + tiles - 1) / tiles, kDqSlicesMax), blocks);
+        L.per = (blocks + want - 1) / want * kDC;
+        L.slices = (int)((N + L.per - 1) / L.per);
+        // the partials, sized by a bound that grows with B where slices * B itself does not: slices <= 8 and slices <= 1024 / tiles + 1
+        // with tiles >= B uslices / 16
+        const int64_t part_rows = std::min<int64_t>(kDqSlicesMax * B, (int64_t)kDqTilesWanted * kDT / L.uslices + B);
+        return FamilyBytes{(size_t)part_rows * De * 4, tb->model == MKB_PROTATE ? (size_t)L.de_tiles * L.uslices * 4 : 0};
+    }
+
+    // raw pair sums -> scores: the loss kernels want scores
+    static void finish_block(float *S, int64_t B, int64_t N, int64_t ld, float c0, float c1, hipStream_t st) {
+        hipLaunchKernelGGL(dist_affine_kernel, dim3((unsigned)std::min<int64_t>((N + 255) / 256, 64), (unsigned)B), dim3(256), 0, st, S, N, ld,
+                           c0, c1);
+    }
+
+    // dS [B, ld] -> g_ent, g_rel, g_modulus (accumulated); w.tail: the modulus partials
+    template <int MODEL, bool HEAD>
+    static int bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, const float *dS, int64_t ld, bool,
+                   const AllPlan<DistFamily> &P, const AllWs &w, hipStream_t st) {
+        const int64_t N = tb->n_entity, De = tb->entity_dim;
+        const Launch &L = P.launch;
+        ChainArgs C;
+        if (int rc = all_chain_open<HEAD>(tb, gr, sample, B, w.dQ, w.stash, w.sort, P.sort, st, C)) return rc;
+        DistArgs A{};
+        A.ent = tb->ent; A.Q = w.Q; A.dS = dS; A.modulus = tb->modulus; A.g_ent = gr->g_ent;
+        A.dQ = L.slices > 1 ? w.part : w.dQ;
+        A.modpart = MODEL == MKB_PROTATE && gr->g_modulus ? w.tail : nullptr;
+        A.B = (int)B; A.d = tb->hidden_dim; A.U = (int)dist_units(tb); A.N = N; A.De = De; A.ld = ld; A.per = L.per; A.kd = tb->phase_div;
+        hipLaunchKernelGGL((dist_dq_kernel<MODEL, HEAD>), dim3((unsigned)((B + kDT - 1) / kDT), (unsigned)L.uslices, (unsigned)L.slices), dim3(256),
+                           0, st, A);
+        if (L.slices > 1)
+            hipLaunchKernelGGL(dist_dq_reduce_kernel, dim3((unsigned)((B * De + 255) / 256)), dim3(256), 0, st, w.part, w.dQ, B * De, L.slices);
+        hipLaunchKernelGGL((dist_de_kernel<MODEL, HEAD>), dim3((unsigned)L.de_tiles, (unsigned)L.uslices), dim3(256), 0, st, A);
+        if (A.modpart) hipLaunchKernelGGL(dist_mod_kernel, dim3(1), dim3(256), 0, st, w.tail, L.de_tiles * L.uslices, gr->g_modulus);
+        hipLaunchKernelGGL((all_chain_kernel<MODEL, HEAD>), dim3((unsigned)(2 * B)), dim3(256), 0, st, C);
+        MKB_LAUNCH_CHECK();
+        return MKB_OK;
+    }
+};
 
 }  // namespace mkb
 
 using namespace mkb;
 
-extern "C" int64_t mkb_dist_all_workspace_bytes(const mkb_tables_t *tb, int64_t B) {
-    DistPlan P;
-    int rc;
-    if (!tb || B <= 0 || !dist_model(tb->model) || !dist_plan(tb, B, P, &rc)) return 0;
-    return (int64_t)P.total;
-}
+// (the bodies of all_host.h for DistFamily)
+extern "C" int64_t mkb_dist_all_workspace_bytes(const mkb_tables_t *tb, int64_t B) { return all_workspace_bytes<DistFamily>(tb, B); }
 
 extern "C" int mkb_dist_all_score_fwd(const mkb_tables_t *tb, const int64_t *sample, int64_t B, int mode, float *scores, void *ws,
                                       int64_t ws_bytes, void *stream) {
-    DistPlan P;
-    MKB_REQUIRE(scores, "null pointer");
-    if (int rc = dist_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    const DistWs w = dist_carve(P, ws);
-    hipStream_t st = (hipStream_t)stream;
-    auto finish = [&](float f0, float f1, int64_t ld) {  // the evaluation's export: the bits mkb_rank_scores hands out
-        hipLaunchKernelGGL(export_scores_kernel, dim3((unsigned)std::min<int64_t>((tb->n_entity + 255) / 256, 64), (unsigned)B), dim3(256), 0,
-                           st, w.S, scores, tb->n_entity, ld, f0, f1);
-    };
-    return dispatch_dist_model(tb->model, mode == MKB_MODE_HEAD,
-                               [&](auto m, auto h) { return run_rank<m(), h()>(tb, sample, B, w.Q, w.S, w.ids, st, finish); });
+    return all_score_fwd<DistFamily>(tb, sample, B, mode, scores, ws, ws_bytes, stream);
 }
 
 extern "C" int mkb_dist_all_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, int mode,
                                       const float *dscore, int64_t ld, void *ws, int64_t ws_bytes, void *stream) {
-    DistPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && dscore, "null pointer");
-    if (int rc = dist_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    MKB_REQUIRE(ld >= tb->n_entity && B * ld <= INT32_MAX, "need ld >= n_entity and B * ld below 2^31");
-    const DistWs w = dist_carve(P, ws);
-    hipStream_t st = (hipStream_t)stream;
-    return dispatch_dist_model(tb->model, mode == MKB_MODE_HEAD, [&](auto m, auto h) {
-        const RowArgs ra = query_build_args(tb->ent, tb->rel, sample, w.Q, tb->entity_dim, tb->relation_dim, tb->hidden_dim, B, tb->phase_div);
-        hipLaunchKernelGGL((query_build_kernel<m(), h()>), dim3((unsigned)B), dim3(256), 0, st, ra);
-        return dist_bwd<m(), h()>(tb, gr, sample, B, dscore, ld, P, w, st);
-    });
+    return all_score_bwd<DistFamily>(tb, gr, sample, B, mode, dscore, ld, ws, ws_bytes, stream);
 }
 
 extern "C" int mkb_dist_all_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
                                  int mode, float temperature, const float *weight_sum, float *loss, float *pos, void *ws,
                                  int64_t ws_bytes, void *stream) {
-    DistPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
-    MKB_REQUIRE(temperature - temperature == 0.f && temperature > 0.f, "the softmax temperature must be finite and > 0");
-    if (int rc = dist_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return dist_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
-        all_softmax_launch(S, B, tb->n_entity, ld, sample + (mode == MKB_MODE_HEAD ? 0 : 2), 3, weight, weight_sum, temperature, loss, pos,
-                           scratch, st);
-    });
+    return all_softmax_step<DistFamily>(tb, gr, sample, weight, B, mode, temperature, weight_sum, loss, pos, ws, ws_bytes, stream);
 }
 
 extern "C" int mkb_dist_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B,
                                      int mode, const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities,
                                      const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream) {
-    DistPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
-    if (int rc = dist_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return dist_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
-        all_bce_launch(S, B, tb->n_entity, ld, sample, mode == MKB_MODE_HEAD, tb->n_relation, keys, n_keys, weight, weight_sum, smoothing,
-                       sum_over_entities != 0, loss, pos, scratch, st);
-    });
+    return all_kvs_step<DistFamily>(tb, gr, sample, weight, B, mode, keys, n_keys, smoothing, sum_over_entities, weight_sum, loss, pos, ws,
+                                    ws_bytes, stream);
 }
 
 extern "C" int mkb_dist_all_filtered_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight,
                                           int64_t B, int mode, const int64_t *keys, int64_t n_keys, float T, float smoothing,
                                           const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream) {
-    DistPlan P;
-    MKB_REQUIRE(gr && gr->g_ent && gr->g_rel && loss && pos, "null pointer");
-    MKB_REQUIRE(T - T == 0.f && T > 0.f, "the softmax temperature must be finite and > 0");
-    if (int rc = dist_check(tb, sample, B, mode, ws, ws_bytes, P)) return rc;
-    if (int rc = bce_check(tb->n_entity, tb->n_relation, mode, keys, n_keys, smoothing, "filtered 1vsAll")) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return dist_step(tb, gr, sample, B, mode, P, ws, st, [&](float *S, int64_t ld, float *scratch) {
-        all_softmax_filtered_launch(S, B, tb->n_entity, ld, sample + (mode == MKB_MODE_HEAD ? 0 : 2), 3, sample, mode == MKB_MODE_HEAD,
-                                    tb->n_relation, keys, n_keys, weight, weight_sum, T, smoothing, loss, pos, scratch, st);
-    });
+    return all_filtered_step<DistFamily>(tb, gr, sample, weight, B, mode, keys, n_keys, T, smoothing, weight_sum, loss, pos, ws, ws_bytes,
+                                         stream);
 }

@@ -19,6 +19,8 @@
                         (``mkb_dist_all_step`` / ``_filtered_step`` / ``_kvs_step``).
 ``distance_score_all`` -- their differentiable ``[B, n_entity]`` block (``mkb_dist_all_score_fwd`` / ``_bwd``).
 """
+import collections
+
 import torch
 
 from . import _gradshare, _hip, _links
@@ -279,68 +281,97 @@ class PooledLossStep(_PooledStep):
         return loss
 
 
-# ---------------------------------------------------------------------------------------------------- 1vsAll (ComplEx / DistMult)
+# ------------------------------------------------------------------------------------- all-entity losses: the two call families
 ONE_VS_ALL_MODELS = ("ComplEx", "DistMult")  # the models whose all-entity block is ONE matrix product
+DISTANCE_MODELS = ("TransE", "RotatE", "pRotatE")  # the models whose all-entity block is a sum of distances
+
+# One record per family of library calls (csrc/all_host.h has their one protocol): ``prefix + "score_fwd" / "score_bwd" / "step" /
+# "filtered_step" / "kvs_step"`` are its calls, ``workspace_symbol`` sizes the scratch they share, ``tag`` keeps the families' cached
+# workspaces apart, ``modulus_grad``: its backward fills pRotatE's modulus gradient, ``refusal``: what a step says of another model.
+_AllFamily = collections.namedtuple("_AllFamily", "prefix workspace_symbol tag models modulus_grad refusal")
+_DOT = _AllFamily("mkb_all_", "mkb_all_step_workspace_bytes", "all", ONE_VS_ALL_MODELS, False,
+                  "{step} covers ComplEx and DistMult, whose all-entity block is one matrix product, not {model}: train it with the "
+                  "sampled softmax, losses.CrossEntropy, or over all entities with fused.DistanceAllStep")
+_DIST = _AllFamily("mkb_dist_all_", "mkb_dist_all_workspace_bytes", "dist_all", DISTANCE_MODELS, True,
+                   "{step} covers TransE, RotatE, pRotatE, whose all-entity block is a sum of distances, not {model}: its block is one "
+                   "matrix product, use fused.OneVsAllStep / fused.KvsAllStep")
+
+
+def _family_workspace(fam, model, B):
+    """Device scratch of the calls of ``fam`` that take tables, cached like ``_workspace``."""
+    dev = model.entity_embedding.device
+    key = (dev, _hip.stream_ptr(dev).value, fam.tag, model.name, model.entity_dim, model.n_entity, model.n_relation, B)
+    return cached_workspace(key, dev, lambda: getattr(_hip.lib(), fam.workspace_symbol)(model._tables(), B))
 
 
 def _all_workspace(model, B):
-    """Device scratch of the three ``mkb_all_*`` calls that take tables, cached like ``_workspace``."""
-    dev = model.entity_embedding.device
-    key = (dev, _hip.stream_ptr(dev).value, "all", model.name, model.entity_dim, model.n_entity, model.n_relation, B)
-    return cached_workspace(key, dev, lambda: _hip.lib().mkb_all_step_workspace_bytes(model._tables(), B))
+    return _family_workspace(_DOT, model, B)
+
+
+def _dist_workspace(model, B):
+    return _family_workspace(_DIST, model, B)
+
+
+def _side_keys(triples, model, device, mode_id):
+    """The sorted key array of the side ``mode_id`` scores (``utils.true_keys``, built once per triple set)."""
+    return true_keys(triples, device, model.n_entity, model.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
 
 
 class _ScoreAllFn(torch.autograd.Function):
-    """scores [B, n_entity] of every entity in the open slot of ``sample``; backward = dense d loss / d tables."""
+    """scores [B, n_entity] of every entity in the open slot of ``sample``, for either family (``modulus``: None for the models
+    that have none); backward = dense d loss / d tables and pRotatE's d loss / d modulus."""
 
     @staticmethod
-    def forward(ctx, ent, rel, model, sample, mode):
+    def forward(ctx, ent, rel, modulus, fam, model, sample, mode):
         B = sample.shape[0]
         scores = torch.empty((B, model.n_entity), dtype=torch.float32, device=ent.device)
-        ws = _all_workspace(model, B)
+        ws = _family_workspace(fam, model, B)
+        name = fam.prefix + "score_fwd"
         with _hip.on_device(ent.device):
-            _hip.check(_hip.lib().mkb_all_score_fwd(model._tables(ent, rel), _hip.ptr(sample), B, mode, _hip.ptr(scores), _hip.ptr(ws),
-                                                    ws.numel(), _hip.stream_ptr()), "mkb_all_score_fwd")
-        ctx.model, ctx.mode = model, mode
-        ctx.save_for_backward(ent, rel, sample)
+            _hip.check(getattr(_hip.lib(), name)(model._tables(ent, rel, modulus), _hip.ptr(sample), B, mode, _hip.ptr(scores), _hip.ptr(ws),
+                                                 ws.numel(), _hip.stream_ptr()), name)
+        ctx.fam, ctx.model, ctx.mode = fam, model, mode
+        ctx.save_for_backward(ent, rel, modulus, sample)
         return scores
 
     @staticmethod
     def backward(ctx, dscore):
-        ent, rel, sample = ctx.saved_tensors
-        model, B = ctx.model, sample.shape[0]
+        ent, rel, modulus, sample = ctx.saved_tensors
+        fam, model, B = ctx.fam, ctx.model, sample.shape[0]
         dscore = _hip.contiguous(dscore, torch.float32)
         g_ent, g_rel = torch.zeros_like(ent), torch.zeros_like(rel)  # every entity row is written: dense, through autograd
-        ws = _all_workspace(model, B)
+        g_mod = torch.zeros_like(modulus) if fam.modulus_grad and model.name == "pRotatE" else None
+        ws = _family_workspace(fam, model, B)
+        name = fam.prefix + "score_bwd"
         with _hip.on_device(ent.device):
-            _hip.check(_hip.lib().mkb_all_score_bwd(model._tables(ent, rel), _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None),
-                                                    _hip.ptr(sample), B, ctx.mode, _hip.ptr(dscore), dscore.shape[1], _hip.ptr(ws),
-                                                    ws.numel(), _hip.stream_ptr()), "mkb_all_score_bwd")
-        return g_ent, g_rel, None, None, None
+            gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
+            _hip.check(getattr(_hip.lib(), name)(model._tables(ent, rel, modulus), gr, _hip.ptr(sample), B, ctx.mode, _hip.ptr(dscore),
+                                                 dscore.shape[1], _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), name)
+        return g_ent, g_rel, g_mod, None, None, None, None
 
 
 def score_all(model, sample, mode):
     """What ``model.score_all(sample, mode)`` runs (models/base.py checks the arguments and makes row-lazy tables current)."""
-    return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, model, sample, _hip.side_id(mode, "1vsAll scores"))
+    return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, None, _DOT, model, sample,
+                             _hip.side_id(mode, "1vsAll scores"))
+
+
+# what a step's one library call is: ``kind`` its suffix ("step" / "filtered_step" / "kvs_step"), the settings that call takes (None:
+# not one of its arguments) and whether it reads the key array of ``true_triples``
+_AllLoss = collections.namedtuple("_AllLoss", "kind temperature smoothing reduction needs_keys")
 
 
 class _AllEntityStep:
     """What the steps over the whole entity row share (``OneVsAllStep``, ``KvsAllStep``, ``DistanceAllStep``): the argument checks, the optimizer
-    protocol of a step that writes EVERY entity row, the id check, the outputs, the workspace and the regulariser hook.  A subclass
-    launches its one library call in ``_launch``."""
+    protocol of a step that writes EVERY entity row, the id check, the outputs, the workspace, the one library call and the
+    regulariser hook.  A subclass names its ``family`` and describes its loss (``_loss_description() -> _AllLoss``)."""
 
-    models = ONE_VS_ALL_MODELS  # the models the subclass's library call takes
-    workspace = staticmethod(_all_workspace)
+    family = _DOT  # whose calls the subclass makes
 
     def __init__(self, model, regularizer=None):
-        if model.name not in self.models:
-            raise NotImplementedError(self._refusal(model))
+        if model.name not in self.family.models:
+            raise NotImplementedError(self.family.refusal.format(step=type(self).__name__, model=model.name))
         self.model, self.regularizer, self.regularization = model, regularizer, None
-
-    def _refusal(self, model):
-        return (f"{type(self).__name__} covers {' and '.join(ONE_VS_ALL_MODELS)}, whose all-entity block is one "
-                f"matrix product, not {model.name}: train it with the sampled softmax, losses.CrossEntropy, or over all "
-                f"entities with fused.DistanceAllStep")
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
         """The other steps' entry point (``compose.Pipeline`` calls it): nothing is drawn from ``sampler``."""
@@ -365,12 +396,23 @@ class _AllEntityStep:
         m._launch_id_check(sample, None)
         pos = torch.empty((B, 1), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ws = self.workspace(m, B)
+        ws = _family_workspace(self.family, m, B)
         gr = grad_buffers(m)
         with _hip.on_device(dev):
             self._launch(m._tables(), gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws)
         self.positive_score = pos
         return _with_regularizer(self, loss.reshape(()), sample, weight, weight_sum, gr)
+
+    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
+        L = self._loss_description()
+        keys = _side_keys(self.true_triples, self.model, sample.device, mode_id) if L.needs_keys else None
+        labels = (_hip.ptr(keys), 0 if keys is None else keys.numel())
+        settings = {"step": (L.temperature,),
+                    "filtered_step": labels + (L.temperature, L.smoothing),
+                    "kvs_step": labels + (L.smoothing, int(L.reduction == "sum"))}[L.kind]
+        name = self.family.prefix + L.kind
+        _hip.check(getattr(_hip.lib(), name)(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, *settings, _hip.ptr(weight_sum),
+                                             _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), name)
 
 
 class OneVsAllStep(_AllEntityStep):
@@ -395,19 +437,9 @@ class OneVsAllStep(_AllEntityStep):
         self.label_smoothing = kvs_all.checked_settings(label_smoothing, kvs_all.REDUCTIONS[0])[0]
         self.true_triples = true_triples
 
-    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
-        if self.true_triples is None and self.label_smoothing == 0.0:
-            _hip.check(_hip.lib().mkb_all_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, self.temperature,
-                                               _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
-                                               _hip.stream_ptr()), "mkb_all_step")
-            return
-        m, keys = self.model, None
-        if self.true_triples is not None:
-            keys = true_keys(self.true_triples, sample.device, m.n_entity, m.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
-        _hip.check(_hip.lib().mkb_all_filtered_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, _hip.ptr(keys),
-                                                    0 if keys is None else keys.numel(), self.temperature, self.label_smoothing,
-                                                    _hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(),
-                                                    _hip.stream_ptr()), "mkb_all_filtered_step")
+    def _loss_description(self):
+        filtered = self.true_triples is not None or self.label_smoothing != 0.0
+        return _AllLoss("filtered_step" if filtered else "step", self.temperature, self.label_smoothing, None, self.true_triples is not None)
 
 
 class KvsAllStep(_AllEntityStep):
@@ -426,28 +458,8 @@ class KvsAllStep(_AllEntityStep):
             raise ValueError("KvsAllStep needs true_triples: the known triples its labels come from")
         self.true_triples = true_triples
 
-    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
-        m = self.model
-        keys = true_keys(self.true_triples, sample.device, m.n_entity, m.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
-        _hip.check(_hip.lib().mkb_all_kvs_step(tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id, _hip.ptr(keys), keys.numel(),
-                                               self.label_smoothing, int(self.reduction == "sum"), _hip.ptr(weight_sum),
-                                               _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
-                   "mkb_all_kvs_step")
-
-
-# ------------------------------------------------------------------------------- all-entity losses (TransE / RotatE / pRotatE)
-DISTANCE_MODELS = ("TransE", "RotatE", "pRotatE")  # the models whose all-entity block is a sum of distances
-
-
-def _dist_workspace(model, B):
-    """Device scratch of the five ``mkb_dist_all_*`` calls that take tables, cached like ``_workspace``."""
-    dev = model.entity_embedding.device
-    key = (dev, _hip.stream_ptr(dev).value, "dist_all", model.name, model.entity_dim, model.n_entity, model.n_relation, B)
-    return cached_workspace(key, dev, lambda: _hip.lib().mkb_dist_all_workspace_bytes(model._tables(), B))
-
-
-def _side_keys(triples, model, device, mode_id):
-    return true_keys(triples, device, model.n_entity, model.n_relation)["head-batch" if mode_id == _hip.MODE_HEAD else "tail-batch"]
+    def _loss_description(self):
+        return _AllLoss("kvs_step", None, self.label_smoothing, self.reduction, True)
 
 
 class DistanceAllStep(_AllEntityStep):
@@ -462,8 +474,7 @@ class DistanceAllStep(_AllEntityStep):
 
     ``true_triples``: the known triples of a ``KvsAll`` marker, or of a ``OneVsAll(filter_known=True)``, that holds none."""
 
-    models = DISTANCE_MODELS
-    workspace = staticmethod(_dist_workspace)
+    family = _DIST
 
     def __init__(self, model, loss, regularizer=None, true_triples=None):
         if not isinstance(loss, (one_vs_all.OneVsAll, kvs_all.KvsAll)):
@@ -476,55 +487,11 @@ class DistanceAllStep(_AllEntityStep):
             raise ValueError("DistanceAllStep needs true_triples: the known triples the loss labels or filters by")
         self.filtered = not self.kvs and (loss.filter_known or loss.label_smoothing != 0.0)
 
-    def _refusal(self, model):
-        return (f"DistanceAllStep covers {', '.join(DISTANCE_MODELS)}, whose all-entity block is a sum of distances, not {model.name}: "
-                f"its block is one matrix product, use fused.OneVsAllStep / fused.KvsAllStep")
-
-    def _launch(self, tb, gr, sample, weight, B, mode_id, weight_sum, loss, pos, ws):
-        lib, L = _hip.lib(), self.loss
-        tail = (_hip.ptr(weight_sum), _hip.ptr(loss), _hip.ptr(pos), _hip.ptr(ws), ws.numel(), _hip.stream_ptr())
-        head = (tb, gr, _hip.ptr(sample), _hip.ptr(weight), B, mode_id)
+    def _loss_description(self):
+        L = self.loss
         if self.kvs:
-            keys = _side_keys(self.true_triples, self.model, sample.device, mode_id)
-            _hip.check(lib.mkb_dist_all_kvs_step(*head, _hip.ptr(keys), keys.numel(), L.label_smoothing, int(L.reduction == "sum"), *tail),
-                       "mkb_dist_all_kvs_step")
-        elif self.filtered:
-            keys = _side_keys(self.true_triples, self.model, sample.device, mode_id) if L.filter_known else None
-            _hip.check(lib.mkb_dist_all_filtered_step(*head, _hip.ptr(keys), 0 if keys is None else keys.numel(), L.temperature,
-                                                      L.label_smoothing, *tail), "mkb_dist_all_filtered_step")
-        else:
-            _hip.check(lib.mkb_dist_all_step(*head, L.temperature, *tail), "mkb_dist_all_step")
-
-
-class _DistanceScoreAllFn(torch.autograd.Function):
-    """``_ScoreAllFn`` for the distance models; backward = dense d loss / d tables and pRotatE's d loss / d modulus."""
-
-    @staticmethod
-    def forward(ctx, ent, rel, modulus, model, sample, mode):
-        B = sample.shape[0]
-        scores = torch.empty((B, model.n_entity), dtype=torch.float32, device=ent.device)
-        ws = _dist_workspace(model, B)
-        with _hip.on_device(ent.device):
-            _hip.check(_hip.lib().mkb_dist_all_score_fwd(model._tables(ent, rel, modulus), _hip.ptr(sample), B, mode, _hip.ptr(scores),
-                                                         _hip.ptr(ws), ws.numel(), _hip.stream_ptr()), "mkb_dist_all_score_fwd")
-        ctx.model, ctx.mode = model, mode
-        ctx.save_for_backward(ent, rel, modulus, sample)
-        return scores
-
-    @staticmethod
-    def backward(ctx, dscore):
-        ent, rel, modulus, sample = ctx.saved_tensors
-        model, B = ctx.model, sample.shape[0]
-        dscore = _hip.contiguous(dscore, torch.float32)
-        g_ent, g_rel = torch.zeros_like(ent), torch.zeros_like(rel)  # every entity row is written: dense, through autograd
-        g_mod = torch.zeros_like(modulus) if model.name == "pRotatE" else None
-        ws = _dist_workspace(model, B)
-        with _hip.on_device(ent.device):
-            gr = _hip.Grads(g_ent.data_ptr(), g_rel.data_ptr(), None if g_mod is None else g_mod.data_ptr())
-            _hip.check(_hip.lib().mkb_dist_all_score_bwd(model._tables(ent, rel, modulus), gr, _hip.ptr(sample), B, ctx.mode,
-                                                         _hip.ptr(dscore), dscore.shape[1], _hip.ptr(ws), ws.numel(), _hip.stream_ptr()),
-                       "mkb_dist_all_score_bwd")
-        return g_ent, g_rel, g_mod, None, None, None
+            return _AllLoss("kvs_step", None, L.label_smoothing, L.reduction, True)
+        return _AllLoss("filtered_step" if self.filtered else "step", L.temperature, L.label_smoothing, None, L.filter_known)
 
 
 def distance_score_all(model, sample, mode):
@@ -545,7 +512,5 @@ def distance_score_all(model, sample, mode):
         model._launch_id_check(sample, None)
     if _links.owner(model.entity_embedding) is not None or _links.owner(model.relation_embedding) is not None:
         model._make_current(sample, None)  # every entity row is read
-    modulus = getattr(model, "modulus", None)
-    if modulus is None:
-        modulus = model.gamma
-    return _DistanceScoreAllFn.apply(model.entity_embedding, model.relation_embedding, modulus, model, sample, mode_id)
+    return _ScoreAllFn.apply(model.entity_embedding, model.relation_embedding, getattr(model, "modulus", None), _DIST, model, sample,
+                             mode_id)
