@@ -758,6 +758,37 @@ int mkb_dist_all_kvs_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const i
                           const int64_t *keys, int64_t n_keys, float smoothing, int sum_over_entities, const float *weight_sum,
                           float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- relation prediction: -log P(r | h, t) over ALL relations as an auxiliary training term ------------------------------------
+ * The auxiliary objective of Chen et al. (AKBC 2021), for any of the five models; mkb_amd/csrc/rel_step.hip.  New symbols under
+ * ABI 9: the version is not bumped (symbols are only added).
+ *   S_ij = score of (h_i, j, t_i) in MKB_MODE_DEFAULT for j < n_relation,   row_i = logsumexp_j (S_ij / T) - S_{i, r_i} / T,
+ *   value = lambda sum_i w_i row_i / W,   dS_ij = lambda (w_i / (W T)) (p_ij - [j = r_i])
+ *   over sample [B, 3]; weight [B] or null (all ones), W = sum of weight (B when null), or weight_sum[0] when given (the rows are a
+ *   shard, as for the loss calls).  No filtering of a pair's other known relations, no label smoothing.
+ *   mkb_rel_score_bwd: the backward of the mkb_rel_scores block over all relations: adds d loss / d tables given dscore [B, ld]
+ *   (columns past n_relation are not read) to gr->g_ent rows h_i and t_i, to every row of gr->g_rel and, for pRotatE, to
+ *   gr->g_modulus[0]; never zeroed, rows_clear is not used.  Two passes that recompute the pair terms: pair-major (a workgroup owns a
+ *   sample row and walks the relations; dH[i], dT[i] into the workspace) and relation-major (a workgroup owns 8 relations x 256 units
+ *   and walks a slice of the batch in order; the slices' partials are added left to right and the total added to g_rel once); the
+ *   2 B occurrences of the batch's entities are radix-sorted and each distinct entity's row has one writer that sums its dH / dT
+ *   rows in batch order and adds the sum once; entity rows outside the batch are not written.  No float atomics: two runs give the
+ *   same bits.  The derivatives at the edges are those of every other backward here.
+ *   mkb_rel_step: forward (the block of mkb_rel_scores in the workspace), the softmax of mkb_all_softmax on it and that backward in
+ *   one call.  loss [1] out = value; pos [B] out = S_{i, r_i}, the bits mkb_score_fwd gives sample in MKB_MODE_DEFAULT.  lambda
+ *   enters once: it multiplies the softmax's loss, and the backward passes read a seed as lambda dS_ij -- the explicit sequence
+ *   (mkb_rel_scores, mkb_all_softmax, lambda times its seeds into mkb_rel_score_bwd) gives the bits of this call.
+ *   ws: mkb_rel_step_workspace_bytes(tb, B) bytes (the same for both calls), 256-byte aligned, caller-owned; nothing is allocated
+ *   in a call.  B == 0 is a valid call that launches nothing (ws may be null).  A null pointer (weight and weight_sum may be null),
+ *   B < 0, T or lambda not finite and > 0, ld < n_relation, B * ld, B * n_relation, 2 * B * entity_dim, n_relation * relation_dim
+ *   or n_entity past 2^31 - 1, a short or misaligned workspace, an unknown model -> MKB_ERR_INVALID before any launch; entity rows too
+ *   long for the slot kernels' LDS staging -> MKB_ERR_UNSUPPORTED.  The workspace function returns 0 for B <= 0, null tables or a B
+ *   that the calls refuse. */
+int64_t mkb_rel_step_workspace_bytes(const mkb_tables_t *tb, int64_t B);
+int mkb_rel_score_bwd(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, int64_t B, const float *dscore, int64_t ld,
+                      void *ws, int64_t ws_bytes, void *stream);
+int mkb_rel_step(const mkb_tables_t *tb, const mkb_grads_t *gr, const int64_t *sample, const float *weight, int64_t B, float temperature,
+                 float lambda, const float *weight_sum, float *loss, float *pos, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- per-kernel timing (measurement aid, no reference counterpart) -------------------------------------
  * When enabled, the launches of the named kernel class are bracketed by hipEvents recorded on the SAME stream
  * the kernel is launched on (on = N > 1: every N-th launch only -- the two event records cost ~6 us of stream time

@@ -194,6 +194,10 @@ _SIGNATURES = {
                                          c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mkb_all_filtered_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_float,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mkb_rel_step_workspace_bytes": (c_int64, [POINTER(Tables), c_int64]),
+    "mkb_rel_score_bwd": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "mkb_rel_step": (c_int, [POINTER(Tables), POINTER(Grads), c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_int64, c_void_p]),
 }
 # the all-entity losses of the distance models: argument for argument the mkb_all_* call each one mirrors
 _SIGNATURES.update({"mkb_dist_all_" + new: _SIGNATURES["mkb_all_" + old] for new, old in (

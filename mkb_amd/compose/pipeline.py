@@ -95,6 +95,10 @@ class Pipeline:
         # Opt-in: a ``mkb_amd.regularizers.Lp`` (``N3``, ``L2``) on the positive triples of every batch.  The fused steps take it
         # as one more library call; the explicit sequence adds ``regularizer(model, sample, weight)`` to the loss.
         self.regularizer = None
+        # Opt-in: a ``mkb_amd.losses.RelationPrediction`` -- -log P(r | h, t) over all relations as an auxiliary term on every
+        # batch.  The fused steps take it as one more library call behind the regulariser's; the explicit sequence adds
+        # ``relation_prediction(model, sample, weight)`` to the loss.
+        self.relation_prediction = None
 
     # ------------------------------------------------------------------ one epoch of steps (pipeline.py:206-244)
     def _fused_step_for(self, model, dataset, sampling, optimizer, loss):
@@ -106,16 +110,16 @@ class Pipeline:
         With TransE, RotatE or pRotatE either loss takes ``DistanceAllStep``, with the same defaults."""
         if isinstance(loss, (OneVsAll, KvsAll)) and getattr(model, "name", None) in DISTANCE_MODELS:
             self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
-            return DistanceAllStep(model, loss, regularizer=self.regularizer, true_triples=dataset.train)
+            return DistanceAllStep(model, loss, regularizer=self.regularizer, relation_prediction=self.relation_prediction, true_triples=dataset.train)
         if isinstance(loss, OneVsAll):
             self._borrowed = []  # (every entity row is written: nothing of a row-lazy optimizer is borrowed)
             triples = (dataset.train if loss.true_triples is None else loss.true_triples) if loss.filter_known else None
-            return OneVsAllStep(model, loss.temperature, regularizer=self.regularizer, label_smoothing=loss.label_smoothing,
+            return OneVsAllStep(model, loss.temperature, regularizer=self.regularizer, relation_prediction=self.relation_prediction, label_smoothing=loss.label_smoothing,
                                 true_triples=triples)
         if isinstance(loss, KvsAll):
             self._borrowed = []
             triples = dataset.train if loss.true_triples is None else loss.true_triples
-            return KvsAllStep(model, triples, loss.label_smoothing, loss.reduction, regularizer=self.regularizer)
+            return KvsAllStep(model, triples, loss.label_smoothing, loss.reduction, regularizer=self.regularizer, relation_prediction=self.relation_prediction)
         if not (self.fuse and isinstance(model, BaseModel) and isinstance(sampling, (NegativeSampling, PoolNegativeSampling))
                 and type(loss) in (Adversarial,) + _POOLED_LOSSES and model.entity_embedding.is_cuda
                 and pooled_supported(model, dataset.batch_size, sampling.size)):
@@ -130,8 +134,8 @@ class Pipeline:
             #                              the touched rows may wait for the next catch-up launch (mkb_amd/optim.py)
             self._borrowed.append("defer_step")
         if type(loss) in _POOLED_LOSSES:
-            return PooledLossStep(model, loss, regularizer=self.regularizer)
-        return FusedTrainStep(model, loss.alpha, regularizer=self.regularizer)
+            return PooledLossStep(model, loss, regularizer=self.regularizer, relation_prediction=self.relation_prediction)
+        return FusedTrainStep(model, loss.alpha, regularizer=self.regularizer, relation_prediction=self.relation_prediction)
 
     def _give_back(self, optimizer):
         """Deferral is scoped to learn(): a pending step lives in the table's gradient rows, and the user's own code after
@@ -172,6 +176,8 @@ class Pipeline:
                 error = loss(positive_score, model(sample=sample, negative_sample=negatives, mode=mode), weight)
                 if self.regularizer is not None:
                     error = error + self.regularizer(model, sample, weight)
+                if self.relation_prediction is not None:
+                    error = error + self.relation_prediction(model, sample, weight)
                 error.backward()
             optimizer.step()
             optimizer.zero_grad()

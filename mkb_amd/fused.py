@@ -25,6 +25,7 @@ import torch
 
 from . import _gradshare, _hip, _links
 from .losses import kvs_all, ns_losses, one_vs_all
+from .losses.relation_prediction import relation_table_written
 from .sampling.negative_sampling import PoolInfo
 from .utils.true_keys import true_keys
 
@@ -185,6 +186,8 @@ class _PooledStep:
         S = torch.empty((B, 2 * K), dtype=torch.float32, device=dev)
         ws = _workspace(m, B, K)
         gr = grad_buffers(m)
+        if self.relation_prediction is not None:
+            relation_table_written(m)  # (the term writes every relation row; in front of anything that writes a gradient row)
         ent = m.entity_embedding
         lazy = _links.owner(ent)
         # row-lazy Adam: the rows read become current, and are marked as written, before anything writes a gradient row
@@ -208,10 +211,16 @@ class FusedTrainStep(_PooledStep):
     one more library call (``mkb_reg_rows``, value and gradient in one launch sequence) behind ``mkb_pool_step`` -- which may
     STORE the batch's gradient rows (``rows_clear``), so the regulariser adds onto them afterwards.  Its rows are the batch's heads
     and tails, which the row-lazy protocol has already made current and marked.  The loss returned is loss + regulariser;
-    ``regularization`` keeps the term alone."""
+    ``regularization`` keeps the term alone.
 
-    def __init__(self, model, alpha, regularizer=None):
+    ``relation_prediction``: a ``losses.RelationPrediction`` whose term on the batch joins the step the same way: one more library
+    call (``mkb_rel_step``) behind the step's own calls and behind the regulariser's, adding onto the rows they wrote.  Its entity
+    rows are the batch's heads and tails; it writes every relation row (a relation table stepped by rows is flushed first and
+    stepped densely).  The loss returned is loss + regulariser + term; ``relation_prediction_loss`` keeps the term alone."""
+
+    def __init__(self, model, alpha, regularizer=None, relation_prediction=None):
         self.model, self.alpha, self.regularizer, self.regularization = model, float(alpha), regularizer, None
+        self.relation_prediction, self.relation_prediction_loss = relation_prediction, None
 
     weight_optional = False  # (mkb_pool_step requires weights)
     may_clear_rows = True  # (mkb_pool_step honours rows_clear: it STORES rows the row-lazy optimizer has just consumed and cleared)
@@ -227,11 +236,15 @@ class FusedTrainStep(_PooledStep):
 
 
 def _with_regularizer(step, loss, sample, weight, weight_sum, gr):
-    """loss + the step's regulariser term, whose gradient is added to the buffers ``gr`` the step has just written."""
-    if step.regularizer is None:
-        return loss
-    step.regularization = step.regularizer.launch(step.model, sample, weight, weight_sum, grads=gr)
-    return loss + step.regularization
+    """loss + the step's regulariser term + its relation-prediction term, in that order; their gradients are added to the
+    buffers ``gr`` the step has just written."""
+    if step.regularizer is not None:
+        step.regularization = step.regularizer.launch(step.model, sample, weight, weight_sum, grads=gr)
+        loss = loss + step.regularization
+    if step.relation_prediction is not None:
+        step.relation_prediction_loss = step.relation_prediction.launch(step.model, sample, weight, weight_sum, grads=gr)
+        loss = loss + step.relation_prediction_loss
+    return loss
 
 
 class PooledLossStep(_PooledStep):
@@ -243,12 +256,14 @@ class PooledLossStep(_PooledStep):
     over the ``[B, 2 size]`` pool block with the sampler's multiplicities, then ``mkb_pool_score_bwd`` on its seeds and the
     positive pair's ``mkb_score_bwd``.  Against the explicit autograd sequence this drops the gather of the ``[B, size]`` view,
     the scatter of its gradient back onto pool positions and the dense zero-filled buffers autograd adds into ``.grad``.
-    ``regularizer``: as for ``FusedTrainStep`` (a sixth call, ``mkb_reg_rows``, behind the two backward calls)."""
+    ``regularizer``: as for ``FusedTrainStep`` (a sixth call, ``mkb_reg_rows``, behind the two backward calls);
+    ``relation_prediction``: as for ``FusedTrainStep`` (``mkb_rel_step``, behind that)."""
 
-    def __init__(self, model, loss, regularizer=None):
+    def __init__(self, model, loss, regularizer=None, relation_prediction=None):
         if getattr(loss, "kind", None) not in (_hip.LOSS_MARGIN, _hip.LOSS_PAIR_LOGISTIC, _hip.LOSS_SOFTMAX):
             raise TypeError("PooledLossStep takes losses.MarginRanking, losses.PairwiseLogistic or losses.CrossEntropy")
         self.model, self.loss, self.regularizer, self.regularization = model, loss, regularizer, None
+        self.relation_prediction, self.relation_prediction_loss = relation_prediction, None
 
     weight_optional = True
     # rows_clear stays 0 whatever the optimizer answers: the promise is only honoured by mkb_pool_step / _bwd, and the two backward
@@ -368,10 +383,11 @@ class _AllEntityStep:
 
     family = _DOT  # whose calls the subclass makes
 
-    def __init__(self, model, regularizer=None):
+    def __init__(self, model, regularizer=None, relation_prediction=None):
         if model.name not in self.family.models:
             raise NotImplementedError(self.family.refusal.format(step=type(self).__name__, model=model.name))
         self.model, self.regularizer, self.regularization = model, regularizer, None
+        self.relation_prediction, self.relation_prediction_loss = relation_prediction, None
 
     def sampled(self, sample, weight, sampler, mode, weight_sum=None):
         """The other steps' entry point (``compose.Pipeline`` calls it): nothing is drawn from ``sampler``."""
@@ -420,7 +436,7 @@ class OneVsAllStep(_AllEntityStep):
     ``(h, r, ?)`` (``'tail-batch'``; ``(?, r, t)`` for ``'head-batch'``) and the cross entropy is taken over the whole row, at
     ``temperature``; fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.  ``positive_score``
     [B, 1] of the last call stays available.  One library call (``mkb_all_step``), no autograd, no negatives.  ``weight``: [B] or
-    None (all ones); ``weight_sum`` and ``regularizer``: as for ``FusedTrainStep``.
+    None (all ones); ``weight_sum``, ``regularizer`` and ``relation_prediction``: as for ``FusedTrainStep``.
 
     ``true_triples`` (not None) filters: a row's OTHER known answers in them -- the columns the filtered evaluation leaves out of
     the rank -- are taken out of its softmax and get a gradient of exactly 0; they are read from the sorted key arrays of the
@@ -431,8 +447,8 @@ class OneVsAllStep(_AllEntityStep):
     Optimizers: the step writes EVERY entity row.  A row-lazily stepped table (``optim.Adam(lazy_rows=True)``) is flushed first and
     its step then takes the route "touched rows unknown -> dense"; ``optim.Adagrad`` uses its all-rows form."""
 
-    def __init__(self, model, temperature=1.0, regularizer=None, label_smoothing=0.0, true_triples=None):
-        super().__init__(model, regularizer)
+    def __init__(self, model, temperature=1.0, regularizer=None, label_smoothing=0.0, true_triples=None, relation_prediction=None):
+        super().__init__(model, regularizer, relation_prediction)
         self.temperature = ns_losses._checked("temperature", temperature, positive=True)
         self.label_smoothing = kvs_all.checked_settings(label_smoothing, kvs_all.REDUCTIONS[0])[0]
         self.true_triples = true_triples
@@ -449,10 +465,10 @@ class KvsAllStep(_AllEntityStep):
     (``losses.KvsAll`` has the formula); fills ``param.grad`` (dense, accumulated) and returns the loss as a 0-dim device tensor.
     ``positive_score`` [B, 1] of the last call stays available.  One library call (``mkb_all_kvs_step``): the labels are read from
     the sorted key arrays of the filtered ranking (``utils.true_keys``, built once), no [B, n_entity] label matrix exists.
-    Arguments of the call, optimizers and ``regularizer``: as for ``OneVsAllStep``."""
+    Arguments of the call, optimizers, ``regularizer`` and ``relation_prediction``: as for ``OneVsAllStep``."""
 
-    def __init__(self, model, true_triples, label_smoothing=0.0, reduction="mean", regularizer=None):
-        super().__init__(model, regularizer)
+    def __init__(self, model, true_triples, label_smoothing=0.0, reduction="mean", regularizer=None, relation_prediction=None):
+        super().__init__(model, regularizer, relation_prediction)
         self.label_smoothing, self.reduction = kvs_all.checked_settings(label_smoothing, reduction)
         if true_triples is None:
             raise ValueError("KvsAllStep needs true_triples: the known triples its labels come from")
@@ -470,16 +486,16 @@ class DistanceAllStep(_AllEntityStep):
     accumulated; pRotatE: the modulus too) and returns the loss as a 0-dim device tensor.  ``positive_score`` [B, 1] of the last
     call stays available.  One library call (``mkb_dist_all_step`` / ``mkb_dist_all_filtered_step`` / ``mkb_dist_all_kvs_step``), no
     autograd, no negatives.  The score is no product here, so the backward recomputes the pair terms in two passes (DESIGN.md has
-    them); arguments of the call, optimizers and ``regularizer``: as for ``OneVsAllStep``.
+    them); arguments of the call, optimizers, ``regularizer`` and ``relation_prediction``: as for ``OneVsAllStep``.
 
     ``true_triples``: the known triples of a ``KvsAll`` marker, or of a ``OneVsAll(filter_known=True)``, that holds none."""
 
     family = _DIST
 
-    def __init__(self, model, loss, regularizer=None, true_triples=None):
+    def __init__(self, model, loss, regularizer=None, true_triples=None, relation_prediction=None):
         if not isinstance(loss, (one_vs_all.OneVsAll, kvs_all.KvsAll)):
             raise TypeError("DistanceAllStep takes losses.OneVsAll or losses.KvsAll")
-        super().__init__(model, regularizer)
+        super().__init__(model, regularizer, relation_prediction)
         self.loss = loss
         self.true_triples = loss.true_triples if loss.true_triples is not None else true_triples
         self.kvs = isinstance(loss, kvs_all.KvsAll)

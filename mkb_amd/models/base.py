@@ -366,6 +366,26 @@ class BaseModel(Base):
             self._make_current(sample, None)  # every entity row is read
         return score_all(self, sample, mode)
 
+    def score_relations(self, sample):
+        """float32 ``[B, n_relation]``: ``out[i, j]`` is the score of ``sample[i]`` with its relation replaced by relation ``j`` --
+        the bits ``utils.relation_scores`` hands out and, in column ``sample[i, 1]``, those of ``model(sample)`` -- differentiable
+        with respect to both tables and pRotatE's modulus (forward ``mkb_rel_scores``, backward ``mkb_rel_score_bwd``: the gradient
+        rows of the batch's heads and tails and every relation row, no float atomics).  The block ``losses.RelationPrediction``
+        takes its softmax over; ids are handled as in ``forward``."""
+        from ..losses.relation_prediction import RelationScoresFn
+
+        _hip.require_device(self.entity_embedding, sample)
+        if sample.dim() != 2 or sample.shape[1] != 3:
+            raise ValueError("sample must be [B, 3]")
+        sample = _hip.contiguous(sample, torch.int64)
+        if sample.shape[0] == 0:  # an empty batch: no launch; differentiable, backward adds nothing
+            return (self.entity_embedding.sum() * 0.0).expand(0, self.n_relation)
+        if VALIDATE_IDS:
+            self._launch_id_check(sample, None)
+        if _links.owner(self.entity_embedding) is not None or _links.owner(self.relation_embedding) is not None:
+            self._make_current(sample, sample[:, 0::2].reshape(-1), None)  # the heads and tails; every relation row is read
+        return RelationScoresFn.apply(self.entity_embedding, self.relation_embedding, _modulus_slot(self), self, sample)
+
     # ------------------------------------------------------------------ id validation
     def _launch_candidate_check(self, sample, cand, col):
         """``_launch_id_check`` for ``score_candidates``: the two columns of ``sample`` that are read, and the candidates against

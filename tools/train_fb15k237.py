@@ -5,6 +5,7 @@ FB15k-237 + RotatE hidden_dim=1000, K=256, batch 1024, Adversarial alpha=1, gamm
                                    [--loss adversarial|margin|pairwise|softmax|onevsall|kvsall] [--reg none|l2|n3] [--reg-weight 1e-3]
                                    [--optimizer adam|adagrad] [--label-smoothing 0.1] [--filter-known]
                                    [--sampler uniform|weighted|inbatch] [--sampler-power 0.75]
+                                   [--relation-prediction LAMBDA] [--relation-temperature T]
 
 --loss: adversarial (the default: Adversarial(--alpha) through FusedTrainStep), margin (MarginRanking(--gamma as the margin,
 --alpha)), pairwise (PairwiseLogistic(0, --alpha)) or softmax (CrossEntropy(--temperature)), the last three through
@@ -17,7 +18,8 @@ handed to the step.  --optimizer: adam (the default: row-lazy optim.Adam) or ada
 ComplEx / DistMult recipe is --loss softmax --reg n3 --optimizer adagrad --lr 0.1), both at --lr.  --sampler: uniform (the default:
 sampling.NegativeSampling, the reference's negatives), weighted (sampling.WeightedNegativeSampling: pool entries drawn with probability
 proportional to the entity's degree in the training triples to the power --sampler-power) or inbatch
-(sampling.InBatchNegativeSampling: the pool is 2 * --size of the batch's own tails / heads).
+(sampling.InBatchNegativeSampling: the pool is 2 * --size of the batch's own tails / heads).  --relation-prediction LAMBDA: the
+auxiliary term losses.RelationPrediction(LAMBDA, --relation-temperature), -log P(r | h, t) over all relations, handed to the step.
 
 Uses the public mkb_amd API only (models / sampling / losses / compose.Pipeline-equivalent loop / evaluation) plus
 the device batch producer.  Prints one JSON line per evaluation."""
@@ -55,6 +57,9 @@ def main():
     ap.add_argument("--optimizer", default="adam", choices=["adam", "adagrad"], help="optim.Adam(lazy_rows=True) or optim.Adagrad at --lr")
     ap.add_argument("--sampler", default="uniform", choices=["uniform", "weighted", "inbatch"])
     ap.add_argument("--sampler-power", type=float, default=0.75, help="--sampler weighted: p_e proportional to degree_e ** power")
+    ap.add_argument("--relation-prediction", type=float, default=None, metavar="LAMBDA",
+                    help="add losses.RelationPrediction(LAMBDA, --relation-temperature) to every step")
+    ap.add_argument("--relation-temperature", type=float, default=1.0)
     ap.add_argument("--no-defer", action="store_true", help="apply the optimizer step at once (one more launch per step)")
     args = ap.parse_args()
 
@@ -77,22 +82,23 @@ def main():
         opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr, lazy_rows=True, draw_ahead=ahead,
                          defer_step=not args.no_defer)  # gradients are cleared through opt.zero_grad() only: the step may wait
     reg = {"none": lambda: None, "l2": lambda: regularizers.L2(args.reg_weight), "n3": lambda: regularizers.N3(args.reg_weight)}[args.reg]()
+    rp = None if args.relation_prediction is None else losses.RelationPrediction(args.relation_prediction, args.relation_temperature)
     if args.loss == "adversarial":
-        step = FusedTrainStep(model, args.alpha, regularizer=reg)
+        step = FusedTrainStep(model, args.alpha, regularizer=reg, relation_prediction=rp)
     elif args.loss in ("onevsall", "kvsall") and args.model in DISTANCE_MODELS:  # the same flags, the distance models' step
         marker = (losses.OneVsAll(args.temperature, args.label_smoothing, args.filter_known) if args.loss == "onevsall"
                   else losses.KvsAll(label_smoothing=args.label_smoothing, reduction=args.reduction))
-        step = DistanceAllStep(model, marker, regularizer=reg, true_triples=ds.train)
+        step = DistanceAllStep(model, marker, regularizer=reg, true_triples=ds.train, relation_prediction=rp)
     elif args.loss == "onevsall":
         step = OneVsAllStep(model, temperature=args.temperature, regularizer=reg, label_smoothing=args.label_smoothing,
-                            true_triples=ds.train if args.filter_known else None)
+                            true_triples=ds.train if args.filter_known else None, relation_prediction=rp)
     elif args.loss == "kvsall":
-        step = KvsAllStep(model, ds.train, label_smoothing=args.label_smoothing, reduction=args.reduction, regularizer=reg)
+        step = KvsAllStep(model, ds.train, label_smoothing=args.label_smoothing, reduction=args.reduction, regularizer=reg, relation_prediction=rp)
     else:
         step = PooledLossStep(model, {"margin": lambda: losses.MarginRanking(margin=args.gamma, alpha=args.alpha),
                                       "pairwise": lambda: losses.PairwiseLogistic(margin=0.0, alpha=args.alpha),
                                       "softmax": lambda: losses.CrossEntropy(temperature=args.temperature)}[args.loss](),
-                              regularizer=reg)
+                              regularizer=reg, relation_prediction=rp)
     ev = evaluation.Evaluation(true_triples=ds.true_triples, entities=ds.entities, relations=ds.relations,
                                batch_size=1024, device="cuda", num_workers=0)
     n_steps, t_train = 0, 0.0
